@@ -2,13 +2,16 @@
 """Headline benchmark: sampled-edges/sec of the full GraphSAGE-mean TRAINING step
 (sample -> gather+mean -> dense -> loss -> backward -> [all-reduce] -> clip+Adam) on a synthetic
 Reddit-shaped graph (N=232,965, F=602, C=41, average degree 492, fan-out 25x10, batch 512 per GPU) --
-BASELINE.json configs[1] -- plus the micro-F1 half of the metric and short driver-visible runs of configs[2..4].
+BASELINE.json configs[1] -- and, with --full, the micro-F1 half of the metric and short driver-visible runs of configs[2..4].
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One JSON line on rank 0.  `value` = (edges all ranks sampled in K steps) / (max-over-ranks wall time),
 features/CSR/labels/epoch order resident in HBM before the timed region.  See DESIGN.md "Measurement".
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line has carried:
+HIP-event statistics, rooflines, the data-parallel schedule, the CPU baseline and micro-F1 legs and the `aux` runs.
+--dump-outputs DIR writes what the last timed step computed (loss, predictions, parameters) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -167,7 +170,14 @@ def parse_args(argv=None):
     ap.add_argument("--steps-per-launch", dest="steps_per_launch", type=int, default=None,
                     help="consecutive training steps replayed per hipGraph launch (default: 32 on one GPU -- measured "
                          "110.4 | 109.5 | 108.9 us/step at 8 | 16 | 32 --, 8 with the all-reduce recorded in the graph)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: HIP-event statistics, rooflines, the data-parallel schedule, the CPU baseline and "
+                         "micro-F1 legs and the `aux` runs (--no-cpu-baseline / --no-aux leave parts out)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, predictions, parameters) as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "rmat":
         given = set(a.split("=")[0] for a in (argv if argv is not None else sys.argv[1:]))
         for flag, val in (("--nodes", 10000000), ("--feat_dim", 256), ("--classes", 64), ("--samples_1", 15)):
@@ -180,6 +190,42 @@ def parse_args(argv=None):
 
 def roots_of(args):
     return (2 * args.batch_size + 20) if args.unsupervised else args.batch_size
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def output_arrays(args, fetched, params):
+    """{name: array} of what the last timed step hands its caller: the fetch of that step (model._fetch /
+    model._fetch_unsup) and the parameters it left (engine.params, flat).  Floats keep their dtype (float32 / float64),
+    integers become float64 (exact below 2**53)."""
+    if args.unsupervised:
+        loss, ranks, aff, mrr, outs = fetched
+        out = {"loss": loss, "mrr": mrr, "ranks": ranks, "aff": aff, "outputs1": outs}
+    else:
+        loss, preds = fetched
+        out = {"loss": loss, "preds": preds}
+    out["params"] = params
+    arrays = {}
+    for k, v in out.items():
+        v = np.asarray(v)
+        arrays[k] = v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)
+    return arrays
+
+
+def write_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """DIR/<name>.npy for every array; an array above its share of `max_bytes` is replaced by a fixed, seeded sample of
+    its flattened entries (same indices for the same shape).  Returns {name: shape written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = max_bytes // max(1, len(arrays))
+    written = {}
+    for k, v in sorted(arrays.items()):
+        if v.nbytes > share:
+            idx = np.sort(np.random.RandomState(0).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+        written[k] = list(v.shape)
+    return written
 
 
 def pmc_profile_path(args):
@@ -338,7 +384,7 @@ def main():
         # number of microseconds (0 = no-op hook)
         model.grad_hook = gsd.SpinHook(e, float(os.environ["GS_PROBE_DP_SCHEDULE"]))
     if model.grad_hook is not None:
-        dp_info = model.measure_dp_allreduce(log=log if rank == 0 else None) or {}
+        dp_info = (model.measure_dp_allreduce(log=log if rank == 0 else None) if args.full else None) or {}
         dp_info["allreduce"] = type(model.grad_hook).__name__
         dp_info["in_graph"] = bool(model._dp_in_graph())
         if hasattr(model.grad_hook, "ranks"):
@@ -385,7 +431,33 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
         torch.distributed.barrier()
-    loss_after = model._fetch_unsup(B)[0] if args.unsupervised else model._fetch(B)[0]
+    fetched = model._fetch_unsup(B) if args.unsupervised else model._fetch(B)
+    loss_after = fetched[0]
+    if args.dump_outputs and rank == 0:
+        written = write_outputs(args.dump_outputs, output_arrays(args, fetched, e.params.cpu().numpy()))
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, json.dumps(written)))
+
+    roots = (2 * B + 20) if args.unsupervised else B
+    edges_per_step = roots * (s2 + s2 * s1)
+    value = edges_per_step * world * args.steps / dt
+
+    metric, workload = describe(args, F, s1, s2, B, world)
+    result = {
+        "metric": metric,
+        "value": value, "unit": "sampled-edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "warmup_steps_run": warm_steps,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload,
+                   "global_batch": B * world, "parallelism": "dp%d" % world, "loss_after": loss_after,
+                   "steps_per_graph_launch": spl, "sampler_law": args.sampler_law, "max_degree": args.max_degree,
+                   "allreduce": dp_info["allreduce"] if dp_info else None,
+                   "rccl_ranks": dp_info.get("rccl_ranks") if dp_info else None},
+    }
+    if not args.full:
+        finish(result, rank, world, t_begin)
+        return
+
     # HIP events on the engine stream around the timed call, repeated -- the device-side duration of the same K
     # steps without the host's launch / synchronisation cost that the wall clock above carries (about 7 us per step at
     # K = 20); `value` stays the wall-clock figure.  All ranks run it (the steps all-reduce under N > 1); rank 0 reports.
@@ -423,23 +495,7 @@ def main():
                         "totals_in_order_us": [round((a + b + c) * 1e6, 1) for a, b, c in zip(t_call, t_wait, t_sync2)]}
         log("launch probe (K = %d): %s" % (args.steps, json.dumps(launch_probe)))
 
-    roots = (2 * B + 20) if args.unsupervised else B
-    edges_per_step = roots * (s2 + s2 * s1)
-    value = edges_per_step * world * args.steps / dt
-
-    metric, workload = describe(args, F, s1, s2, B, world)
-    result = {
-        "metric": metric,
-        "value": value, "unit": "sampled-edges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "warmup_steps_run": warm_steps,
-        "ms_per_step": dt / args.steps * 1e3, "ms_per_step_events": events, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload,
-                   "global_batch": B * world, "parallelism": "dp%d" % world, "loss_after": loss_after,
-                   "steps_per_graph_launch": spl, "sampler_law": args.sampler_law, "max_degree": args.max_degree,
-                   "allreduce": dp_info["allreduce"] if dp_info else None,
-                   "rccl_ranks": dp_info.get("rccl_ranks") if dp_info else None},
-    }
+    result["ms_per_step_events"] = events
     if launch_probe:
         result["launch_probe"] = launch_probe
     if dp_info:
@@ -616,6 +672,11 @@ def main():
     if headline and not args.no_aux:
         result["aux"] = run_aux(DG, args, B, s1, s2)
 
+    finish(result, rank, world, t_begin)
+
+
+def finish(result, rank, world, t_begin):
+    """Print the JSON line on rank 0 and take the process group down."""
     if rank == 0:
         result["bench_wall_s"] = time.time() - t_begin
         print(json.dumps(result), flush=True)

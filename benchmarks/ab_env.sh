@@ -13,7 +13,7 @@ for cfg in "${cfgs[@]}"; do
   i=0
   for envs in "$@"; do
     i=$((i+1))
-    env $envs timeout 300 python bench.py $args --warmup 5 --no-cpu-baseline --no-aux > $O/ab_${name}_$i.json 2> $O/ab_${name}_$i.err
+    env $envs timeout 300 python bench.py $args --warmup 5 --full --no-cpu-baseline --no-aux > $O/ab_${name}_$i.json 2> $O/ab_${name}_$i.err
     python - "$O/ab_${name}_$i.json" "$name" "$envs" <<'PY' | tee -a $O/ab.txt
 import json, sys
 try:

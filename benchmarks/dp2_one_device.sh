@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 run() { # name, "env -- args"
   name=$1; envs=${2%%--*}; args=${2#*--}
-  env $envs GS_FAULT_DUMP_S=80 GS_DIST_BACKEND=gloo timeout 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 295$((10 + RANDOM % 80)) bench.py --gpus 2 --warmup 8 --no-cpu-baseline --no-aux $args 2>$O/$name.err | tail -1 > $O/$name.json
+  env $envs GS_FAULT_DUMP_S=80 GS_DIST_BACKEND=gloo timeout 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 295$((10 + RANDOM % 80)) bench.py --gpus 2 --warmup 8 --full --no-cpu-baseline --no-aux $args 2>$O/$name.err | tail -1 > $O/$name.json
   python - $O/$name.json $name $O/$name.err <<'P'
 import json, sys, re
 try:

@@ -8,7 +8,7 @@ cd $R
 i=0
 for cfg in "" "GS_PROBE_DP_SCHEDULE=0" "GS_PROBE_DP_SCHEDULE=10" "GS_PROBE_DP_SCHEDULE=18" "GS_PROBE_DP_SCHEDULE=30" "$@"; do
   i=$((i+1))
-  env $cfg timeout 300 python bench.py --steps 96 --warmup 5 --no-cpu-baseline --no-aux --steps-per-launch 8 > $O/dp_$i.json 2> $O/dp_$i.err
+  env $cfg timeout 300 python bench.py --steps 96 --warmup 5 --full --no-cpu-baseline --no-aux --steps-per-launch 8 > $O/dp_$i.json 2> $O/dp_$i.err
   python - "$O/dp_$i.json" "$cfg" <<'PY'
 import json, sys
 try:

@@ -27,7 +27,7 @@ for v in d["configs"].values():
 json.dump(d, open(sys.argv[2], "w"), indent=1)
 PY
 cp $P/* $R/profiles/
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $P/${TAG}_f_driver_bench.json 2> $O/f_driver.err
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $P/${TAG}_f_driver_bench.json 2> $O/f_driver.err
 python - "$P/${TAG}_f_driver_bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

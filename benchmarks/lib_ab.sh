@@ -11,7 +11,7 @@ for cfg in "headline:--steps 200" "gcn:--model gcn --steps 96" "rmat:--workload 
   for lib in "$@"; do
     i=$((i+1))
     if [ -n "$lib" ]; then export GS_LIB=$R/$lib; else unset GS_LIB; fi
-    timeout 300 python bench.py $args --warmup 5 --no-cpu-baseline --no-aux > $O/lab_${name}_$i.json 2> $O/lab_${name}_$i.err
+    timeout 300 python bench.py $args --warmup 5 --full --no-cpu-baseline --no-aux > $O/lab_${name}_$i.json 2> $O/lab_${name}_$i.err
     python - "$O/lab_${name}_$i.json" "$name" "${lib:-in-tree}" <<'PY'
 import json, sys
 try:

@@ -13,8 +13,8 @@ if [ -n "$TESTS" ]; then
   echo "pytest rc=$?"; tail -3 $O/pytest.log
 fi
 # the driver's command, twice (the first one also pays the page-in of a fresh box)
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_driver_bench.json 2> $O/${TAG}_driver_bench.err
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-aux > $O/${TAG}_driver_bench2.json 2>> $O/${TAG}_driver_bench.err
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_driver_bench.json 2> $O/${TAG}_driver_bench.err
+timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-aux > $O/${TAG}_driver_bench2.json 2>> $O/${TAG}_driver_bench.err
 python - <<P
 import json
 for f in ("${TAG}_driver_bench.json", "${TAG}_driver_bench2.json"):
@@ -27,7 +27,7 @@ for f in ("${TAG}_driver_bench.json", "${TAG}_driver_bench2.json"):
 P
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/trh
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trh -o t -- python $R/bench.py --steps 96 --warmup 20 --no-cpu-baseline --no-aux > $O/${TAG}_headline_bench.json 2> $O/${TAG}_headline_bench.err
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trh -o t -- python $R/bench.py --steps 96 --warmup 20 --full --no-cpu-baseline --no-aux > $O/${TAG}_headline_bench.json 2> $O/${TAG}_headline_bench.err
 python $R/benchmarks/rocpd_stats.py $(ls $O/trh/*_results.db $O/trh/*/*_results.db 2>/dev/null | head -1) --md $O/${TAG}_bench_kernel_stats.md > /dev/null 2>&1
 rm -rf $O/trh
 head -30 $O/${TAG}_bench_kernel_stats.md

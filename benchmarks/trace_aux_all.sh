@@ -13,7 +13,7 @@ for cfg in maxpool unsup gcn rmat; do
     gcn) ARGS="--model gcn --steps 64";;
     rmat) ARGS="--workload rmat --steps 64";;
   esac
-  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trca -o t -- python $R/bench.py $ARGS --no-cpu-baseline --no-aux > $O/${TAG}_${cfg}_bench.json 2> $O/${TAG}_${cfg}_bench.err
+  timeout 400 rocprofv3 --kernel-trace --stats -d $O/trca -o t -- python $R/bench.py $ARGS --full --no-cpu-baseline --no-aux > $O/${TAG}_${cfg}_bench.json 2> $O/${TAG}_${cfg}_bench.err
   python $R/benchmarks/rocpd_stats.py $(ls $O/trca/*_results.db $O/trca/*/*_results.db 2>/dev/null | head -1) --md $O/${TAG}_${cfg}_kernel_stats.md > /dev/null 2>&1
   echo "$cfg: $(python -c "import json; d=json.load(open('$O/${TAG}_${cfg}_bench.json')); print('%.1f us/step (under the kernel trace)' % (d['ms_per_step']*1e3))" 2>&1 | tail -1)"
 done

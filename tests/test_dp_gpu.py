@@ -260,7 +260,7 @@ def test_bench_gpus_2_launches_its_own_ranks(dev):
         env.pop(k, None)
     env.update({"GS_DIST_BACKEND": "gloo", "GS_DP_NATIVE": "0", "GS_FAULT_DUMP_S": "280"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--nodes", "20000",
-           "--avg_degree", "40", "--no-cpu-baseline", "--no-aux"]
+           "--avg_degree", "40", "--full", "--no-cpu-baseline", "--no-aux"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -176,6 +176,50 @@ def test_bench_json_strings_format():
     assert "RMAT 10M-node/200M-edge" in metric and "15x10" in metric and "E=200000000" in workload
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(__file__), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_and_full_options():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` is the headline alone: --full (off by default) adds the other
+    measurements, --dump-outputs names the directory of the last timed step's arrays, and --steps is at least one step."""
+    bench = _bench_module()
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 3, False, None)
+    args = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert args.full and args.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_bench_output_arrays_dtypes_and_size_cap(tmp_path):
+    """--dump-outputs writes float32 / float64 .npy files only (integers as float64), and an array above its share of the
+    64 MB budget is replaced by the same seeded sample of its entries on every run."""
+    bench = _bench_module()
+    args = bench.parse_args([])
+    preds = np.random.RandomState(1).rand(4, 3).astype(np.float32)
+    arrays = bench.output_arrays(args, (0.5, preds), np.arange(10, dtype=np.float32))
+    assert sorted(arrays) == ["loss", "params", "preds"]
+    assert arrays["loss"].dtype == np.float64 and arrays["preds"].dtype == np.float32
+    args = bench.parse_args(["--unsupervised"])
+    arrays = bench.output_arrays(args, (0.5, np.arange(4), preds, 0.25, preds), np.zeros(3, np.float32))
+    assert sorted(arrays) == ["aff", "loss", "mrr", "outputs1", "params", "ranks"]
+    assert arrays["ranks"].dtype == np.float64 and np.array_equal(arrays["ranks"], np.arange(4))
+    big = np.arange(1000, dtype=np.float64)
+    shapes = bench.write_outputs(str(tmp_path / "a"), {"big": big, "small": preds}, max_bytes=2 * 800)
+    assert shapes == {"big": [100], "small": [4, 3]}
+    a = np.load(str(tmp_path / "a" / "big.npy"))
+    assert a.dtype == np.float64 and np.all(np.diff(a) > 0) and set(a.tolist()) <= set(big.tolist())
+    bench.write_outputs(str(tmp_path / "b"), {"big": big, "small": preds}, max_bytes=2 * 800)
+    assert np.array_equal(a, np.load(str(tmp_path / "b" / "big.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "a" / "small.npy")), preds)
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["big.npy", "small.npy"]
+
+
 def test_single_hip_runtime_mapped():
     """Loading the C-ABI library before torch must not map a second libamdhip64 (torch bundles its own copy; two HIP
     runtimes in one process cannot share streams or memory).  _lib.load() imports torch first for that reason."""

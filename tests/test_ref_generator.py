@@ -1,34 +1,12 @@
-"""The committed tests/golden/ref_*.npz ARE what the generator writes when it executes /root/reference (skipped where the
-reference is absent, e.g. on the GPU box), and the TF1 stand-in the generator runs on behaves like TensorFlow 1.x on the
-documented points the reference relies on."""
+"""The TF1 stand-in that tests/golden/make_ref_fixtures.py runs the reference on behaves like TensorFlow 1.x on the
+documented points the reference relies on, and nothing in the product imports it or the fixtures."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = os.environ.get("GRAPHSAGE_REFERENCE", "/root/reference")
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "graphsage")), reason="reference sources not present")
-def test_generator_reproduces_committed_fixtures(tmp_path):
-    gen = os.path.join(HERE, "golden", "make_ref_fixtures.py")
-    subprocess.run([sys.executable, gen], check=True, env=dict(os.environ, REF_FIXTURE_DIR=str(tmp_path)),
-                   stdout=subprocess.DEVNULL)
-    names = sorted(f for f in os.listdir(tmp_path) if f.startswith("ref_"))
-    committed = sorted(f for f in os.listdir(os.path.join(HERE, "golden")) if f.startswith("ref_"))
-    assert names == committed and len(names) >= 13
-    for f in names:
-        a, b = np.load(os.path.join(tmp_path, f)), np.load(os.path.join(HERE, "golden", f))
-        assert sorted(a.files) == sorted(b.files), f
-        for k in a.files:
-            if a[k].dtype.kind == "f":        # BLAS thread counts may differ between runs of the generator
-                np.testing.assert_allclose(a[k], b[k], rtol=1e-5 if a[k].dtype == np.float32 else 1e-12,
-                                           atol=1e-6 if a[k].dtype == np.float32 else 1e-13, err_msg=f + ":" + k)
-            else:
-                assert np.array_equal(a[k], b[k]), f + ":" + k
 
 
 def test_nothing_in_the_product_imports_the_shim_or_the_fixtures():
