@@ -15,7 +15,7 @@ ACT_RELU = 1
 LAW_IID, LAW_REFERENCE, LAW_DISTINCT = 0, 1, 2      # GS_LAW_* (sampling law of the CSR sampler)
 SAMPLER_LAWS = {"iid": LAW_IID, "reference": LAW_REFERENCE, "distinct": LAW_DISTINCT}
 GS_PEER_HANDLE_BYTES = 64
-GS_ABI_VERSION = 10     # must equal GS_ABI_VERSION of include/graphsage_amd.h (struct layouts below mirror that header)
+GS_ABI_VERSION = 11     # must equal GS_ABI_VERSION of include/graphsage_amd.h (struct layouts below mirror that header)
 
 
 class GraphsageAmdError(RuntimeError):
@@ -142,6 +142,9 @@ _PROTOS = {
     "gs_maxpool_sparse_wgrad": [_P, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, c_int64, c_int32, c_int32, _P,
                                 c_int64, _P],
     "gs_stage_batch": [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, _P, c_int64, _P],
+    "gs_lstm_lengths": [_P, c_int32, c_int32, _P, _P],
+    "gs_lstm_fwd": [_P, c_int32, c_int32, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gs_lstm_bwd": [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
 }
 
 
@@ -224,6 +227,17 @@ class VarDesc(ctypes.Structure):
     """struct gs_var_desc (include/graphsage_amd.h)"""
     _fields_ = [("offset", c_int64), ("size", c_int64), ("slabs", c_void_p), ("n_slabs", c_int32), ("decay", c_int32),
                 ("clear", c_int32), ("reserved_", c_int32)]
+
+GS_LSTM_MAX_SEG = 4
+
+
+class LstmSeg(ctypes.Structure):
+    """struct gs_lstm_seg (include/graphsage_amd.h)"""
+    _fields_ = [("X", c_void_p), ("ids", c_void_p), ("ldx", c_int64), ("n", c_int64), ("row0", c_int64), ("seq0", c_int64),
+                ("T", c_int32), ("reserved_", c_int32)]
+
+
+assert ctypes.sizeof(LstmSeg) == 56      # static_assert in csrc/gs_lstm.hip (passed by pointer, not in gs_abi_struct_sizes)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -1,4 +1,4 @@
-"""Mean / GCN / MaxPooling / MeanPooling aggregators with the constructor and call signatures of
+"""Mean / GCN / MaxPooling / MeanPooling / Seq (LSTM) aggregators with the constructor and call signatures of
 graphsage/aggregators.py, executing on the gfx950 kernels.
 
     agg = MeanAggregator(input_dim, output_dim, act=..., dropout=..., name=..., concat=..., model_size=...)
@@ -762,3 +762,139 @@ class MaxPoolingAggregator(_PoolingAggregator):
 class MeanPoolingAggregator(_PoolingAggregator):
     """Aggregates via mean-pooling over MLP functions (aggregators.py:197-273)."""
     POOL = "mean"
+
+
+class SeqAggregator(_SageBase):
+    """Aggregates via a standard LSTM (aggregators.py:363-449): TF 1.x BasicLSTMCell(H) run by dynamic_rnn over the s sampled
+    neighbors of each node, for the first L = max(1, #non-zero neighbor rows) steps (aggregators.py:411-414); the hidden state
+    after step L - 1 is the neighborhood vector, then the SAGE matmuls.  H = 128 ("small") or 256 ("big").  SeqAggregator._call
+    applies no dropout.
+
+    The cell's kernel [neigh_in + H, 4H] and bias [4H] are NOT in aggregator.vars (no weight decay; still clipped and
+    updated by Adam).  The kernel is held as two variables, its x_t rows (`lstm_wx`) and its h_{t-1} rows (`lstm_wh`): a
+    weight gradient's operand has the variable's row count, and clip + Adam are elementwise, so the split changes no result.
+    Every hop of a layer shares one cell, as the reference's reused variable scope does.
+
+    Per layer: G = X . W_x + b over every neighbor row (one contraction per contiguous piece), the lengths, ONE recurrence launch
+    over all hops (gs_lstm_fwd; the activated gates overwrite G), then [self . W_self | h_last . W_neigh].  The backward runs
+    the recurrence in reverse (gs_lstm_bwd; dG overwrites the gates) and sends dG through the ordinary weight-gradient and
+    input-gradient contractions."""
+
+    def __init__(self, input_dim, output_dim, model_size="small", neigh_input_dim=None, dropout=0., bias=False,
+                 act=relu, name=None, concat=False, **kwargs):
+        super(SeqAggregator, self).__init__(**kwargs)
+        self.dropout = dropout
+        self.bias = bias
+        self.act = act
+        self.act_code = _act_code(act)
+        self.concat = concat
+        if neigh_input_dim is None:
+            neigh_input_dim = input_dim
+        if model_size == "small":
+            hidden_dim = self.hidden_dim = 128
+        elif model_size == "big":
+            hidden_dim = self.hidden_dim = 256
+        else:
+            raise ops._lib.GraphsageAmdError("model_size must be 'small' or 'big'")
+        if bias and concat:
+            # the reference adds a [output_dim] bias to the [n, 2 * output_dim] concatenation, which TF refuses
+            raise ops._lib.GraphsageAmdError("SeqAggregator: bias needs concat=False (the bias has output_dim entries)")
+        scope = _scope(self.name, name)
+        e = self.engine
+        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((hidden_dim, output_dim)), decay=True)
+        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
+        if self.bias:
+            self.vars['bias'] = e.add_variable(scope + '/bias', zeros((output_dim,)), decay=True)
+        kernel = glorot((neigh_input_dim + hidden_dim, 4 * hidden_dim))       # BasicLSTMCell kernel (glorot over the whole)
+        cell = self.name + '/rnn/basic_lstm_cell'
+        self.lstm_wx = e.add_variable(cell + '/kernel_x', kernel[:neigh_input_dim], decay=False)
+        self.lstm_wh = e.add_variable(cell + '/kernel_h', kernel[neigh_input_dim:], decay=False)
+        self.lstm_b = e.add_variable(cell + '/bias', zeros((4 * hidden_dim,)), decay=False)
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        self.neigh_input_dim = neigh_input_dim
+        self._saved = []
+
+    def prefetch(self, self_all, neighs, tag=0):
+        return None   # the recurrence needs the weights: nothing can run ahead
+
+    def prefetch_jobs(self, self_all, neighs, tag=0):
+        return None, []
+
+    def call_hops(self, self_all, neighs, means=None, side_jobs=None):
+        e = self.engine
+        _run_jobs(e, side_jobs)
+        n_total = self_all.n
+        k = len(self._saved)
+        H = self.hidden_dim
+        flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
+        x_all = _contiguous(flat)
+        pieces = [x_all] if x_all is not None else flat
+        rows_total = sum(x.n for x in flat)
+        # one recurrence segment per hop: n sequences of s steps, step rows in the hop's order of the flattened neighbors
+        segs, row0 = [], 0
+        for nv in neighs:
+            n, s, _ = nv.shape3
+            segs.append((nv.src, nv.ids, n, s, row0))
+            row0 += n * s
+        G = e.ws_mat((self.name, "lstm_gates", k), rows_total, 4 * H)
+        r = 0
+        for x in pieces:        # [x_t, h_{t-1}] . kernel + bias, the x_t half for every step at once
+            ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, self.lstm_wx.value, 4 * H, False, ACT_IDENTITY,
+                               self.lstm_b.value.buf, G.rows_slice(r, r + x.n), stream=e.stream)
+            r += x.n
+        lengths = e.ws_i32((self.name, "lstm_len", k), n_total)
+        ops.lstm_lengths(segs, neighs[0].shape3[2], lengths, stream=e.stream)
+        C = e.ws_mat((self.name, "lstm_c", k), rows_total, H)
+        Hp = e.ws_mat((self.name, "lstm_h_prev", k), rows_total, H)
+        h_last = e.ws_mat((self.name, "lstm_h_last", k), n_total, H)
+        ops.lstm_fwd(segs, H, self.lstm_wh.value, lengths, G, G, C, Hp, h_last, stream=e.stream)
+        # from_self / from_neighs + concat|add + bias + act (aggregators.py:437-449): one launch for all hops
+        n_out = self.output_dim * (2 if self.concat else 1)
+        out = e.ws_mat((self.name, "out", k), n_total, n_out)
+        b = self.vars['bias'].value.buf if self.bias else None
+        ops.sage_dense_fwd(self_all.src, self_all.ids, h_last, None, n_total, self.vars['self_weights'].value,
+                           self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b, out,
+                           stream=e.stream)
+        self._push((self_all, neighs, pieces, segs, rows_total, lengths, G, C, Hp, h_last, out))
+        return out
+
+    def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
+        e = self.engine
+        self_all, neighs, pieces, segs, rows_total, lengths, A, C, Hp, h_last, out = self._saved.pop()
+        if embed_sink is not None:
+            raise ops._lib.GraphsageAmdError("SeqAggregator: trainable identity features are not supported")
+        n_total = self_all.n
+        k = len(self._saved)
+        H = self.hidden_dim
+        o = self.output_dim
+        n_out = o * (2 if self.concat else 1)
+        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
+        col_n = o if self.concat else 0
+        e.wgrad(self.vars['self_weights'], self_all.src, self_all.ids, dz, 0, n_total)
+        e.wgrad(self.vars['neigh_weights'], h_last, None, dz, col_n, n_total)
+        if self.bias:
+            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        dh_last = e.ws_mat((self.name, "d_lstm_h_last", k), n_total, H)
+        ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, dh_last, stream=e.stream)
+        wt = e.ws_f32((self.name, "lstm_wh_t"), 4 * H * H)
+        dG = ops.lstm_bwd(segs, H, self.lstm_wh.value, wt, lengths, A, C, dh_last, A, stream=e.stream)   # dG over the gates
+        e.wgrad(self.lstm_wh, Hp, None, dG, 0, rows_total)
+        e.bgrad(self.lstm_b, dG, rows_total, 4 * H)
+        r = 0
+        for x in pieces:
+            e.wgrad(self.lstm_wx, x.src, x.ids, dG.rows_slice(r, r + x.n), 0, x.n)
+            r += x.n
+        if d_prev is None:
+            return
+        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
+        ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value, d_self_all, stream=e.stream)
+        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
+        ops.dense_dgrad(dG, 0, 4 * H, rows_total, self.lstm_wx.value, d_neigh, stream=e.stream)
+        pull, hr = [], 0
+        for h, nv in enumerate(neighs):         # every neighbor row has its own gradient row (s = 1)
+            n, s, _ = nv.shape3
+            pull.append((d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0))
+            hr += n * s
+        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=pull,
+                            mask_y=prev_mask, stream=e.stream)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .aggregators import GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator
+from .aggregators import GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator, SeqAggregator
 from .engine import get_engine
 from .inits import glorot
 from .layers import Rows, identity
@@ -36,13 +36,12 @@ _AGGREGATORS = {
     "maxpool": MaxPoolingAggregator,
     "meanpool": MeanPoolingAggregator,
     "gcn": GCNAggregator,
+    "seq": SeqAggregator,
 }
 
 
 def _aggregator_cls(aggregator_type):
-    """Dispatch of models.py:211-222 / supervised_models.py:34-45 ('seq' is out of scope, SURVEY §2 #11)."""
-    if aggregator_type == "seq":
-        raise NotImplementedError("SeqAggregator (LSTM) is outside the MI355X hot-path scope")
+    """Dispatch of models.py:211-222 / supervised_models.py:34-45."""
     if aggregator_type not in _AGGREGATORS:
         raise Exception("Unknown aggregator: ", aggregator_type)
     return _AGGREGATORS[aggregator_type]
@@ -92,6 +91,9 @@ class SampleAndAggregate(object):
         self.model_size = model_size
         self.adj_info = adj
         self.identity_dim = int(identity_dim)
+        if aggregator_type == "seq" and self.identity_dim > 0:
+            # the LSTM's input gradients would have to reach the trainable table columns through every step: not built
+            raise ops._lib.GraphsageAmdError("identity_dim > 0 is not supported with the LSTM aggregator (graphsage_seq)")
         self._init_features(features, adj, self.identity_dim)
         self.degrees = degrees
         self.concat = concat

@@ -640,6 +640,59 @@ def linkpred_tail_neg(desc, loss_out=None, accumulate=False, mrr_out=None, count
          cs[0][0], cs[0][1], cs[1][0], cs[1][1], cs[2][0], cs[2][1], ctypes.addressof(jarr), len(jobs), _s(stream))
 
 
+# ------------------------------------------------------------------------------------------ LSTM aggregator (gs_lstm.hip)
+def lstm_segments(segs):
+    """segs: [(X Mat | None, ids int32 tensor | None, n sequences, T steps, row0)] -> (struct gs_lstm_seg array, number of
+    sequences, number of step rows).  Sequence rows (lengths, h_last, dh_last) follow the segments' order."""
+    assert 1 <= len(segs) <= _lib.GS_LSTM_MAX_SEG, len(segs)
+    arr = (_lib.LstmSeg * len(segs))()
+    seq0 = rows = 0
+    for k, (X, ids, n, T, row0) in enumerate(segs):
+        assert n >= 0 and T >= 1 and row0 >= 0
+        if ids is not None:
+            assert ids.dtype == torch.int32 and ids.is_contiguous() and ids.numel() >= n * T
+        elif X is not None:
+            assert X.rows >= n * T
+        arr[k].X, arr[k].ids = (X.ptr, X.ld) if X is not None else (None, 0)
+        arr[k].ids = ptr(ids)
+        arr[k].ldx = X.ld if X is not None else 0
+        arr[k].n, arr[k].row0, arr[k].seq0, arr[k].T = n, row0, seq0, T
+        seq0 += n
+        rows = max(rows, row0 + n * T)
+    return arr, seq0, rows
+
+
+def lstm_lengths(segs, d, lengths, stream=None):
+    """lengths[r] = max(1, #{t : row t of sequence r is not all zeros}) (aggregators.py:411-414)."""
+    arr, n_total, _ = lstm_segments(segs)
+    assert lengths.dtype == torch.int32 and lengths.numel() >= n_total
+    assert all(X is not None and X.d >= d for X, _, n, _, _ in segs if n > 0)
+    call("gs_lstm_lengths", ctypes.addressof(arr), len(segs), d, ptr(lengths), _s(stream))
+    return lengths
+
+
+def lstm_fwd(segs, H, W_h, lengths, G, A, C, H_prev, h_last, stream=None):
+    """Forward recurrence of BasicLSTMCell under dynamic_rnn (gs_lstm_fwd); A may be G (in place)."""
+    arr, n_total, rows = lstm_segments(segs)
+    assert W_h.rows == H and W_h.d == 4 * H and lengths.numel() >= n_total
+    assert min(G.rows, A.rows, C.rows, H_prev.rows) >= rows and h_last.rows >= n_total
+    assert G.d >= 4 * H and A.d >= 4 * H and C.d >= H and H_prev.d >= H and h_last.d >= H
+    call("gs_lstm_fwd", ctypes.addressof(arr), len(segs), H, W_h.ptr, W_h.ld, ptr(lengths), G.ptr, G.ld, A.ptr, A.ld,
+         C.ptr, C.ld, H_prev.ptr, H_prev.ld, h_last.ptr, h_last.ld, _s(stream))
+    return h_last
+
+
+def lstm_bwd(segs, H, W_h, wt_ws, lengths, A, C, dh_last, dG, stream=None):
+    """Backward recurrence (gs_lstm_bwd): dG = d loss / d(gate pre-activations), zero past each length; dG may be A."""
+    arr, n_total, rows = lstm_segments(segs)
+    assert W_h.rows == H and W_h.d == 4 * H and lengths.numel() >= n_total and wt_ws.numel() >= 4 * H * H
+    assert min(A.rows, C.rows, dG.rows) >= rows and dh_last.rows >= n_total
+    assert A.d >= 4 * H and C.d >= H and dh_last.d >= H and dG.d >= 4 * H
+    call("gs_lstm_bwd", ctypes.addressof(arr), len(segs), H, W_h.ptr, W_h.ld, ptr(wt_ws), ptr(lengths), A.ptr, A.ld,
+         C.ptr, C.ld, dh_last.ptr, dh_last.ld, dG.ptr, dG.ld, _s(stream))
+    return dG
+
+
 # ------------------------------------------------------------------------------------------ K6
 def reduce_slabs(slabs, n_slabs, slab_stride, rows, cols, ld_slab, weight_decay, w_ptr, ldw, grad_ptr, ldg,
                  accumulate=False, stream=None):

@@ -4,7 +4,7 @@ graphsage/unsupervised_train.py (flags :25-55, loop :246-316, save_val_embedding
     python -m graphsage_amd.unsupervised_train --train_prefix ./example_data/toy-ppi --model graphsage_mean --max_total_steps 1000
     python -m graphsage_amd.unsupervised_train --synthetic small --model graphsage_mean --epochs 1
 
-Models: graphsage_mean | gcn | graphsage_maxpool | graphsage_meanpool (graphsage_seq and n2v are out of scope).
+Models: graphsage_mean | gcn | graphsage_seq | graphsage_maxpool | graphsage_meanpool (n2v is out of scope).
 """
 from __future__ import division, print_function
 
@@ -158,6 +158,11 @@ def train(G, context_pairs):
                        SAGEInfo("node", sampler, FLAGS.samples_2, 2 * FLAGS.dim_2)]
         model = SampleAndAggregate(placeholders, features, adj_info, minibatch.deg, layer_infos=layer_infos,
                                    aggregator_type="gcn", concat=False, **kw)
+    elif FLAGS.model == 'graphsage_seq':                         # :183-198
+        layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
+                       SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
+        model = SampleAndAggregate(placeholders, features, adj_info, minibatch.deg, layer_infos=layer_infos,
+                                   aggregator_type="seq", **kw)
     elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool'):   # :203-230
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]

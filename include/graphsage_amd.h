@@ -38,7 +38,7 @@ extern "C" {
 #define GS_ACT_IDENTITY 0
 #define GS_ACT_RELU 1
 
-#define GS_ABI_VERSION 10
+#define GS_ABI_VERSION 11
 
 const char* gs_last_error(void);
 int gs_abi_version(void);
@@ -701,6 +701,40 @@ int gs_scatter_add_rows(const float* d, int64_t ldd, int64_t n, int32_t s, int32
 /* dst[r, 0:cols] = src[r, 0:cols]: refreshes the embedding columns of the combined feature table (the
  * tf.concat([embeds, features], axis=1) of models.py:240, kept materialised) after an optimizer step. */
 int gs_copy_cols(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t rows, int32_t cols, void* stream);
+
+/* ---- LSTM aggregator (SeqAggregator, aggregators.py:363-449; ABI 11, csrc/gs_lstm.hip) ----------------------------------
+ * TF 1.x BasicLSTMCell (gate order i, j, f, o; forget_bias 1.0 added at call time) under dynamic_rnn(sequence_length = L):
+ *   [i j f o] = G[r, t] + h_{t-1} . W_h,  c_t = c_{t-1} sigma(f + 1) + sigma(i) tanh(j),  h_t = tanh(c_t) sigma(o),
+ * zero initial state, steps t < L_r run, h_last[r] = h_{L_r - 1}.  G = X . W_x + b (the input projection of every step's row)
+ * and all weight / input gradients are ordinary contractions (gs_sage_dense_fwd, gs_dense_wgrad*, gs_dense_dgrad).
+ * One launch covers every hop of a layer: segment k holds n sequences of T steps; the step rows of sequence r of segment k
+ * are row0 + r*T + t of the [rows, *] step arrays (G, A, C, H_prev, dG); its row of lengths / h_last / dh_last is
+ * seq0 + r (seq0 = the sequences of the segments before it).  Hidden size H in {128, 256}.
+ * gs_lstm_seg is 56 bytes on every target (checked at compile time here and by the binding). */
+#define GS_LSTM_MAX_SEG 4
+typedef struct gs_lstm_seg {
+    const float* X;        /* gs_lstm_lengths only: the segment's input rows X[ids ? ids[i] : i], i < n*T */
+    const int32_t* ids;    /* nullable */
+    int64_t ldx;
+    int64_t n;             /* sequences */
+    int64_t row0;          /* first step row of the segment */
+    int64_t seq0;          /* first sequence row of the segment (== sum of n of the segments before it) */
+    int32_t T;             /* steps (>= 1) */
+    int32_t reserved_;
+} gs_lstm_seg;
+/* lengths[seq0 + r] = max(1, #{t < T : some x[r, t, c] != 0, c < d})     (aggregators.py:411-414) */
+int gs_lstm_lengths(const gs_lstm_seg* segs_host, int32_t n_seg, int32_t d, int32_t* lengths, void* stream);
+/* Forward recurrence.  W_h: [H, 4H]; G: [rows, 4H] pre-activations from the input projection; writes the activated gates
+ * A [rows, 4H] (A may alias G), the cell states C [rows, H], the previous hidden states H_prev [rows, H] (0 for t >= L_r)
+ * and h_last [n_total, H].  Step rows t >= L_r of A and C are left untouched. */
+int gs_lstm_fwd(const gs_lstm_seg* segs_host, int32_t n_seg, int32_t H, const float* W_h, int64_t ldw, const int32_t* lengths,
+                const float* G, int64_t ldg, float* A, int64_t lda, float* C, int64_t ldc, float* H_prev, int64_t ldhp,
+                float* h_last, int64_t ldh, void* stream);
+/* Backward recurrence (BPTT) from dh_last [n_total, H]: dG [rows, 4H] = d loss / d(pre-activations), zero for t >= L_r
+ * (dG may alias A).  W_hT_ws: caller scratch of 4H * H floats (W_h^T, written by the launch). */
+int gs_lstm_bwd(const gs_lstm_seg* segs_host, int32_t n_seg, int32_t H, const float* W_h, int64_t ldw, float* W_hT_ws,
+                const int32_t* lengths, const float* A, int64_t lda, const float* C, int64_t ldc, const float* dh_last,
+                int64_t lddh, float* dG, int64_t lddg, void* stream);
 
 /* Input gradient of one aggregator layer w.r.t. the previous layer's hidden rows, in ONE launch ("pull" form: every
  * output row sums the contributions it receives, so no accumulation order is involved):
