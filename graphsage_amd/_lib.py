@@ -15,7 +15,7 @@ ACT_RELU = 1
 LAW_IID, LAW_REFERENCE, LAW_DISTINCT = 0, 1, 2      # GS_LAW_* (sampling law of the CSR sampler)
 SAMPLER_LAWS = {"iid": LAW_IID, "reference": LAW_REFERENCE, "distinct": LAW_DISTINCT}
 GS_PEER_HANDLE_BYTES = 64
-GS_ABI_VERSION = 11     # must equal GS_ABI_VERSION of include/graphsage_amd.h (struct layouts below mirror that header)
+GS_ABI_VERSION = 12     # must equal GS_ABI_VERSION of include/graphsage_amd.h (struct layouts below mirror that header)
 
 
 class GraphsageAmdError(RuntimeError):
@@ -145,6 +145,13 @@ _PROTOS = {
     "gs_lstm_lengths": [_P, c_int32, c_int32, _P, _P],
     "gs_lstm_fwd": [_P, c_int32, c_int32, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gs_lstm_bwd": [_P, c_int32, c_int32, _P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gs_n2v_stage": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_uint64, _P, c_int64, _P, c_int32, _P, _P, _P],
+    "gs_n2v_supported": [c_int32, c_int32],
+    "gs_n2v_slabs": [c_int64, c_int32, c_int32],
+    "gs_n2v_fwd_bwd": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_int, _P, _P, _P, c_int64, _P,
+                       c_int64, _P, _P, _P, _P, _P, _P],
+    "gs_n2v_apply": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int32,
+                     _P, _P, _P, _P, _P, c_uint64, _P, c_uint64, _P],
 }
 
 

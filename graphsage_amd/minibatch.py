@@ -124,12 +124,14 @@ class EdgeMinibatchIterator(object):
     G -- GraphData;  id2idx -- ignored (identity);  placeholders -- dict of feed slots
     context_pairs -- if not None, an int array [n, 2] of co-occurring node pairs (from random walks)
     batch_size -- size of the minibatches;  max_degree -- size of the padded adjacency lists
+    n2v_retrain -- the iterator retrains the node2vec baseline on walks from the val / test nodes (minibatch.py:39-58):
+        pairs with an isolated endpoint are kept and the validation pairs are the training pairs
+    fixed_n2v -- with n2v_retrain: only pairs whose SECOND node is a train node are kept (_n2v_prune), so that only
+        existing nodes serve as context
     """
 
     def __init__(self, G, id2idx, placeholders, context_pairs=None, batch_size=100, max_degree=25, n2v_retrain=False,
                  fixed_n2v=False, build_padded=True, **kwargs):
-        if n2v_retrain:
-            raise NotImplementedError("the node2vec baseline is out of scope (SURVEY §2 #12)")
         self.G = G
         self.id2idx = id2idx
         self.placeholders = placeholders
@@ -153,11 +155,20 @@ class EdgeMinibatchIterator(object):
         else:
             edges = np.asarray(context_pairs, dtype=np.int32).reshape(-1, 2)
         self.train_edges = self.edges = np.random.permutation(edges)
-        self.train_edges = self._remove_isolated(self.train_edges)
-        self.val_edges = np.stack([G.src, G.dst], axis=1)[G.train_removed]          # minibatch.py:45
+        if not n2v_retrain:
+            self.train_edges = self._remove_isolated(self.train_edges)
+            self.val_edges = np.stack([G.src, G.dst], axis=1)[G.train_removed]      # minibatch.py:45
+        elif fixed_n2v:
+            self.train_edges = self.val_edges = self._n2v_prune(self.edges)         # :47-48
+        else:
+            self.train_edges = self.val_edges = self.edges                          # :49-50
         print(int((~no_train & G.present).sum()), 'train nodes')
         print(int(no_train.sum()), 'test nodes')
         self.val_set_size = len(self.val_edges)
+
+    def _n2v_prune(self, edges):
+        """minibatch.py:56-58: keep the pairs whose second node is neither a val nor a test node."""
+        return edges[~(self.G.val_mask | self.G.test_mask)[edges[:, 1]]]
 
     def _remove_isolated(self, edge_list):
         """minibatch.py:60-74: drop pairs with a zero-train-degree endpoint unless an endpoint is a test node."""

@@ -965,3 +965,271 @@ class SampleAndAggregate(object):
             for a in self.aggregators:
                 a.reset()
         self._tape = None
+
+
+class Node2VecModel(object):
+    """Simple version of the Node2Vec / DeepWalk algorithm (graphsage/models.py:408-504) on the gfx950 engine: trainable
+    target / context embedding tables [dict_size, nodevec_dim] and a context bias [dict_size], trained by plain SGD on the
+    skip-gram cross-entropy against `neg_sample_size` DISTINCT degree^0.75 negatives shared by the batch.
+
+        loss, ranks, aff_all, mrr, outputs1 = model.train_step(feed_dict)   # unsupervised_train.py:273-274
+        loss, ranks, mrr, outputs1 = model.eval_step(feed_dict)             # no update (evaluate, save_val_embeddings)
+
+    dict_size: rows of the tables (the driver passes N + 1, the pad row included); degrees: the N TRAIN degrees (the
+    unigrams of the negative sampler); nodevec_dim in {64, 128, 256, 512}; lr: the SGD learning rate.  The reference reads
+    FLAGS.neg_sample_size; here it is the keyword neg_sample_size.  A step is three launches (csrc/gs_n2v.hip): staging |
+    forward + gradient rows | sparse apply; the tables are updated in place and never copied.  identity_dim, dropout and
+    weight_decay have no meaning for this model, as in the reference.  Data-parallel training needs a sparse exchange and
+    is refused.  Initial values come from a seeded host stream; device_init=True draws the same distributions with torch's
+    generator on the device instead (tables of 10^7 rows would take minutes to draw and upload from the host)."""
+
+    def __init__(self, placeholders, dict_size, degrees, name=None, nodevec_dim=50, lr=0.001, neg_sample_size=20, seed=123,
+                 grad_hook=None, world_size=1, device_init=False, **kwargs):
+        if grad_hook is not None or int(world_size) > 1:
+            raise NotImplementedError("Node2VecModel is single-GPU: its sparse row updates have no gradient exchange")
+        self.engine = e = get_engine()
+        self.name = name or "node2vecmodel"
+        self.placeholders = placeholders
+        self.degrees = np.asarray(degrees)
+        self.dict_size = int(dict_size)
+        self.hidden_dim = d = int(nodevec_dim)
+        self.lr = float(lr)
+        self.neg_sample_size = n_neg = int(neg_sample_size)
+        lib = ops._lib.load()
+        if not lib.gs_n2v_supported(d, n_neg):
+            raise ops._lib.GraphsageAmdError(
+                "Node2VecModel: nodevec_dim = 2 * dim_1 must be one of 64 / 128 / 256 / 512 and neg_sample_size must fit "
+                "LDS beside the workgroup's rows (got nodevec_dim=%d, neg_sample_size=%d)" % (d, n_neg))
+        if len(self.degrees) > self.dict_size:
+            raise ValueError("Node2VecModel: %d degrees for a table of %d rows" % (len(self.degrees), self.dict_size))
+        # following the tensorflow word2vec tutorial (models.py:434-445): uniform [-1, 1), truncated normal (draws beyond two
+        # standard deviations are re-drawn) with stddev 1 / sqrt(d), zeros -- from a seeded host stream
+        if device_init:
+            gen = torch.Generator(device=e.device)
+            gen.manual_seed(seed)
+            self.target_embeds = torch.rand((self.dict_size, d), device=e.device, generator=gen) * 2.0 - 1.0
+            self.context_embeds = torch.empty((self.dict_size, d), dtype=torch.float32, device=e.device)
+            torch.nn.init.trunc_normal_(self.context_embeds, mean=0.0, std=1.0 / np.sqrt(d), a=-2.0 / np.sqrt(d),
+                                        b=2.0 / np.sqrt(d), generator=gen)
+        else:
+            rng = np.random.RandomState(seed)
+            target = rng.uniform(-1.0, 1.0, size=(self.dict_size, d)).astype(np.float32)
+            ctx = rng.standard_normal((self.dict_size, d))
+            far = np.abs(ctx) > 2.0
+            while far.any():
+                ctx[far] = rng.standard_normal(int(far.sum()))
+                far = np.abs(ctx) > 2.0
+            ctx = (ctx / np.sqrt(d)).astype(np.float32)
+            self.target_embeds = torch.from_numpy(target).to(e.device)
+            self.context_embeds = torch.from_numpy(ctx).to(e.device)
+        self.context_bias = torch.zeros(self.dict_size, dtype=torch.float32, device=e.device)
+        # fixed unigram distribution ~ degree^0.75 as a uint32 cdf, as SampleAndAggregate.build; unique=True (:449-456)
+        w = np.power(self.degrees.astype(np.float64), 0.75)
+        if w.sum() <= 0:
+            raise ValueError("Node2VecModel: every degree is zero, there is nothing to draw negatives from")
+        c = np.cumsum(w) / w.sum()
+        cdf = np.minimum(np.floor(c * 4294967296.0), 4294967295.0).astype(np.uint32)
+        cdf[-1] = np.uint32(4294967295)
+        steps_up = np.concatenate([[0], cdf.astype(np.uint64)])
+        reachable = int((steps_up[1:] > steps_up[:-1]).sum())
+        if reachable < n_neg:
+            # tf.nn.fixed_unigram_candidate_sampler(unique=True) would spin for ever
+            raise ValueError("Node2VecModel: neg_sample_size = %d distinct negatives, but only %d nodes have a non-zero "
+                             "sampling weight" % (n_neg, reachable))
+        self._neg_cdf = torch.from_numpy(cdf.view(np.int32).copy()).to(e.device)
+        self._n_cdf = int(cdf.shape[0])
+        # guide table of the inverse-cdf search, as SampleAndAggregate.build: guide[b] = first index whose cdf exceeds
+        # b << (32 - bits); a draw then searches a few entries instead of log2(N) dependent loads (same result)
+        self._guide_bits = 18
+        thr = (np.arange((1 << self._guide_bits) + 1, dtype=np.uint64) << np.uint64(32 - self._guide_bits))
+        guide = np.searchsorted(cdf.astype(np.uint64), thr, side="right")
+        self._neg_guide = torch.from_numpy(np.minimum(guide, len(cdf) - 1).astype(np.int32)).to(e.device)
+        self.neg_seed = 123
+        self.clock_dev = torch.zeros(1, dtype=torch.int64, device=e.device)
+        self.loss_dev = torch.zeros(1, dtype=torch.float32, device=e.device)
+        self.mrr_dev = torch.zeros(1, dtype=torch.float32, device=e.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=e.device)
+        self.use_graphs = True
+        self._bufs, self._graphs, self._warm = {}, {}, set()
+        self._injected_neg = None
+        self._pairs = self._cursor = None
+        torch.cuda.synchronize()
+
+    # ------------------------------------------------------------------------------------------------ buffers / launches
+    def _buffers(self, B, tag):
+        key = (int(B), tag)
+        b = self._bufs.get(key)
+        if b is None:
+            e, d, n_neg = self.engine, self.hidden_dim, self.neg_sample_size
+            n_slabs = int(ops._lib.load().gs_n2v_slabs(B, d, n_neg))
+            f = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=e.device)
+            b = dict(B=int(B), n_slabs=n_slabs, ids=torch.zeros(2 * B + n_neg, dtype=torch.int32, device=e.device),
+                     loss_rows=f(B), rr_rows=f(B), aff_all=f(B, n_neg + 1), outputs1=f(B, d), g_target=f(B, d), g_ctx=f(B, d),
+                     g_bias=f(B), neg_slabs=f(n_slabs, n_neg, d), bias_slabs=f(n_slabs, n_neg))
+            torch.cuda.synchronize()
+            self._bufs[key] = b
+        return b
+
+    def _stage(self, b, pairs=None, cursor=None):
+        ops.call("gs_n2v_stage", ops.ptr(pairs), pairs.shape[0] if pairs is not None else 0, ops.ptr(cursor), b["B"],
+                 ops.ptr(self._neg_cdf), self._n_cdf, self.neg_sample_size, self.neg_seed, ops.ptr(self.clock_dev), 0,
+                 ops.ptr(self._neg_guide), self._guide_bits, ops.ptr(b["ids"]), ops.ptr(self._status), self.engine.stream)
+
+    def _fwd_bwd(self, b, train):
+        P = ops.ptr
+        d = self.hidden_dim
+        ops.call("gs_n2v_fwd_bwd", P(self.target_embeds), d, P(self.context_embeds), d, P(self.context_bias), self.dict_size,
+                 P(b["ids"]), b["B"], d, self.neg_sample_size, 1 if train else 0, P(b["loss_rows"]), P(b["rr_rows"]),
+                 P(b["aff_all"]), self.neg_sample_size + 1, P(b["outputs1"]), d, P(b["g_target"]), P(b["g_ctx"]),
+                 P(b["g_bias"]), P(b["neg_slabs"]), P(b["bias_slabs"]), self.engine.stream)
+
+    def _apply(self, b, cursor=None):
+        """GradientDescentOptimizer(lr).minimize(loss) (models.py:447, 474-475) on the rows of this step, with the step
+        epilogue (mean loss / mrr, sampler clock + 1, epoch cursor + B) as an extra workgroup."""
+        P = ops.ptr
+        d = self.hidden_dim
+        ops.call("gs_n2v_apply", P(self.target_embeds), d, P(self.context_embeds), d, P(self.context_bias), self.dict_size,
+                 P(b["ids"]), b["B"], d, self.neg_sample_size, self.lr, P(b["g_target"]), P(b["g_ctx"]), P(b["g_bias"]),
+                 P(b["neg_slabs"]), P(b["bias_slabs"]), b["n_slabs"], P(b["loss_rows"]), P(b["rr_rows"]), P(self.loss_dev),
+                 P(self.mrr_dev), P(self.clock_dev), 1, P(cursor), b["B"] if cursor is not None else 0, self.engine.stream)
+
+    # ------------------------------------------------------------------------------------------------ host-fed steps
+    def inject_negatives(self, neg):
+        """Parity tests: the negatives of the next host-fed step (the reference draws them from TF's candidate sampler)."""
+        self._injected_neg = None if neg is None else np.ascontiguousarray(neg, dtype=np.int32)
+
+    def _check_ids(self, a, what):
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.dict_size):
+            raise ValueError("Node2VecModel: %s holds ids outside [0, %d)" % (what, self.dict_size))
+
+    def _stage_feed(self, feed_dict):
+        e, ph = self.engine, self.placeholders
+        b1 = np.ascontiguousarray(np.asarray(feed_dict[ph['batch1']]), dtype=np.int32)
+        b2 = np.ascontiguousarray(np.asarray(feed_dict[ph['batch2']]), dtype=np.int32)
+        B = int(b1.shape[0])
+        assert B > 0 and b2.shape[0] == B and int(feed_dict.get(ph['batch_size'], B)) == B
+        self._check_ids(b1, "batch1")
+        self._check_ids(b2, "batch2")
+        b = self._buffers(B, "h")
+        e.sync()
+        b["ids"][:B].copy_(torch.from_numpy(b1))
+        b["ids"][B:2 * B].copy_(torch.from_numpy(b2))
+        neg, self._injected_neg = self._injected_neg, None
+        if neg is not None:
+            assert neg.shape[0] == self.neg_sample_size and len(np.unique(neg)) == len(neg), "negatives must be distinct"
+            self._check_ids(neg, "the injected negatives")
+            b["ids"][2 * B:].copy_(torch.from_numpy(neg))
+        torch.cuda.current_stream().synchronize()
+        if neg is None:
+            self._stage(b)
+        return b
+
+    def _fetch(self, b, with_outputs=True):
+        self.engine.sync()
+        if int(self._status.item()):
+            raise ops._lib.GraphsageAmdError("Node2VecModel: the negative sampler gave up before it saw %d distinct nodes"
+                                             % self.neg_sample_size)
+        self.outputs1, self.aff_all = b["outputs1"], b["aff_all"]
+        self.neg_samples = b["ids"][2 * b["B"]:]
+        loss, mrr = float(self.loss_dev.item()), float(self.mrr_dev.item())
+        aff = b["aff_all"].cpu().numpy()
+        ranks = (aff[:, :-1] >= aff[:, -1:]).sum(axis=1)
+        outs = b["outputs1"].cpu().numpy() if with_outputs else None
+        return loss, ranks, aff, mrr, outs
+
+    def train_step(self, feed_dict, fetch=True):
+        """sess.run([opt_op, loss, ranks, aff_all, mrr, outputs1], feed_dict)  (unsupervised_train.py:273-274, :356-357)."""
+        b = self._stage_feed(feed_dict)
+        self._fwd_bwd(b, True)
+        self._apply(b)
+        return self._fetch(b) if fetch else None
+
+    def eval_step(self, feed_dict):
+        """sess.run([loss, ranks, mrr(, outputs1)], feed_dict): the evaluation form of the forward launch, no gradients
+        and no update; new negatives every call (the sampler clock advances)."""
+        b = self._stage_feed(feed_dict)
+        self._fwd_bwd(b, False)
+        inv = 1.0 / b["B"]
+        ops.call("gs_finalize_step2", ops.ptr(b["loss_rows"]), b["B"], inv, ops.ptr(self.loss_dev), 0, ops.ptr(b["rr_rows"]), inv,
+                 ops.ptr(self.mrr_dev), None, 0, ops.ptr(self.clock_dev), 1, None, 0, self.engine.stream)
+        loss, ranks, aff, mrr, outs = self._fetch(b)
+        return loss, ranks, mrr, outs
+
+    # ---- device-resident epoch: the pairs live in HBM and are consumed through a device cursor; `steps_per_launch`
+    #      steps are one captured graph.  Step t + 1 reads the rows step t wrote, so the steps of a graph are serial:
+    #      nothing of the next step is prefetched here (unlike SampleAndAggregate's device epoch).
+    def attach_device_pairs(self, pairs):
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if len(pairs) == 0:
+            raise ValueError("Node2VecModel: empty pair list")
+        self._check_ids(pairs, "the pair list")
+        self.engine.sync()
+        self._pairs = torch.from_numpy(pairs).to(self.engine.device)
+        self._cursor = torch.zeros(1, dtype=torch.int64, device=self.engine.device)
+        self._graphs, self._warm = {}, set()          # captured graphs hold the old list's address
+        torch.cuda.synchronize()
+
+    def set_epoch_pairs(self, pairs):
+        """A re-shuffled list of the same length, in place (captured graphs stay valid); the cursor returns to 0."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        assert pairs.shape == tuple(self._pairs.shape), "set_epoch_pairs: same length as the attached list"
+        self._check_ids(pairs, "the pair list")
+        self.engine.sync()
+        self._pairs.copy_(torch.from_numpy(pairs))
+        self._cursor.zero_()
+        torch.cuda.synchronize()
+
+    def _device_steps(self, b, k):
+        for _ in range(k):
+            self._stage(b, self._pairs, self._cursor)
+            self._fwd_bwd(b, True)
+            self._apply(b, self._cursor)
+
+    def train_step_device(self, B, fetch=False):
+        return self.train_steps_device(B, 1, steps_per_launch=1, fetch=fetch)
+
+    def train_steps_device(self, B, steps, steps_per_launch=8, fetch=False):
+        """`steps` steps on the attached pairs, `steps_per_launch` per graph launch (eager on first use of a length,
+        captured on the second, replayed afterwards)."""
+        assert self._pairs is not None, "attach_device_pairs first"
+        e = self.engine
+        b = self._buffers(B, "d")
+        done = 0
+        while done < steps:
+            k = max(1, min(int(steps_per_launch), steps - done))
+            key = (int(B), k)
+            g = self._graphs.get(key)
+            if g is not None:
+                g.launch()
+            elif not self.use_graphs or key not in self._warm:
+                self._device_steps(b, k)
+                self._warm.add(key)
+            else:
+                g = ops.Graph(e.stream)
+                g.begin()
+                try:
+                    self._device_steps(b, k)
+                except Exception:
+                    try:                      # leave the stream out of capture mode, or every later launch on it fails too
+                        g.end()
+                    except Exception:
+                        pass
+                    raise
+                g.end()
+                self._graphs[key] = g
+                g.launch()
+            done += k
+        return self._fetch(b) if fetch else None
+
+    def tables(self):
+        """(target_embeds, context_embeds, context_bias) as NumPy arrays (synchronises)."""
+        self.engine.sync()
+        return self.target_embeds.cpu().numpy(), self.context_embeds.cpu().numpy(), self.context_bias.cpu().numpy()
+
+    def assign_tables(self, target=None, context=None, bias=None):
+        """Overwrite variables in place (tests load the reference's values)."""
+        self.engine.sync()
+        for t, a in ((self.target_embeds, target), (self.context_embeds, context), (self.context_bias, bias)):
+            if a is not None:
+                t.copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(tuple(t.shape))))
+        torch.cuda.synchronize()

@@ -3,8 +3,11 @@ graphsage/unsupervised_train.py (flags :25-55, loop :246-316, save_val_embedding
 
     python -m graphsage_amd.unsupervised_train --train_prefix ./example_data/toy-ppi --model graphsage_mean --max_total_steps 1000
     python -m graphsage_amd.unsupervised_train --synthetic small --model graphsage_mean --epochs 1
+    python -m graphsage_amd.unsupervised_train --synthetic small --model n2v --learning_rate 0.1
 
-Models: graphsage_mean | gcn | graphsage_seq | graphsage_maxpool | graphsage_meanpool (n2v is out of scope).
+Models: graphsage_mean | gcn | graphsage_seq | graphsage_maxpool | graphsage_meanpool | n2v.  n2v is the DeepWalk /
+node2vec baseline (:227-232): after val.npy it retrains on random walks from the val / test nodes for --n2v_test_epochs
+epochs and writes val-test.npy / val-test.txt (:322-372).
 """
 from __future__ import division, print_function
 
@@ -131,7 +134,7 @@ def construct_placeholders():
 def train(G, context_pairs):
     from . import engine as eng
     from .minibatch import EdgeMinibatchIterator
-    from .models import SAGEInfo, SampleAndAggregate
+    from .models import Node2VecModel, SAGEInfo, SampleAndAggregate
     from .neigh_samplers import AdjInfo, CSRAdjacency, PaddedAdjacency, UniformNeighborSampler
 
     features = G.padded_features()
@@ -168,6 +171,10 @@ def train(G, context_pairs):
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
         model = SampleAndAggregate(placeholders, features, adj_info, minibatch.deg, layer_infos=layer_infos,
                                    aggregator_type=FLAGS.model.split('_')[1], **kw)
+    elif FLAGS.model == 'n2v':                                   # :227-232
+        model = Node2VecModel(placeholders, G.n_nodes + 1, minibatch.deg,
+                              nodevec_dim=2 * FLAGS.dim_1,      # 2x because graphsage uses concat
+                              lr=FLAGS.learning_rate, neg_sample_size=FLAGS.neg_sample_size)
     else:
         raise Exception('Error: model name unrecognized.')
 
@@ -220,7 +227,48 @@ def train(G, context_pairs):
     if FLAGS.save_embeddings:
         adj_info.assign(test_adj)
         save_val_embeddings(model, minibatch, FLAGS.validate_batch_size, log_dir())
+        if FLAGS.model == "n2v":
+            n2v_retrain(G, model, minibatch, placeholders)
     return shadow_mrr
+
+
+def n2v_retrain(G, model, minibatch, placeholders):
+    """unsupervised_train.py:322-372: embeddings for the val / test nodes of the node2vec baseline -- random walks from
+    them over the whole graph, n2v_test_epochs more SGD epochs on the walk pairs whose context is a train node, then
+    val-test.npy / val-test.txt.
+    The reference first re-binds the Python attribute model.context_embeds to a stop-gradient mix (:324-333), AFTER opt_op
+    was built: the optimizer keeps updating the variable itself, so that block changes no gradient.  What restricts this
+    phase is the iterator's _n2v_prune alone (every first node is a val / test node, every second a train node), and that
+    is what runs here."""
+    from . import utils
+    from .minibatch import EdgeMinibatchIterator
+    nodes = np.where((G.val_mask | G.test_mask) & G.present)[0]
+    start_time = time.time()
+    rowptr, col = minibatch.test_csr                              # the walks see every edge (:335-338 walks on G)
+    pairs = utils.run_random_walks(rowptr, col, nodes, num_walks=50)
+    walk_time = time.time() - start_time
+    test_minibatch = EdgeMinibatchIterator(G, None, placeholders, batch_size=FLAGS.batch_size, max_degree=FLAGS.max_degree,
+                                           num_neg_samples=FLAGS.neg_sample_size, context_pairs=pairs, n2v_retrain=True,
+                                           fixed_n2v=True, build_padded=False)
+    start_time = time.time()
+    print("Doing test training for n2v.")
+    test_steps = 0
+    for epoch in range(FLAGS.n2v_test_epochs):
+        test_minibatch.shuffle()
+        while not test_minibatch.end():
+            feed_dict = test_minibatch.next_minibatch_feed_dict()
+            feed_dict.update({placeholders['dropout']: FLAGS.dropout})
+            train_cost, ranks, aff_all, train_mrr, outputs1 = model.train_step(feed_dict)
+            if test_steps % FLAGS.print_every == 0:
+                print("Iter:", '%04d' % test_steps,
+                      "train_loss=", "{:.5f}".format(train_cost),
+                      "train_mrr=", "{:.5f}".format(train_mrr))
+            test_steps += 1
+    train_time = time.time() - start_time
+    save_val_embeddings(model, minibatch, FLAGS.validate_batch_size, log_dir(), mod="-test")
+    print("Total time: ", train_time + walk_time)
+    print("Walk time: ", walk_time)
+    print("Train time: ", train_time)
 
 
 def main(argv=None):

@@ -38,7 +38,7 @@ extern "C" {
 #define GS_ACT_IDENTITY 0
 #define GS_ACT_RELU 1
 
-#define GS_ABI_VERSION 11
+#define GS_ABI_VERSION 12
 
 const char* gs_last_error(void);
 int gs_abi_version(void);
@@ -850,6 +850,57 @@ int gs_event_record(void* ev, void* stream);
 int gs_stream_wait_event(void* stream, void* ev);
 int gs_event_elapsed_ms(void* ev_start, void* ev_stop, float* ms_out_host); /* synchronises ev_stop */
 int gs_event_destroy(void* ev);
+
+/* ---------------------------------------------------------------------------------------------
+ * N2V  node2vec / DeepWalk baseline   replaces models.py:408-504 (Node2VecModel): trainable target / context embedding tables
+ *      [n_rows, d] and a context bias [n_rows], gathered, scored and updated in place by plain SGD.  A step is
+ *      gs_n2v_stage | gs_n2v_fwd_bwd | gs_n2v_apply; no float atomics, the tables are never copied or densified, row offsets
+ *      are 64-bit.  ids = [batch1 (B) | batch2 (B) | negatives (n_neg)], every id in [0, n_rows) (the caller checks).
+ *      d in {64, 128, 256, 512}; n_neg as gs_n2v_supported says (the negatives' rows and one partial-gradient image per
+ *      pair of the workgroup share LDS: 20 fit at every d).
+ * ------------------------------------------------------------------------------------------- */
+
+/* gs_unsup_stage with n_neg DISTINCT negatives (tf.nn.fixed_unigram_candidate_sampler(unique=True), models.py:449-456):
+ * the first n_neg distinct nodes of gs_unsup_stage's stream of draws (draw t keyed by slot_offset + t, t = 0, 1, ...).
+ * The cdf must reach at least n_neg nodes (the caller checks; TensorFlow would spin for ever).  *status (nullable, device)
+ * is set to 1 if the stream was given up after 2^18 draws; the missing slots then repeat the first node.
+ * guide (nullable): int32 [2^guide_bits + 1], guide[b] = first index whose cdf exceeds b << (32 - guide_bits), clipped to
+ * n_nodes - 1, as in gs_fanout_desc: the same draws from a search of a few entries instead of log2(n_nodes) dependent loads. */
+int gs_n2v_stage(const int32_t* pairs, int64_t n_pairs, const uint64_t* cursor_dev, int64_t B, const uint32_t* cdf,
+                 int64_t n_nodes, int32_t n_neg, uint64_t seed, const uint64_t* clock_dev, int64_t slot_offset,
+                 const int32_t* guide, int32_t guide_bits, int32_t* ids_out, int32_t* status, void* stream);
+
+/* 1 if (d, n_neg) is a shape the launches below take, else 0.  gs_n2v_slabs: the number of [n_neg, d] slabs (and [n_neg]
+ * bias slabs) gs_n2v_fwd_bwd writes for B pairs, 0 if unsupported. */
+int gs_n2v_supported(int32_t d, int32_t n_neg);
+int gs_n2v_slabs(int64_t B, int32_t d, int32_t n_neg);
+
+/* With o1 = target[batch1[i]], o2 = context[batch2[i]], neg_q = context[neg[q]] and scale = 1/B:
+ *   aff_all[i]   = [<o1, neg_q> (n_neg) | <o1, o2>]            WITHOUT the bias (models.py:489-500, prediction.py)
+ *   rr_rows[i]   = 1 / (1 + #{q : <o1, neg_q> >= <o1, o2>})    (the convention of gs_linkpred_fwd_bwd)
+ *   loss_rows[i] = xent(1, <o1,o2> + bias[batch2[i]]) + sum_q xent(0, <o1,neg_q> + bias[neg[q]])     (models.py:477-487)
+ *   outputs1[i]  = o1
+ * train != 0 also writes the gradient rows of scale * sum_i loss_rows[i] (dense, ld = d):
+ *   g_target [B, d]  w.r.t. target[batch1[i]];   g_ctx [B, d], g_bias [B]  w.r.t. context / bias[batch2[i]];
+ *   neg_slabs [gs_n2v_slabs, n_neg, d], bias_slabs [gs_n2v_slabs, n_neg]: per-workgroup partial sums over the batch of the
+ *   gradient w.r.t. context / bias[neg[q]]  (summed in a fixed order by gs_n2v_apply).
+ * train == 0 (evaluation, embedding export) writes no gradient; the five buffers may be NULL. */
+int gs_n2v_fwd_bwd(const float* target, int64_t ldt, const float* context, int64_t ldc, const float* bias, int64_t n_rows,
+                   const int32_t* ids, int64_t B, int32_t d, int32_t n_neg, int train, float* loss_rows, float* rr_rows,
+                   float* aff_all, int64_t ld_aff, float* outputs1, int64_t ldo, float* g_target, float* g_ctx, float* g_bias,
+                   float* neg_slabs, float* bias_slabs, void* stream);
+
+/* tf.train.GradientDescentOptimizer on the indexed slices of gs_n2v_fwd_bwd (a launch of its own: every read of the step's
+ * rows precedes every write): for each destination row ONE owner -- the first slot holding that id, slots ordered
+ * batch1 for the target table and [negatives | batch2] for the context table and the bias -- adds the staged rows of all
+ * slots with the same id in ascending slot order and performs one p -= lr * sum.  O(touched rows); bitwise reproducible.
+ * loss_rows != NULL: an extra workgroup writes loss_out = mean(loss_rows), mrr_out = mean(rr_rows) and advances the
+ * device counters (*c0 += d0, *c1 += d1; nullable). */
+int gs_n2v_apply(float* target, int64_t ldt, float* context, int64_t ldc, float* bias, int64_t n_rows, const int32_t* ids,
+                 int64_t B, int32_t d, int32_t n_neg, float lr, const float* g_target, const float* g_ctx, const float* g_bias,
+                 const float* neg_slabs, const float* bias_slabs, int32_t n_slabs, const float* loss_rows,
+                 const float* rr_rows, float* loss_out, float* mrr_out, uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1,
+                 void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR.  Replaces the networkx loops of
