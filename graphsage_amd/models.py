@@ -80,12 +80,14 @@ class SampleAndAggregate(object):
 
     def __init__(self, placeholders, features, adj, degrees, layer_infos, concat=True, aggregator_type="mean",
                  model_size="small", identity_dim=0, learning_rate=0.00001, weight_decay=0.0, neg_sample_size=20,
-                 world_size=1, rank=0, _defer_build=False, **kwargs):
+                 world_size=1, rank=0, _defer_build=False, loss_fn='xent', bilinear_weights=False, pred_bias=False, **kwargs):
         allowed_kwargs = {'name', 'logging', 'model_size'}
         for kwarg in kwargs.keys():
             assert kwarg in allowed_kwargs, 'Invalid keyword argument: ' + kwarg
         self.name = kwargs.get('name') or self.__class__.__name__.lower()
         self.engine = get_engine()
+        # arguments of the link-prediction layer (prediction.py:12-15; the reference hard-codes the defaults, models.py:363-366)
+        self.loss_fn, self.bilinear_weights, self.pred_bias = loss_fn, bool(bilinear_weights), bool(pred_bias)
         self.aggregator_cls = _aggregator_cls(aggregator_type)
         self.aggregator_type = aggregator_type
         self.model_size = model_size
@@ -215,7 +217,8 @@ class SampleAndAggregate(object):
         from .prediction import BipartiteEdgePredLayer
         dim_mult = 2 if self.concat else 1
         self.link_pred_layer = BipartiteEdgePredLayer(dim_mult * self.dims[-1], dim_mult * self.dims[-1], self.placeholders,
-                                                      act="sigmoid", bilinear_weights=False, name='edge_predict')
+                                                      act="sigmoid", loss_fn=self.loss_fn, bias=self.pred_bias,
+                                                      bilinear_weights=self.bilinear_weights, name='edge_predict')
         e.finalize()
         if self.embeds is not None:
             self._refresh_embeds()
@@ -344,6 +347,8 @@ class SampleAndAggregate(object):
         model with concat, no aggregator bias, no dropout, no trainable identity features, at shapes the kernel supports."""
         if not getattr(self, "fuse_tail", True) or len(self.layer_infos) != 2 or self.aggregator_type != "mean":
             return False
+        if self.loss_fn != 'xent' or self.bilinear_weights:
+            return False          # gs_unsup_tail.hip is the xent head; the other losses take the per-operator schedule
         a1 = self.aggregators[1]
         return (self.concat and not a1.bias and self._dropout_rate() == 0 and self.embeds is None
                 and self.num_samples[-1] <= 11
@@ -418,6 +423,7 @@ class SampleAndAggregate(object):
             mode, agg0, rows, offsets, outs = self._tape[0]
             agg0.backward_hops(self._tail_dh0, True, embed_sink=None)
         else:
+            self.link_pred_layer.bilinear_wgrad()          # dW of the bilinear affinity, queued with the other weight gradients
             self.aggregate_backward(self._d_agg_out)
         # every term of the loss is divided by batch_size (:378) -> so is the weight-decay gradient
         e.finish_backward(self.weight_decay / B, fuse_adam=fuse_adam, lr=self.learning_rate, clip=5.0, side_jobs=wgrad_jobs,

@@ -640,6 +640,31 @@ def linkpred_tail_neg(desc, loss_out=None, accumulate=False, mrr_out=None, count
          cs[0][0], cs[0][1], cs[1][0], cs[1][1], cs[2][0], cs[2][1], ctypes.addressof(jarr), len(jobs), _s(stream))
 
 
+# ------------------------------------------------------------------------------------------ loss kinds (gs_linkpred_loss.hip)
+LP_LOSS_KINDS = {"xent": 0, "skipgram": 1, "hinge": 2}      # GS_LP_LOSS_* of include/graphsage_amd.h
+LP_WIDTHS = (64, 128, 256, 512)
+
+
+def linkpred_loss_fwd_bwd(kind, X, B, n_neg, neg_weight, margin, scale, loss_rows, rr_rows, aff_all, dX, neg_slabs, Y=None,
+                          U=None, dU=None, epilogue=None, stream=None):
+    """gs_linkpred_loss_fwd_bwd[_step].  U is None: X [2B + n_neg, d] raw aggregator outputs -> Y normalised, dX = dLoss/dX.
+    U given ([B, d], the bilinear left operand): X normalised -> dU and rows [B, 2B + n_neg) of dX.
+    epilogue: (loss_out, accumulate, mrr_out, [(counter, delta)] * 3) rides in the second launch."""
+    if isinstance(kind, str):
+        kind = LP_LOSS_KINDS[kind]
+    m = lambda a: (a.ptr, a.ld) if a is not None else (None, 0)
+    args = (int(kind), X.ptr, X.ld) + m(U) + (B, X.d, n_neg, float(neg_weight), float(margin), float(scale)) + m(Y) + \
+           (ptr(loss_rows), ptr(rr_rows)) + m(aff_all) + m(dX) + m(dU) + (ptr(neg_slabs),)
+    if epilogue is None:
+        call("gs_linkpred_loss_fwd_bwd", *args, _s(stream))
+        return
+    loss_out, accumulate, mrr_out, counters = epilogue
+    cargs = []
+    for c, dlt in counters:
+        cargs += [ptr(c) if (c is not None and dlt) else None, int(dlt) if c is not None else 0]
+    call("gs_linkpred_loss_fwd_bwd_step", *args, ptr(loss_out), 1 if accumulate else 0, ptr(mrr_out), *cargs, _s(stream))
+
+
 # ------------------------------------------------------------------------------------------ LSTM aggregator (gs_lstm.hip)
 def lstm_segments(segs):
     """segs: [(X Mat | None, ids int32 tensor | None, n sequences, T steps, row0)] -> (struct gs_lstm_seg array, number of

@@ -1,19 +1,28 @@
-"""BipartiteEdgePredLayer -- constructor surface of graphsage/prediction.py:12-66; the xent skip-gram loss
-(:102-110), the affinities (:68-92) and the MRR ranks of models.py:393-405 run as ONE fused gfx950 kernel
-(gs_linkpred_fwd_bwd) that also produces the gradients w.r.t. the three groups of normalised embeddings.
-Only loss_fn='xent' with bilinear_weights=False is on the hot path (the only configuration the reference
-drivers use, models.py:363-366); other settings fail loudly."""
+"""BipartiteEdgePredLayer -- graphsage/prediction.py:12-125: the three losses (xent :102-110, skipgram :112-117, hinge
+:119-125), the affinities with or without bilinear weights (:68-92) and the MRR ranks of models.py:393-405 as fused
+gfx950 kernels that also produce the gradients w.r.t. the three groups of normalised embeddings.
+
+The default configuration (loss_fn='xent', bilinear_weights=False: what models.py:363-366 instantiates) runs
+gs_linkpred_norm_fwd_bwd (or, from the model, the fused tail); every other one runs gs_linkpred_loss_fwd_bwd
+(csrc/gs_linkpred_loss.hip).
+
+The skipgram loss keeps the reference's sign exactly: it is written `aff - log sum_j exp(neg_aff_j)` (:115-116), so
+MINIMISING it pushes the pairs apart.  That is the reference's own source and is not "fixed" here.  neg_sample_weights
+enters the xent loss only, as in the reference.  `bias=True` creates vars['bias'] ([1] zeros, :55-56); the reference never
+reads it, so it gets no gradient and is never updated."""
 from . import ops
+from .inits import glorot, zeros
 from .layers import Layer
+
+LOSS_FNS = ('xent', 'skipgram', 'hinge')
 
 
 class BipartiteEdgePredLayer(Layer):
     def __init__(self, input_dim1, input_dim2, placeholders, dropout=False, act="sigmoid", loss_fn='xent',
                  neg_sample_weights=1.0, bias=False, bilinear_weights=False, **kwargs):
         super(BipartiteEdgePredLayer, self).__init__(**kwargs)
-        if loss_fn != 'xent' or bilinear_weights or bias:
-            raise NotImplementedError("only loss_fn='xent', bilinear_weights=False, bias=False is implemented "
-                                      "(what models.py:363-366 instantiates)")
+        if loss_fn not in LOSS_FNS:
+            raise ValueError("loss_fn must be one of %s (got %r)" % (", ".join(LOSS_FNS), loss_fn))
         self.input_dim1 = input_dim1
         self.input_dim2 = input_dim2
         self.act = act
@@ -22,14 +31,33 @@ class BipartiteEdgePredLayer(Layer):
         self.margin = 0.1
         self.neg_sample_weights = neg_sample_weights
         self.bilinear_weights = bilinear_weights
+        self.loss_fn = loss_fn
         self.dropout = 0.
         self.output_dim = 1
+        e = self.engine
+        if bilinear_weights:
+            if input_dim1 != input_dim2 or input_dim1 not in ops.LP_WIDTHS:
+                raise ops._lib.GraphsageAmdError("bilinear_weights needs input_dim1 == input_dim2 in %s (got %d, %d)"
+                                                 % (list(ops.LP_WIDTHS), input_dim1, input_dim2))
+            # xavier_initializer (:49-53); no weight decay: _loss decays aggregator variables only (models.py:386-388)
+            self.vars['weights'] = e.add_variable(self.name + "/weights", glorot((input_dim1, input_dim2)), decay=False)
+        if bias:
+            self.vars['bias'] = e.add_variable(self.name + "/bias", zeros((self.output_dim,)), decay=False)
+
+    @property
+    def default_head(self):
+        """The configuration of models.py:363-366: the xent kernels (and the model's fused tail) apply."""
+        return self.loss_fn == 'xent' and not self.bilinear_weights
 
     def loss_and_grads(self, outputs_all, batch_size, n_neg, scale, loss_rows, rr_rows, aff_all, d_outputs_all):
         """outputs_all: Mat [2B + n_neg, d] = [outputs1 | outputs2 | neg_outputs] (l2-normalised).
         Fills loss_rows (per-pair xent, :102-110), rr_rows (1/(rank+1), models.py:399-404), aff_all ([neg_aff | aff],
         models.py:395-400) and d_outputs_all = scale * dLoss/d(outputs_all)."""
         import ctypes
+        if not self.default_head:
+            raise ops._lib.GraphsageAmdError("loss_and_grads is the xent head on normalised rows; loss_fn=%r, "
+                                             "bilinear_weights=%r go through loss_and_grads_fused"
+                                             % (self.loss_fn, self.bilinear_weights))
         e = self.engine
         d = outputs_all.d
         B = batch_size
@@ -49,12 +77,16 @@ class BipartiteEdgePredLayer(Layer):
                              epilogue=None):
         """z_all: Mat [2B + n_neg, d] RAW aggregator outputs.  One launch (+ a small one for the negatives' rows):
         outputs_all = l2_normalize(z_all) (models.py:368-370), loss_rows / rr_rows / aff_all as loss_and_grads, and
-        d_z_all = scale * dLoss/d(z_all) (the gradient carried back through the normalisation)."""
+        d_z_all = scale * dLoss/d(z_all) (the gradient carried back through the normalisation).
+        With bilinear weights the schedule is normalise | U = Y1 . W | the loss kernel on (U, Y2, Yneg) | dY1 = dU . W^T |
+        normalisation backward; `bilinear_wgrad()` then queues dW = Y1^T . dU with the step's other weight gradients."""
         e = self.engine
         d = z_all.d
         B = batch_size
         n_slabs = (B + 3) // 4
         slabs = e.ws_f32((self.name, "neg_slabs", B, n_neg, d), n_slabs * n_neg * d)
+        if not self.default_head:
+            return self._general_head(z_all, outputs_all, B, n_neg, scale, loss_rows, rr_rows, aff_all, d_z_all, slabs, epilogue)
         args = (z_all.ptr, z_all.ld, B, d, n_neg, float(self.neg_sample_weights), float(scale),
                 outputs_all.ptr, outputs_all.ld, ops.ptr(loss_rows), ops.ptr(rr_rows),
                 aff_all.ptr if aff_all is not None else None, aff_all.ld if aff_all is not None else 0,
@@ -70,3 +102,32 @@ class BipartiteEdgePredLayer(Layer):
                 cargs += [ops.ptr(c) if (c is not None and dlt) else None, int(dlt) if c is not None else 0]
             ops.call("gs_linkpred_norm_fwd_bwd_step", *args, ops.ptr(loss_out), 1 if accumulate else 0, ops.ptr(mrr_out), *cargs,
                      e.stream)
+
+    def _general_head(self, z_all, outputs_all, B, n_neg, scale, loss_rows, rr_rows, aff_all, d_z_all, slabs, epilogue):
+        e = self.engine
+        d = z_all.d
+        n_rows = 2 * B + n_neg
+        common = dict(B=B, n_neg=n_neg, neg_weight=self.neg_sample_weights, margin=self.margin, scale=scale,
+                      loss_rows=loss_rows, rr_rows=rr_rows, aff_all=aff_all, neg_slabs=slabs, epilogue=epilogue, stream=e.stream)
+        if not self.bilinear_weights:
+            ops.linkpred_loss_fwd_bwd(self.loss_fn, z_all, dX=d_z_all, Y=outputs_all, **common)
+            return
+        W = self.vars['weights']
+        inv = e.ws_f32((self.name, "inv_norm", n_rows), n_rows)
+        U = e.ws_mat((self.name, "bilinear_u"), B, d)
+        dU = e.ws_mat((self.name, "bilinear_du"), B, d)
+        dY = e.ws_mat((self.name, "d_outputs_all"), n_rows, d)
+        y1 = outputs_all.rows_slice(0, B)
+        ops.l2norm_fwd(z_all.rows_slice(0, n_rows), n_rows, outputs_all, inv, stream=e.stream)
+        ops.gemm(False, False, B, d, d, y1, W.value, U, stream=e.stream)                      # neg_cost's inputs1 . W (:90)
+        ops.linkpred_loss_fwd_bwd(self.loss_fn, outputs_all, U=U, dU=dU, dX=dY, **common)
+        ops.dense_dgrad(dU, 0, d, B, W.value, dY.rows_slice(0, B), stream=e.stream)          # dY1 = dU . W^T
+        ops.l2norm_bwd(dY, outputs_all, inv, n_rows, d_z_all, stream=e.stream)
+        self._bilinear_saved = (y1, dU, B)
+
+    def bilinear_wgrad(self):
+        """Queue dW = Y1^T . dU of the last loss_and_grads_fused call (between Engine.begin_backward and finish_backward)."""
+        if not self.bilinear_weights:
+            return
+        y1, dU, B = self._bilinear_saved
+        self.engine.wgrad(self.vars['weights'], y1, None, dU, 0, B)

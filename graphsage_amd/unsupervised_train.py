@@ -56,6 +56,11 @@ def build_flags(argv=None):
                    help='sampling law of the CSR sampler: reference (the reference\'s joint law on a virtual padded '
                         '[N+1, max_degree] table, minibatch.py:227-245 + neigh_samplers.py:24-29) | iid (independent '
                         'draws with replacement from the full neighbor list) | distinct (per-row without replacement)')
+    p.add_argument('--loss_fn', default='xent', choices=['xent', 'skipgram', 'hinge'],
+                   help='loss of the link-prediction layer (prediction.py:58-63); skipgram keeps the reference\'s sign; '
+                        'ignored by --model n2v')
+    p.add_argument('--bilinear_weights', action='store_true',
+                   help='affinity u^T A v with a trainable A (prediction.py:68-92); ignored by --model n2v')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     return p.parse_args(argv)
 
@@ -65,7 +70,11 @@ def log_dir():
     parts = FLAGS.train_prefix.split("/")
     tag = parts[-2] if len(parts) >= 2 else (FLAGS.synthetic or "data")
     d = FLAGS.base_log_dir + "/unsup-" + tag
-    d += "/{model:s}_{model_size:s}_{lr:0.6f}/".format(model=FLAGS.model, model_size=FLAGS.model_size, lr=FLAGS.learning_rate)
+    d += "/{model:s}_{model_size:s}_{lr:0.6f}".format(model=FLAGS.model, model_size=FLAGS.model_size, lr=FLAGS.learning_rate)
+    if FLAGS.model != 'n2v':            # non-default heads get their own directory (the defaults keep the reference's name)
+        loss_fn = getattr(FLAGS, "loss_fn", "xent")
+        d += ("_" + loss_fn if loss_fn != "xent" else "") + ("_bilinear" if getattr(FLAGS, "bilinear_weights", False) else "")
+    d += "/"
     if not os.path.exists(d):
         os.makedirs(d)
     return d
@@ -151,7 +160,8 @@ def train(G, context_pairs):
     adj_info = AdjInfo(train_adj)
     sampler = UniformNeighborSampler(adj_info, law=FLAGS.sampler_law, max_degree=FLAGS.max_degree)
     kw = dict(model_size=FLAGS.model_size, identity_dim=FLAGS.identity_dim, learning_rate=FLAGS.learning_rate,
-              weight_decay=FLAGS.weight_decay, neg_sample_size=FLAGS.neg_sample_size, logging=True)
+              weight_decay=FLAGS.weight_decay, neg_sample_size=FLAGS.neg_sample_size, logging=True,
+              loss_fn=FLAGS.loss_fn, bilinear_weights=FLAGS.bilinear_weights)
     if FLAGS.model in ('graphsage_mean', 'graphsage'):          # unsupervised_train.py:160-172
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]

@@ -457,8 +457,41 @@ int gs_linkpred_norm_fwd_bwd_step(const float* Z, int64_t ldz, int64_t B, int32_
                                   float* mrr_out, uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1, uint64_t* c2,
                                   uint64_t d2, void* stream);
 
+/* The head generalised over the loss (prediction.py:58-63) and the left operand (bilinear weights, prediction.py:68-92).
+ * With a_i = affinity, n_ij = neg_cost and `scale` multiplying every gradient:
+ *   GS_LP_LOSS_XENT      as gs_linkpred_fwd_bwd                                               (prediction.py:102-110)
+ *   GS_LP_LOSS_SKIPGRAM  loss_i = a_i - log sum_j exp(n_ij)  (the reference's sign, prediction.py:112-117: minimising it
+ *                        pushes pairs apart; the log-sum-exp has the row maximum subtracted);  d/da_i = 1,  d/dn_ij = -softmax_j
+ *   GS_LP_LOSS_HINGE     loss_i = sum_j relu(n_ij - (a_i - margin))  (prediction.py:119-125);  m_ij = [n_ij - (a_i - margin) > 0],
+ *                        d/dn_ij = m_ij,  d/da_i = -sum_j m_ij  (relu'(0) = 0)
+ * neg_weight enters the xent loss only.  rr_rows / aff_all as gs_linkpred_fwd_bwd (from the same a_i / n_ij).
+ *   U == NULL: X [2B + n_neg, d] are the RAW aggregator outputs; Y = l2_normalize(X) is written, the left operand is the
+ *              normalised outputs1 and dX [2B + n_neg, d] = scale * dLoss/dX through the normalisation (dU is not used) --
+ *              gs_linkpred_norm_fwd_bwd for every loss kind.
+ *   U != NULL: X are the NORMALISED rows, U [B, d] is the left operand (l2_normalize(outputs1) . W, not unit-norm):
+ *              a_i = <U_i, X_{B+i}>, n_ij = <U_i, X_{2B+j}>.  dU [B, d] = scale * dLoss/dU and rows [B, 2B + n_neg) of dX =
+ *              scale * dLoss/d(normalised outputs2 | negatives) are written; rows [0, B) of dX are left alone (the caller
+ *              forms dU . W^T there); Y is not used.
+ * Two launches: the pairs (one wave per pair, ceil(B/4) workgroups, slabs of the negatives' gradient in
+ * neg_slabs [ceil(B/4), n_neg, d]), then n_neg workgroups that sum the slabs in a fixed order (no float atomics).  The _step
+ * form carries the epilogue of gs_linkpred_norm_fwd_bwd_step in the second launch.
+ * d in {64,128,256,512}; 5*n_neg*d*4 bytes must fit 160 KB of LDS; X / dX / neg_slabs 16-byte aligned with ld % 4 == 0. */
+#define GS_LP_LOSS_XENT 0
+#define GS_LP_LOSS_SKIPGRAM 1
+#define GS_LP_LOSS_HINGE 2
+int gs_linkpred_loss_fwd_bwd(int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B, int32_t d,
+                             int32_t n_neg, float neg_weight, float margin, float scale, float* Y, int64_t ldy,
+                             float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff, float* dX, int64_t lddx,
+                             float* dU, int64_t lddu, float* neg_slabs, void* stream);
+int gs_linkpred_loss_fwd_bwd_step(int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B,
+                                  int32_t d, int32_t n_neg, float neg_weight, float margin, float scale, float* Y, int64_t ldy,
+                                  float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff, float* dX, int64_t lddx,
+                                  float* dU, int64_t lddu, float* neg_slabs, float* loss_out, int accumulate, float* mrr_out,
+                                  uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1, uint64_t* c2, uint64_t d2,
+                                  void* stream);
+
 /* ---------------------------------------------------------------------------------------------
- * K6  optimizer               replaces supervised_models.py:95-99 (clip_by_value +-5, Adam) and the
+ * K6  optimizer              replaces supervised_models.py:95-99 (clip_by_value +-5, Adam) and the
  *                             weight-decay terms :104-108
  * ------------------------------------------------------------------------------------------- */
 
