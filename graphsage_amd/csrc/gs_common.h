@@ -72,6 +72,19 @@ __device__ __forceinline__ uint64_t gs_mix64(uint64_t z) {
     return z;
 }
 
+// Wave-wide sum / max of one value per lane, the result in every lane: the xor butterfly at 32, 16, .., 1 (six ds_bpermute).
+// THE order of every single-value wave reduction outside the fused tails (gs_tail_dev.h has a DPP form with another order).
+__device__ __forceinline__ float gs_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ float gs_wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
 // ---- inverted dropout, tf.nn.dropout(x, keep_prob = 1 - rate) (aggregators.py:46-47,104-105; layers.py:107) ----
 // The keep mask is a pure function of (seed, device step clock, call site, global row, float4 column): one mix64 per
 // float4 gives 16 random bits per element, an element is dropped iff its bits < thresh16 = round(rate * 2^16).
@@ -176,8 +189,7 @@ __device__ __forceinline__ void gs_step_epilogue_block(const StepEpilogue& e, fl
     if (e.aux_rows) {                          // a second mean in the same launch (unsupervised: mrr, models.py:404)
         float s = 0.f;
         for (int64_t i = threadIdx.x; i < e.n; i += 256) s += e.aux_rows[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        s = gs_wave_sum(s);
         if ((threadIdx.x & 63) == 0) part2[threadIdx.x >> 6] = s;
         __syncthreads();
         if (threadIdx.x == 0) e.aux_out[0] = ((part2[0] + part2[1]) + (part2[2] + part2[3])) * e.aux_scale;
@@ -185,8 +197,7 @@ __device__ __forceinline__ void gs_step_epilogue_block(const StepEpilogue& e, fl
     if (e.loss_rows) {
         float s = 0.f;
         for (int64_t i = threadIdx.x; i < e.n; i += 256) s += e.loss_rows[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        s = gs_wave_sum(s);
         if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
         __syncthreads();
         if (threadIdx.x == 0) {

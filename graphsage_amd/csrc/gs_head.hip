@@ -3,17 +3,6 @@
 #include "gs_common.h"
 #include <stdlib.h>
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // ------------------------------------------------------------------------------ segment max
 __global__ __launch_bounds__(256) void segment_max_fwd_kernel(const float* __restrict__ H, int64_t ldh, int64_t n,
                                                               int32_t s, int32_t hidden, float* __restrict__ pooled,
@@ -183,7 +172,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict
         const float v = x[r * ldx + c];
         ss += v * v;
     }
-    ss = wave_sum(ss);
+    ss = gs_wave_sum(ss);
     const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));  // tf.nn.l2_normalize epsilon
     const int dp = (d + 3) & ~3;
     for (int c = lane; c < dp; c += 64) y[r * ldy + c] = c < d ? x[r * ldx + c] * inv : 0.f;
@@ -210,7 +199,7 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict
     if (r >= n) return;
     float dot = 0.f;
     for (int c = lane; c < d; c += 64) dot += dy[r * lddy + c] * y[r * ldy + c];
-    dot = wave_sum(dot);
+    dot = gs_wave_sum(dot);
     const float inv = inv_norm[r];
     const bool clamped = inv >= 1.0e6f;  // sum(x^2) < 1e-12: y = x * 1e6, no normalisation term
     const int dp = (d + 3) & ~3;
@@ -261,12 +250,12 @@ __global__ __launch_bounds__(256) void class_loss_kernel(const float* __restrict
             if (preds) preds[r * ldp + c] = p;
             if (dlogits) dlogits[r * lddl + c] = g;
         }
-        acc = wave_sum(acc);
+        acc = gs_wave_sum(acc);
         if (lane == 0) loss_rows[r] = acc / (float)C;
     } else {
         float m = -INFINITY;
         for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-        m = wave_max(m);
+        m = gs_wave_max(m);
         float se = 0.f, zs = 0.f, zx = 0.f;
         for (int c = lane; c < C; c += 64) {
             const float xv = x[c], zv = z[c];
@@ -274,9 +263,9 @@ __global__ __launch_bounds__(256) void class_loss_kernel(const float* __restrict
             zs += zv;
             zx += zv * xv;
         }
-        se = wave_sum(se);
-        zs = wave_sum(zs);
-        zx = wave_sum(zx);
+        se = gs_wave_sum(se);
+        zs = gs_wave_sum(zs);
+        zx = gs_wave_sum(zx);
         const float lse = m + logf(se);
         const float inv_se = 1.0f / se;
         const float gscale = 1.0f / (float)n;
@@ -387,7 +376,7 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
         float ss = 0.f;
 #pragma unroll
         for (int j = 0; j < DJ; ++j) ss += xr[j] * xr[j];
-        ss = wave_sum(ss);
+        ss = gs_wave_sum(ss);
         const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
         const bool clamped = ss < 1e-12f;
 #pragma unroll
@@ -416,7 +405,7 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
         float m = -INFINITY, se = 0.f, zs = 0.f, zx = 0.f, loss_acc = 0.f;
 #pragma unroll
         for (int q = 0; q < CQ; ++q) m = fmaxf(m, (q * 64 + lane < C) ? lg[q] : -INFINITY);
-        m = wave_max(m);
+        m = gs_wave_max(m);
 #pragma unroll
         for (int q = 0; q < CQ; ++q) {
             const bool ok = q * 64 + lane < C;
@@ -424,9 +413,9 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
             zs += ok ? lab[q] : 0.f;
             zx += ok ? lab[q] * lg[q] : 0.f;
         }
-        se = wave_sum(se);
-        zs = wave_sum(zs);
-        zx = wave_sum(zx);
+        se = gs_wave_sum(se);
+        zs = gs_wave_sum(zs);
+        zx = gs_wave_sum(zx);
         const float inv_se = 1.0f / se;
         const float gscale = sigmoid_loss ? 1.0f / ((float)n * (float)C) : 1.0f / (float)n;
         float dl[CQ];
@@ -453,7 +442,7 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
                 dlogits[r * lddl + c] = g;
             }
         }
-        if (sigmoid_loss) loss_acc = wave_sum(loss_acc);
+        if (sigmoid_loss) loss_acc = gs_wave_sum(loss_acc);
         if (lane == 0) loss_rows[r] = sigmoid_loss ? loss_acc / (float)C : zs * (m + logf(se)) - zx;
         // ---- d_y = dlogits · W^T (lanes over k) and the l2-normalise backward
         if (dx) {
@@ -475,7 +464,7 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
             float dot = 0.f;
 #pragma unroll
             for (int j = 0; j < DJ; ++j) dot += dyk[j] * xr[j];
-            dot = wave_sum(dot);
+            dot = gs_wave_sum(dot);
 #pragma unroll
             for (int j = 0; j < DJ; ++j)
                 dx[r * lddx + j * 64 + lane] = clamped ? dyk[j] * inv : inv * (dyk[j] - xr[j] * dot);

@@ -1,69 +1,21 @@
-// Link-prediction head generalised over the loss kind and the left operand (prediction.py:68-125, models.py:393-405).
+// The link-prediction head (prediction.py:68-125, models.py:393-405): the ONE definition behind gs_linkpred_fwd_bwd,
+// gs_linkpred_norm_fwd_bwd[_step] and gs_linkpred_loss_fwd_bwd[_step].
 //   linkpred_loss_kernel     one wave per pair, four pairs per workgroup, the (normalised) negatives staged once per workgroup
-//                            in LDS -- the shape of linkpred_norm_fwd_bwd_kernel (gs_unsup.hip), with
+//                            in LDS, with
 //                              KIND  xent (:102-110) | skipgram (:112-117) | hinge (:119-125)
-//                              NORM  true:  X = RAW aggregator outputs; the kernel normalises them, the left operand is the
-//                                           normalised outputs1 and the gradient is carried back through the normalisation
+//                              NORM  true:  X = RAW aggregator outputs; the kernel normalises them (models.py:368-370), the
+//                                           left operand is the normalised outputs1 and the gradient is carried back through
+//                                           the normalisation:  dZ = inv * (g - y <g, y>)  (inv = rsqrt(max(sum z^2, 1e-12));
+//                                           clamped rows: dZ = g * inv)
 //                                    false: X = normalised rows, the left operand is a separate U [B, d] (bilinear weights:
-//                                           U = l2_normalize(outputs1) . W, not unit-norm); the kernel returns dU and the
-//                                           gradient w.r.t. the normalised outputs2 / negatives
+//                                           U = l2_normalize(outputs1) . W, not unit-norm; or the rows [0, B) of X themselves);
+//                                           the kernel returns dU and the gradient w.r.t. the normalised outputs2 / negatives
 //   linkpred_loss_neg_kernel the negatives' gradient: per-workgroup slabs summed in a fixed order (no float atomics, bitwise
 //                            reproducible), optionally through the normalisation; the step epilogue rides as one more block.
 #include "gs_common.h"
+#include "gs_linkpred_dev.h"
 
 enum { LP_XENT = GS_LP_LOSS_XENT, LP_SKIPGRAM = GS_LP_LOSS_SKIPGRAM, LP_HINGE = GS_LP_LOSS_HINGE };
-
-__device__ __forceinline__ float lp_wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float lp_wmax(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// Affinities of the wave's left row against negatives qb .. qb + nq - 1 (nq <= 64, wave-uniform): lane q returns negative
-// qb + q's (lanes >= nq return 0).  Four independent dot products / reductions in flight, as linkpred_pair.
-template <int DJ>
-__device__ __forceinline__ float lp_neg_affinities(const float (&o1)[DJ], const float* __restrict__ negs, const int qb,
-                                                   const int nq, const int lane) {
-    constexpr int d = DJ * 64;
-    float nav = 0.f;
-    int q = 0;
-    for (; q + 4 <= nq; q += 4) {
-        float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-        const float* nr = negs + (size_t)(qb + q) * d + lane;
-#pragma unroll
-        for (int j = 0; j < DJ; ++j) {
-            p0 += o1[j] * nr[j * 64];
-            p1 += o1[j] * nr[d + j * 64];
-            p2 += o1[j] * nr[2 * d + j * 64];
-            p3 += o1[j] * nr[3 * d + j * 64];
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            p0 += __shfl_xor(p0, off, 64);
-            p1 += __shfl_xor(p1, off, 64);
-            p2 += __shfl_xor(p2, off, 64);
-            p3 += __shfl_xor(p3, off, 64);
-        }
-        nav = lane == q ? p0 : nav;
-        nav = lane == q + 1 ? p1 : nav;
-        nav = lane == q + 2 ? p2 : nav;
-        nav = lane == q + 3 ? p3 : nav;
-    }
-    for (; q < nq; ++q) {
-        float p0 = 0.f;
-#pragma unroll
-        for (int j = 0; j < DJ; ++j) p0 += o1[j] * negs[(size_t)(qb + q) * d + j * 64 + lane];
-        p0 = lp_wsum(p0);
-        nav = lane == q ? p0 : nav;
-    }
-    return nav;
-}
 
 struct LpLossArgs {
     const float* X; int64_t ldx;       // [2B + n_neg, d]: rows [0,B) outputs1, [B,2B) outputs2, [2B, ..) negatives
@@ -100,7 +52,7 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
             ss += v[j] * v[j];
         }
         float inv = 1.0f;
-        if (NORM) inv = __builtin_amdgcn_rsqf(fmaxf(lp_wsum(ss), 1e-12f));
+        if (NORM) inv = __builtin_amdgcn_rsqf(fmaxf(gs_wave_sum(ss), 1e-12f));
 #pragma unroll
         for (int j = 0; j < DJ; ++j) {
             const float y = NORM ? v[j] * inv : v[j];
@@ -123,8 +75,8 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
             s1 += o1[j] * o1[j];
             s2 += o2[j] * o2[j];
         }
-        inv1 = __builtin_amdgcn_rsqf(fmaxf(lp_wsum(s1), 1e-12f));
-        inv2 = __builtin_amdgcn_rsqf(fmaxf(lp_wsum(s2), 1e-12f));
+        inv1 = __builtin_amdgcn_rsqf(fmaxf(gs_wave_sum(s1), 1e-12f));
+        inv2 = __builtin_amdgcn_rsqf(fmaxf(gs_wave_sum(s2), 1e-12f));
 #pragma unroll
         for (int j = 0; j < DJ; ++j) {
             o1[j] *= inv1;
@@ -140,7 +92,7 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
     float aff = 0.f;
 #pragma unroll
     for (int j = 0; j < DJ; ++j) aff += o1[j] * o2[j];
-    aff = lp_wsum(aff);
+    aff = gs_wave_sum(aff);
 
     const int nq0 = min(64, n_neg), nq1 = max(0, n_neg - 64);
     float nav[2];
@@ -150,25 +102,23 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
     const int rank = __popcll(__ballot(in[0] && nav[0] >= aff)) + __popcll(__ballot(in[1] && nav[1] >= aff));
     float gq[2], da, loss;
     if (KIND == LP_XENT) {
-        const float ea = __expf(-fabsf(aff));
-        const float ra = __builtin_amdgcn_rcpf(1.0f + ea);
-        const float sa = aff >= 0.f ? ra : ea * ra;
+        float sa, lga;
+        gs_sigmoid_lg(aff, sa, lga);
         da = (sa - 1.0f) * a.scale;
-        loss = fmaxf(aff, 0.f) - aff + __logf(1.0f + ea);
+        loss = fmaxf(aff, 0.f) - aff + lga;
         float ln = 0.f;
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
-            const float e = __expf(-fabsf(nav[b]));
-            const float r1 = __builtin_amdgcn_rcpf(1.0f + e);
-            const float sg = nav[b] >= 0.f ? r1 : e * r1;             // sigmoid(nav)
-            ln += in[b] ? fmaxf(nav[b], 0.f) + __logf(1.0f + e) : 0.f;
+            float sg, lg;
+            gs_sigmoid_lg(nav[b], sg, lg);
+            ln += in[b] ? fmaxf(nav[b], 0.f) + lg : 0.f;
             gq[b] = in[b] ? a.neg_w * a.scale * sg : 0.f;
         }
-        loss += a.neg_w * lp_wsum(ln);
+        loss += a.neg_w * gs_wave_sum(ln);
     } else if (KIND == LP_SKIPGRAM) {
-        const float mx = lp_wmax(fmaxf(in[0] ? nav[0] : -INFINITY, in[1] ? nav[1] : -INFINITY));
+        const float mx = gs_wave_max(fmaxf(in[0] ? nav[0] : -INFINITY, in[1] ? nav[1] : -INFINITY));
         const float e0 = in[0] ? __expf(nav[0] - mx) : 0.f, e1 = in[1] ? __expf(nav[1] - mx) : 0.f;
-        const float S = lp_wsum(e0 + e1);                             // >= 1: the maximum's own term
+        const float S = gs_wave_sum(e0 + e1);                             // >= 1: the maximum's own term
         const float rS = 1.0f / S;
         loss = aff - (mx + __logf(S));
         da = a.scale;
@@ -178,7 +128,7 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
         const float thr = aff - a.margin;                             // tf.subtract(neg_aff, aff - margin), relu'(0) = 0
         const float t0 = nav[0] - thr, t1 = nav[1] - thr;
         const bool m0 = in[0] && t0 > 0.f, m1 = in[1] && t1 > 0.f;
-        loss = lp_wsum((m0 ? t0 : 0.f) + (m1 ? t1 : 0.f));
+        loss = gs_wave_sum((m0 ? t0 : 0.f) + (m1 ? t1 : 0.f));
         da = -a.scale * (float)(__popcll(__ballot(m0)) + __popcll(__ballot(m1)));
         gq[0] = m0 ? a.scale : 0.f;
         gq[1] = m1 ? a.scale : 0.f;
@@ -216,8 +166,8 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
                 dot1 += g1[j] * o1[j];
                 dot2 += da * o1[j] * o2[j];
             }
-            dot1 = lp_wsum(dot1);
-            dot2 = lp_wsum(dot2);
+            dot1 = gs_wave_sum(dot1);
+            dot2 = gs_wave_sum(dot2);
             const bool c1 = inv1 >= 1.0e6f, c2 = inv2 >= 1.0e6f;
 #pragma unroll
             for (int j = 0; j < DJ; ++j) {
@@ -246,10 +196,12 @@ __global__ __launch_bounds__(256) void linkpred_loss_kernel(const LpLossArgs a) 
         slab[t] = (part[t] + part[(size_t)n_neg * d + t]) + (part[2 * (size_t)n_neg * d + t] + part[3 * (size_t)n_neg * d + t]);
 }
 
-// One workgroup per negative row q: g = sum of the n_slabs per-workgroup slabs in a fixed order (the walk of
-// linkpred_neg_bwd_kernel: d/4 float4 columns x 1024/d slab groups over the 256 threads, 16 loads in flight per group, the
-// groups meet in LDS and are summed group 0, 1, ...).  through_norm: X holds the RAW row and g goes back through its
-// normalisation; otherwise the row of dX is g itself.  Block n_neg (when has_epi) is the step epilogue.
+// One workgroup per negative row q: g = sum of the n_slabs per-workgroup slabs in a fixed order.  The row's d/4 float4 columns
+// x SG = 1024/d slab groups are spread over the 256 threads; a group walks its slabs (sg, sg + SG, ...) with 16 independent
+// 16-byte loads in flight (the first version: 8 dword loads per batch, 16 dependent round trips for 128 slabs -- 8 us of pure
+// latency), the groups meet in LDS and are summed group 0, 1, ...  through_norm: X holds the RAW row and g goes back through
+// its normalisation (the row's own inv recomputed from X); otherwise the row of dX is g itself.  Block n_neg (when has_epi) is
+// the step epilogue (mean loss / mrr + device counters): it only needs the rows the previous launch wrote.
 __global__ __launch_bounds__(256) void linkpred_loss_neg_kernel(const float* __restrict__ slabs, int32_t n_slabs, int32_t n_neg,
                                                                 int32_t d, const float* __restrict__ X, int64_t ldx,
                                                                 int64_t row0, float* __restrict__ dX, int64_t lddx,
@@ -292,13 +244,13 @@ __global__ __launch_bounds__(256) void linkpred_loss_neg_kernel(const float* __r
         z = *reinterpret_cast<const f32x4*>(X + (row0 + q) * ldx + 4 * tid);
         ss = (z.x * z.x + z.y * z.y) + (z.z * z.z + z.w * z.w);
     }
-    ss = lp_wsum(ss);
+    ss = gs_wave_sum(ss);
     if ((tid & 63) == 0) red[0][tid >> 6] = ss;
     __syncthreads();
     ss = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
     const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
     float dot = ((g.x * z.x + g.y * z.y) + (g.z * z.z + g.w * z.w)) * inv;
-    dot = lp_wsum(dot);
+    dot = gs_wave_sum(dot);
     if ((tid & 63) == 0) red[1][tid >> 6] = dot;
     __syncthreads();
     dot = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
@@ -331,23 +283,25 @@ static int lp_loss_launch_kind(int32_t kind, const LpLossArgs& a, int32_t d, int
     return lp_loss_launch_d<LP_HINGE, NORM>(a, d, blocks, lds_bytes, st);
 }
 
-static int linkpred_loss_launch(int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B, int32_t d,
-                                int32_t n_neg, float neg_weight, float margin, float scale, float* Y, int64_t ldy,
-                                float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff, float* dX, int64_t lddx,
-                                float* dU, int64_t lddu, float* neg_slabs, const StepEpilogue* epi, void* stream) {
-    GS_REQUIRE(loss_kind == LP_XENT || loss_kind == LP_SKIPGRAM || loss_kind == LP_HINGE,
-               "gs_linkpred_loss_fwd_bwd: unknown loss kind %d", loss_kind);
-    GS_REQUIRE(X && loss_rows && rr_rows && dX && neg_slabs && B > 0 && n_neg > 0, "gs_linkpred_loss_fwd_bwd: bad args");
-    GS_REQUIRE(d == 64 || d == 128 || d == 256 || d == 512, "gs_linkpred_loss_fwd_bwd: d must be 64/128/256/512 (got %d)", d);
+// `who`: the entry point's name for its error messages.  n_slabs_out != nullptr: the first launch only -- the slabs are left
+// for the caller's gs_reduce_slabs and their count is returned (gs_linkpred_fwd_bwd).
+static int linkpred_loss_launch(const char* who, int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu,
+                                int64_t B, int32_t d, int32_t n_neg, float neg_weight, float margin, float scale, float* Y,
+                                int64_t ldy, float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff, float* dX,
+                                int64_t lddx, float* dU, int64_t lddu, float* neg_slabs, const StepEpilogue* epi,
+                                int32_t* n_slabs_out, void* stream) {
+    GS_REQUIRE(loss_kind == LP_XENT || loss_kind == LP_SKIPGRAM || loss_kind == LP_HINGE, "%s: unknown loss kind %d", who, loss_kind);
+    GS_REQUIRE(X && loss_rows && rr_rows && dX && neg_slabs && B > 0 && n_neg > 0, "%s: bad args", who);
+    GS_REQUIRE(d == 64 || d == 128 || d == 256 || d == 512, "%s: d must be 64/128/256/512 (got %d)", who, d);
     const bool norm = U == nullptr;
-    GS_REQUIRE(norm ? (Y != nullptr && ldy >= d) : (dU != nullptr && ldu >= d && lddu >= d),
-               "gs_linkpred_loss_fwd_bwd: %s", norm ? "Y missing or ldy too small" : "dU missing or ldu / lddu too small");
-    GS_REQUIRE(ldx >= d && lddx >= d && (!aff_all || ld_aff >= n_neg + 1), "gs_linkpred_loss_fwd_bwd: ld too small");
+    GS_REQUIRE(norm ? (Y != nullptr && ldy >= d) : (dU != nullptr && ldu >= d && lddu >= d), "%s: %s", who,
+               norm ? "Y missing or ldy too small" : "dU missing or ldu / lddu too small");
+    GS_REQUIRE(ldx >= d && lddx >= d && (!aff_all || ld_aff >= n_neg + 1), "%s: ld too small", who);
     const size_t lds_bytes = (size_t)5 * n_neg * d * sizeof(float);
-    GS_REQUIRE(lds_bytes <= 160 * 1024, "gs_linkpred_loss_fwd_bwd: %d negatives x d=%d do not fit LDS", n_neg, d);
+    GS_REQUIRE(lds_bytes <= 160 * 1024, "%s: %d negatives x d=%d do not fit LDS", who, n_neg, d);
     // the second launch moves whole float4: 16-byte rows
-    GS_REQUIRE(ldx % 4 == 0 && lddx % 4 == 0 && gs_aligned16(X) && gs_aligned16(dX) && gs_aligned16(neg_slabs),
-               "gs_linkpred_loss_fwd_bwd: X / dX / neg_slabs must be 16-byte aligned with ld %% 4 == 0");
+    GS_REQUIRE(n_slabs_out || (ldx % 4 == 0 && lddx % 4 == 0 && gs_aligned16(X) && gs_aligned16(dX) && gs_aligned16(neg_slabs)),
+               "%s: X / dX / neg_slabs must be 16-byte aligned with ld %% 4 == 0", who);
     const int64_t blocks = gs_ceil_div(B, 4);
     hipStream_t st = (hipStream_t)stream;
     const LpLossArgs a = {X, ldx, U, ldu, B, n_neg, neg_weight, margin, scale, Y, ldy, loss_rows, rr_rows, aff_all, ld_aff,
@@ -356,6 +310,10 @@ static int linkpred_loss_launch(int32_t loss_kind, const float* X, int64_t ldx, 
                         : lp_loss_launch_kind<false>(loss_kind, a, d, blocks, lds_bytes, st);
     if (rc != GS_OK) return rc;
     GS_LAUNCH_CHECK("linkpred_loss_kernel");
+    if (n_slabs_out) {
+        *n_slabs_out = (int32_t)blocks;
+        return GS_OK;
+    }
     const StepEpilogue none = {};
     hipLaunchKernelGGL(linkpred_loss_neg_kernel, dim3((unsigned)(n_neg + (epi ? 1 : 0))), dim3(256), 0, st, neg_slabs,
                        (int32_t)blocks, n_neg, d, X, ldx, 2 * B, dX, lddx, norm ? 1 : 0, epi ? *epi : none);
@@ -363,12 +321,18 @@ static int linkpred_loss_launch(int32_t loss_kind, const float* X, int64_t ldx, 
     return GS_OK;
 }
 
+static StepEpilogue lp_step_epilogue(int64_t B, float* loss_rows, float* rr_rows, float* loss_out, int accumulate, float* mrr_out,
+                                     uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1, uint64_t* c2, uint64_t d2) {
+    const float inv_b = B > 0 ? 1.0f / (float)B : 0.f;
+    return {loss_rows, B, inv_b, loss_out, accumulate, rr_rows, inv_b, mrr_out, c0, d0, c1, d1, c2, d2};
+}
+
 extern "C" int gs_linkpred_loss_fwd_bwd(int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B,
                                         int32_t d, int32_t n_neg, float neg_weight, float margin, float scale, float* Y,
                                         int64_t ldy, float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff,
                                         float* dX, int64_t lddx, float* dU, int64_t lddu, float* neg_slabs, void* stream) {
-    return linkpred_loss_launch(loss_kind, X, ldx, U, ldu, B, d, n_neg, neg_weight, margin, scale, Y, ldy, loss_rows, rr_rows,
-                                aff_all, ld_aff, dX, lddx, dU, lddu, neg_slabs, nullptr, stream);
+    return linkpred_loss_launch("gs_linkpred_loss_fwd_bwd", loss_kind, X, ldx, U, ldu, B, d, n_neg, neg_weight, margin, scale, Y,
+                                ldy, loss_rows, rr_rows, aff_all, ld_aff, dX, lddx, dU, lddu, neg_slabs, nullptr, nullptr, stream);
 }
 
 extern "C" int gs_linkpred_loss_fwd_bwd_step(int32_t loss_kind, const float* X, int64_t ldx, const float* U, int64_t ldu,
@@ -378,8 +342,39 @@ extern "C" int gs_linkpred_loss_fwd_bwd_step(int32_t loss_kind, const float* X, 
                                              float* loss_out, int accumulate, float* mrr_out, uint64_t* c0, uint64_t d0,
                                              uint64_t* c1, uint64_t d1, uint64_t* c2, uint64_t d2, void* stream) {
     GS_REQUIRE(loss_out && mrr_out, "gs_linkpred_loss_fwd_bwd_step: loss_out / mrr_out missing");
-    const float inv_b = B > 0 ? 1.0f / (float)B : 0.f;
-    const StepEpilogue epi = {loss_rows, B, inv_b, loss_out, accumulate, rr_rows, inv_b, mrr_out, c0, d0, c1, d1, c2, d2};
-    return linkpred_loss_launch(loss_kind, X, ldx, U, ldu, B, d, n_neg, neg_weight, margin, scale, Y, ldy, loss_rows, rr_rows,
-                                aff_all, ld_aff, dX, lddx, dU, lddu, neg_slabs, &epi, stream);
+    const StepEpilogue epi = lp_step_epilogue(B, loss_rows, rr_rows, loss_out, accumulate, mrr_out, c0, d0, c1, d1, c2, d2);
+    return linkpred_loss_launch("gs_linkpred_loss_fwd_bwd", loss_kind, X, ldx, U, ldu, B, d, n_neg, neg_weight, margin, scale, Y,
+                                ldy, loss_rows, rr_rows, aff_all, ld_aff, dX, lddx, dU, lddu, neg_slabs, &epi, nullptr, stream);
+}
+
+// ---- the xent head's older entry points: the same kernels ----
+// Rows of Y already normalised: the gradient of the pair rows into dY, the negatives' slabs left for gs_reduce_slabs.
+extern "C" int gs_linkpred_fwd_bwd(const float* Y, int64_t ldy, int64_t B, int32_t d, int32_t n_neg, float neg_weight,
+                                   float scale, float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff,
+                                   float* dY, int64_t lddy, float* neg_slabs, int32_t* n_slabs_out, void* stream) {
+    int32_t n_slabs = 0;
+    const int rc = linkpred_loss_launch("gs_linkpred_fwd_bwd", LP_XENT, Y, ldy, Y, ldy, B, d, n_neg, neg_weight, 0.f, scale, nullptr,
+                                        0, loss_rows, rr_rows, aff_all, ld_aff, dY, lddy, dY, lddy, neg_slabs, nullptr, &n_slabs,
+                                        stream);
+    if (rc == GS_OK && n_slabs_out) *n_slabs_out = n_slabs;
+    return rc;
+}
+
+// RAW rows Z: Y = l2_normalize(Z), the gradient back through the normalisation into dZ, negatives' rows included.
+extern "C" int gs_linkpred_norm_fwd_bwd(const float* Z, int64_t ldz, int64_t B, int32_t d, int32_t n_neg, float neg_weight,
+                                        float scale, float* Y, int64_t ldy, float* loss_rows, float* rr_rows, float* aff_all,
+                                        int64_t ld_aff, float* dZ, int64_t lddz, float* neg_slabs, void* stream) {
+    return linkpred_loss_launch("gs_linkpred_norm_fwd_bwd", LP_XENT, Z, ldz, nullptr, 0, B, d, n_neg, neg_weight, 0.f, scale, Y, ldy,
+                                loss_rows, rr_rows, aff_all, ld_aff, dZ, lddz, nullptr, 0, neg_slabs, nullptr, nullptr, stream);
+}
+
+extern "C" int gs_linkpred_norm_fwd_bwd_step(const float* Z, int64_t ldz, int64_t B, int32_t d, int32_t n_neg, float neg_weight,
+                                             float scale, float* Y, int64_t ldy, float* loss_rows, float* rr_rows,
+                                             float* aff_all, int64_t ld_aff, float* dZ, int64_t lddz, float* neg_slabs,
+                                             float* loss_out, int accumulate, float* mrr_out, uint64_t* c0, uint64_t d0,
+                                             uint64_t* c1, uint64_t d1, uint64_t* c2, uint64_t d2, void* stream) {
+    GS_REQUIRE(loss_out && mrr_out, "gs_linkpred_norm_fwd_bwd_step: loss_out / mrr_out missing");
+    const StepEpilogue epi = lp_step_epilogue(B, loss_rows, rr_rows, loss_out, accumulate, mrr_out, c0, d0, c1, d1, c2, d2);
+    return linkpred_loss_launch("gs_linkpred_norm_fwd_bwd", LP_XENT, Z, ldz, nullptr, 0, B, d, n_neg, neg_weight, 0.f, scale, Y, ldy,
+                                loss_rows, rr_rows, aff_all, ld_aff, dZ, lddz, nullptr, 0, neg_slabs, &epi, nullptr, stream);
 }

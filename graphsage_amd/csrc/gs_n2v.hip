@@ -8,7 +8,8 @@
 //   n2v_apply_kernel    GradientDescentOptimizer on indexed slices: per destination row ONE owner sums the staged rows
 //                       of every slot with that id in ascending slot order and subtracts once
 // ids = [batch1 (B) | batch2 (B) | negatives (n_neg)] everywhere.  Row offsets are 64-bit (tables of 10^7 rows).
-#include "gs_common.h"
+#include "gs_linkpred_dev.h"
+#include "gs_sample_dev.h"
 
 #define N2V_MAX_NEG 1024          // kept list of the unique sampler (LDS)
 #define N2V_MAX_ROUNDS 4096       // 64 draws each; the host refuses a distribution with fewer than n_neg reachable nodes
@@ -29,31 +30,18 @@ __global__ __launch_bounds__(256) void n2v_stage_kernel(const int32_t* __restric
         const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         if (t < B) {
             const uint64_t c = cursor ? *cursor : 0ull;
-            const int64_t e = (int64_t)((c + (uint64_t)t) % (uint64_t)n_pairs);
-            ids_out[t] = pairs[2 * e];
-            ids_out[B + t] = pairs[2 * e + 1];
+            ids_out[t] = gs_stage_pair(pairs, n_pairs, c, t, 0);
+            ids_out[B + t] = gs_stage_pair(pairs, n_pairs, c, t, 1);
         }
         return;
     }
     if (threadIdx.x >= 64) return;
     const int lane = threadIdx.x;
     const uint64_t st = clock ? *clock : 0ull;
-    const uint64_t key = gs_mix64(seed ^ (st * 0x9E3779B97F4A7C15ull) ^ (0xFFull << 56));
     int n_kept = 0;
     for (int round = 0; round < N2V_MAX_ROUNDS && n_kept < n_neg; ++round) {
         const uint64_t t = (uint64_t)round * 64ull + (uint64_t)lane;
-        const uint32_t r = (uint32_t)(gs_mix64(key + t + (uint64_t)slot_offset) >> 32);
-        int64_t lo = 0, hi = n_nodes - 1;  // first index with cdf[idx] > r
-        if (guide) {                       // same result; the table only narrows the starting interval (gs_sample_dev.h)
-            const uint32_t b = r >> (32 - guide_bits);
-            lo = guide[b];
-            hi = min((int64_t)guide[b + 1], n_nodes - 1);
-        }
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (cdf[mid] > r) hi = mid; else lo = mid + 1;
-        }
-        const int32_t id = (int32_t)lo;
+        const int32_t id = gs_unigram_pick(cdf, n_nodes, guide, guide_bits, gs_unigram_draw32(seed, st, t + (uint64_t)slot_offset));
         bool fresh = true;
         for (int k = 0; k < n_kept; ++k) fresh = fresh && kept[k] != id;
         for (int l = 0; l < 63; ++l) {                         // an earlier draw of this round with the same node
@@ -90,12 +78,6 @@ extern "C" int gs_n2v_stage(const int32_t* pairs, int64_t n_pairs, const uint64_
                        guide_bits);
     GS_LAUNCH_CHECK("n2v_stage_kernel");
     return GS_OK;
-}
-
-__device__ __forceinline__ float n2v_wsum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 struct N2vFwd {
@@ -169,13 +151,12 @@ __global__ __launch_bounds__(256) void n2v_fwd_bwd_kernel(const N2vFwd a) {
     float aff = 0.f;
 #pragma unroll
     for (int j = 0; j < DJ; ++j) aff += o1[j] * o2[j];
-    aff = n2v_wsum(aff);
+    aff = gs_wave_sum(aff);
     const float affb = aff + bias2;
-    const float ea = __expf(-fabsf(affb));
-    const float ra = __builtin_amdgcn_rcpf(1.0f + ea);
-    const float sa = affb >= 0.f ? ra : ea * ra;
+    float sa, lga;
+    gs_sigmoid_lg(affb, sa, lga);
     const float da = (sa - 1.0f) * a.scale;
-    float loss = fmaxf(affb, 0.f) - affb + __logf(1.0f + ea);
+    float loss = fmaxf(affb, 0.f) - affb + lga;
     int rank = 0;
 #pragma unroll
     for (int j = 0; j < DJ; ++j) g1[j] = da * o2[j];
@@ -183,49 +164,18 @@ __global__ __launch_bounds__(256) void n2v_fwd_bwd_kernel(const N2vFwd a) {
     float* mypartb = partb + (size_t)wave * n_neg;
     for (int qb = 0; qb < n_neg; qb += 64) {
         const int nq = min(64, n_neg - qb);                       // wave-uniform
-        float nav = 0.f;                                          // lane q: negative qb + q
-        int q = 0;
-        for (; q + 4 <= nq; q += 4) {                             // four independent dot products / reductions in flight
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;
-            const float* nr = negs + (size_t)(qb + q) * d + lane;
-#pragma unroll
-            for (int j = 0; j < DJ; ++j) {
-                p0 += o1[j] * nr[j * 64];
-                p1 += o1[j] * nr[d + j * 64];
-                p2 += o1[j] * nr[2 * d + j * 64];
-                p3 += o1[j] * nr[3 * d + j * 64];
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                p0 += __shfl_xor(p0, off, 64);
-                p1 += __shfl_xor(p1, off, 64);
-                p2 += __shfl_xor(p2, off, 64);
-                p3 += __shfl_xor(p3, off, 64);
-            }
-            nav = lane == q ? p0 : nav;
-            nav = lane == q + 1 ? p1 : nav;
-            nav = lane == q + 2 ? p2 : nav;
-            nav = lane == q + 3 ? p3 : nav;
-        }
-        for (; q < nq; ++q) {
-            float p0 = 0.f;
-#pragma unroll
-            for (int j = 0; j < DJ; ++j) p0 += o1[j] * negs[(size_t)(qb + q) * d + j * 64 + lane];
-            p0 = n2v_wsum(p0);
-            nav = lane == q ? p0 : nav;
-        }
+        const float nav = lp_neg_affinities<DJ>(o1, negs, qb, nq, lane);   // lane q: negative qb + q
         const bool in = lane < nq;
         const float navb = nav + (in ? nbias[qb + lane] : 0.f);
-        const float e = __expf(-fabsf(navb));
-        const float r1 = __builtin_amdgcn_rcpf(1.0f + e);
-        const float sg = navb >= 0.f ? r1 : e * r1;               // sigmoid(nav + bias)
-        loss += n2v_wsum(in ? fmaxf(navb, 0.f) + __logf(1.0f + e) : 0.f);
+        float sg, lg;                                             // sigmoid(nav + bias)
+        gs_sigmoid_lg(navb, sg, lg);
+        loss += gs_wave_sum(in ? fmaxf(navb, 0.f) + lg : 0.f);
         rank += __popcll(__ballot(in && nav >= aff));
         if (live && in && a.aff_all) a.aff_all[i * a.ld_aff + qb + lane] = nav;
         if (train) {
             const float gqv = (in && live) ? a.scale * sg : 0.f;
             if (in) mypartb[qb + lane] = gqv;
-            for (q = 0; q < nq; ++q) {
+            for (int q = 0; q < nq; ++q) {
                 const float gq = __shfl(gqv, q, 64);
                 const float* nr = negs + (size_t)(qb + q) * d + lane;
                 float* mp = mypart + (size_t)(qb + q) * d + lane;
@@ -391,7 +341,7 @@ __global__ __launch_bounds__(256) void n2v_apply_kernel(const N2vApply a) {
         float gb = 0.f;                                    // bias: wave 0 sums the slabs' entries, lane-strided then butterfly
         if (wave == 0) {
             for (int k = lane; k < a.n_slabs; k += 64) gb += a.bias_slabs[(size_t)k * n_neg + q];
-            gb = n2v_wsum(gb);
+            gb = gs_wave_sum(gb);
         }
         __syncthreads();
         f32x4 g = zero4;

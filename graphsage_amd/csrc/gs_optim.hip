@@ -136,8 +136,7 @@ __global__ __launch_bounds__(1024) void sum_kernel(const float* __restrict__ x, 
         const float v = x[i];
         s += SQUARE ? v * v : v;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = gs_wave_sum(s);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -221,8 +220,7 @@ __global__ __launch_bounds__(GS_OPT_THREADS) void flat_reduce_adam_kernel(const 
                 if (threadIdx.x < 64) {
                     float sacc = 0.f;
                     for (int64_t i = threadIdx.x; i < loss_n; i += 64) sacc += loss_rows[i];
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) sacc += __shfl_xor(sacc, off, 64);
+                    sacc = gs_wave_sum(sacc);
                     if (threadIdx.x == 0) loss_out[0] = loss_accumulate ? loss_out[0] + sacc * loss_scale : sacc * loss_scale;
                 }
                 return;

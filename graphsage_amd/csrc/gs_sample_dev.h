@@ -93,6 +93,46 @@ __device__ __forceinline__ uint32_t gs_draw(const SampleLaw lw, uint64_t seed, u
     }
     return (uint32_t)(((gs_mix64(rowkey + j) >> 32) * (uint64_t)deg) >> 32);    // GS_LAW_IID: Lemire range map
 }
+
+// ---- unsupervised root staging: ONE definition for gs_unsup_stage, gs_n2v_stage and the fused fan-out staging below, which
+// promise the same ids bit for bit (restated in oracle/sampler_hash.py) ----
+// side (0 | 1) of edge pair e = (cursor + t) % n_pairs (minibatch.py:113-132 on the device)
+__device__ __forceinline__ int32_t gs_stage_pair(const int32_t* __restrict__ pairs, int64_t n_pairs, uint64_t cursor, int64_t t,
+                                                 int side) {
+    const int64_t e = (int64_t)((cursor + (uint64_t)t) % (uint64_t)n_pairs);
+    return pairs[2 * e + side];
+}
+// the 32-bit draw of a step's unigram-negative stream at GLOBAL slot `slot` (data-parallel ranks draw different negatives and
+// the stand-alone and the fused staging of the same step agree)
+__device__ __forceinline__ uint32_t gs_unigram_draw32(uint64_t seed, uint64_t clock, uint64_t slot) {
+    const uint64_t key = gs_mix64(seed ^ (clock * 0x9E3779B97F4A7C15ull) ^ (0xFFull << 56));
+    return (uint32_t)(gs_mix64(key + slot) >> 32);
+}
+// [lo, hi]: where "the first index with cdf[idx] > r" lies.  guide (nullable): guide[b] = first index with
+// cdf > (b << (32 - guide_bits)), 2^guide_bits + 1 entries; the table only narrows the interval, never changes the result.
+__device__ __forceinline__ void gs_unigram_interval(int64_t n, const int32_t* __restrict__ guide, int32_t guide_bits, uint32_t r,
+                                                    int64_t& lo, int64_t& hi) {
+    lo = 0;
+    hi = n - 1;
+    if (guide) {
+        const uint32_t b = r >> (32 - guide_bits);
+        lo = guide[b];
+        hi = min((int64_t)guide[b + 1], n - 1);
+    }
+}
+// the negative of draw r: the first node whose cdf (uint32 [n], cdf[i] = floor(2^32 * P(node <= i)), P ~ degree^0.75, last =
+// 2^32 - 1) exceeds it, by serial bisection
+__device__ __forceinline__ int32_t gs_unigram_pick(const uint32_t* __restrict__ cdf, int64_t n, const int32_t* __restrict__ guide,
+                                                   int32_t guide_bits, uint32_t r) {
+    int64_t lo, hi;
+    gs_unigram_interval(n, guide, guide_bits, r, lo, hi);
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (cdf[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    return (int32_t)lo;
+}
+
 #define GS_FANOUT_LDS 8192          // per-root ids of the kept hops, standalone kernel
 #define GS_FANOUT_LDS_SMALL 512     // ... when the sampler rides in another launch (e.g. 10 for fan-out 25x10)
 struct FanoutArgs {
@@ -176,8 +216,7 @@ __device__ __forceinline__ void sample_fanout_root(const FanoutArgs& a, const in
         if (i < 2 * a.n_pair_roots) {
             if (tid == 0) {
                 const int side = i >= a.n_pair_roots ? 1 : 0;
-                const int64_t e = (int64_t)((c + (uint64_t)(i - side * a.n_pair_roots)) % (uint64_t)a.n_pairs);
-                root = a.pairs[2 * e + side];
+                root = gs_stage_pair(a.pairs, a.n_pairs, c, i - side * a.n_pair_roots, side);
                 a.ids_all[a.offsets[0] + i] = root;
             }
         } else if (tid < 64) {
@@ -186,15 +225,10 @@ __device__ __forceinline__ void sample_fanout_root(const FanoutArgs& a, const in
             // where the binary search ends); longer intervals are halved first.  (One lane bisecting was one dependent round
             // trip per step: the 20 negatives' workgroups ended 4-5 us after the 1024 pair roots' and with them the launch.)
             const uint64_t t = (uint64_t)(i - 2 * a.n_pair_roots);
-            const uint64_t nkey = gs_mix64(a.neg_seed ^ (st * 0x9E3779B97F4A7C15ull) ^ (0xFFull << 56));
             // keyed by the GLOBAL slot: data-parallel ranks draw different negatives
-            const uint32_t r = (uint32_t)(gs_mix64(nkey + t + (uint64_t)a.root_offset) >> 32);
-            int64_t lo = 0, hi = a.n_cdf - 1;  // first index with cdf[idx] > r
-            if (a.guide) {
-                const uint32_t b = r >> (32 - a.guide_bits);
-                lo = a.guide[b];
-                hi = min((int64_t)a.guide[b + 1], a.n_cdf - 1);
-            }
+            const uint32_t r = gs_unigram_draw32(a.neg_seed, st, t + (uint64_t)a.root_offset);
+            int64_t lo, hi;  // first index with cdf[idx] > r
+            gs_unigram_interval(a.n_cdf, a.guide, a.guide_bits, r, lo, hi);
             while (hi - lo > 64) {
                 const int64_t mid = (lo + hi) >> 1;
                 if (a.cdf[mid] > r) hi = mid; else lo = mid + 1;

@@ -115,8 +115,7 @@ __global__ __launch_bounds__(256) void split16_table_kernel(const float* __restr
     const float* x = X + row * ldx;
     float mx = 0.f;
     for (int k = lane; k < d; k += 64) mx = fmaxf(mx, fabsf(x[k]));
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    mx = gs_wave_max(mx);
     const int e = gs_scale_exp(mx);
     if (lane == 0) rexp[row] = e;
     _Float16* h = X2 + row * 2 * (int64_t)KP;

@@ -106,11 +106,7 @@ __device__ __forceinline__ float tail_wave_sum(float v) {
     const float r0 = __shfl(v, 0, 64), r1 = __shfl(v, 16, 64), r2 = __shfl(v, 32, 64), r3 = __shfl(v, 48, 64);
     return (r0 + r1) + (r2 + r3);
 }
-__device__ __forceinline__ float tail_wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
+__device__ __forceinline__ float tail_wave_max(float v) { return gs_wave_max(v); }
 #else
 __device__ __forceinline__ float tail_wave_sum(float v) {
     v += tail_dpp<0xB1>(v);

@@ -19,6 +19,7 @@
 // word) for the 2 helpers (one per term) of ITS group and of the negative groups; counters are monotonic, a group's consumed count is
 // written by its main (pair groups) or by launch 2 (negative groups: every main reads them).
 #include "gs_tail_dev.h"
+#include "gs_linkpred_dev.h"
 
 #define LP_MAX_NEG 32        // negatives held normalised in LDS by every main workgroup
 
@@ -218,11 +219,10 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
             aff += o1[m] * o2[m];
         }
         aff = tail_wave_sum(aff);
-        const float ea = __expf(-fabsf(aff));
-        const float ra = __builtin_amdgcn_rcpf(1.0f + ea);
-        const float sa = aff >= 0.f ? ra : ea * ra;
+        float sa, lga;
+        gs_sigmoid_lg(aff, sa, lga);
         const float da = (sa - 1.0f) * L.scale;
-        float loss = fmaxf(aff, 0.f) - aff + __logf(1.0f + ea);
+        float loss = fmaxf(aff, 0.f) - aff + lga;
 #pragma unroll
         for (int m = 0; m < DJ; ++m) g1[m] = da * o2[m];
         // the n_neg <= 32 affinities: four reductions in flight, then lane qn holds negative qn's
@@ -258,10 +258,9 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
             nav = lane == qn ? p0 : nav;
         }
         const bool in = lane < n_neg;
-        const float e = __expf(-fabsf(nav));
-        const float r1 = __builtin_amdgcn_rcpf(1.0f + e);
-        const float sg = nav >= 0.f ? r1 : e * r1;                   // sigmoid(nav)
-        loss += L.neg_w * tail_wave_sum(in ? fmaxf(nav, 0.f) + __logf(1.0f + e) : 0.f);
+        float sg, lg;                                                // sigmoid(nav)
+        gs_sigmoid_lg(nav, sg, lg);
+        loss += L.neg_w * tail_wave_sum(in ? fmaxf(nav, 0.f) + lg : 0.f);
         const int rank = __popcll(__ballot(in && nav >= aff));
         const float gqv = (in && live) ? L.neg_w * L.scale * sg : 0.f;
         gqs[p * 64 + lane] = gqv;

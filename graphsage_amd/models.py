@@ -22,6 +22,7 @@ from .engine import get_engine
 from .inits import glorot
 from .layers import Rows, identity
 from .ops import Mat
+from .utils import unigram_cdf
 
 # SAGEInfo is a namedtuple that specifies the parameters of the recursive GraphSAGE layers
 # (graphsage/models.py:180-185)
@@ -224,21 +225,13 @@ class SampleAndAggregate(object):
             self._refresh_embeds()
         self.loss_dev = torch.zeros(1, dtype=torch.float32, device=e.device)
         self.mrr_dev = torch.zeros(1, dtype=torch.float32, device=e.device)
-        # fixed unigram distribution ~ degree^0.75 of tf.nn.fixed_unigram_candidate_sampler (:336-343) as a uint32 CDF
-        w = np.power(np.asarray(self.degrees, dtype=np.float64), 0.75)
-        if w.sum() <= 0:
-            w = np.ones_like(w)
-        c = np.cumsum(w) / w.sum()
-        cdf = np.minimum(np.floor(c * 4294967296.0), 4294967295.0).astype(np.uint32)
-        cdf[-1] = np.uint32(4294967295)
+        # fixed unigram distribution ~ degree^0.75 of tf.nn.fixed_unigram_candidate_sampler (:336-343); uniform if no node
+        # has a neighbor
+        deg = np.asarray(self.degrees, dtype=np.float64)
+        self._guide_bits = 18
+        cdf, guide = unigram_cdf(deg if np.power(deg, 0.75).sum() > 0 else np.ones_like(deg), self._guide_bits)
         self._neg_cdf = torch.from_numpy(cdf.view(np.int32).copy()).to(e.device)   # raw bits; the kernel reads uint32
         self._n_cdf = int(cdf.shape[0])
-        # guide table of the inverse-cdf search: guide[b] = first index whose cdf exceeds b << (32 - bits); a draw r then
-        # searches [guide[r >> s], guide[(r >> s) + 1]] only (same result, ~6 dependent loads instead of 18)
-        self._guide_bits = 18          # 1 MB table; ~1 node per bucket: the search is 1-2 dependent loads
-        thr = (np.arange((1 << self._guide_bits) + 1, dtype=np.uint64) << np.uint64(32 - self._guide_bits))
-        guide = np.searchsorted(cdf.astype(np.uint64), thr, side="right")
-        guide = np.minimum(guide, len(cdf) - 1).astype(np.int32)
         self._neg_guide = torch.from_numpy(guide).to(e.device)
         self.neg_seed = 123
         torch.cuda.synchronize()
@@ -323,22 +316,29 @@ class SampleAndAggregate(object):
         # the head's second launch (with dropout the clock must not move before the backward pass: separate launch later)
         fold = epilogue is not None and self._dropout_rate() == 0.0
         self._epilogue_folded = fold
-        epi = None
-        if fold:
-            epi = (self.loss_dev, False, self.mrr_dev,
-                   [(e.step_dev, epilogue.get("step", 0)), (e.sample_clock_dev, epilogue.get("clock", 0)),
-                    (epilogue.get("cursor"), epilogue.get("cursor_delta", 0))])
+        epi = (self.loss_dev, False, self.mrr_dev, self._epilogue_counters(epilogue)) if fold else None
         self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B, self._loss_rows,
                                                   self._rr_rows, self.aff_all, self._d_agg_out, epilogue=epi)
         # loss = (sum_vars wd*l2_loss + xent) / batch_size  (:386-390, :378); the xent mean (and the mrr, :404) are formed
         # by the epilogue (folded: the weight-decay terms are added behind it; separate launch: it adds to them)
+        self._weight_decay_loss(B, fold)
+
+    def _epilogue_counters(self, epilogue):
+        """The step epilogue's [(device counter, increment)] * 3: optimizer step, sampler clock, pair cursor."""
+        e = self.engine
+        return [(e.step_dev, epilogue.get("step", 0)), (e.sample_clock_dev, epilogue.get("clock", 0)),
+                (epilogue.get("cursor"), epilogue.get("cursor_delta", 0))]
+
+    def _weight_decay_loss(self, B, fold):
+        """loss_dev (+)= sum_vars wd * l2_loss / batch_size (:386-388, :378).  fold: the epilogue has written the head's mean
+        already and the terms are added behind it; otherwise they start the sum and the later epilogue adds to them."""
         self._loss_accumulate = False
         if self.weight_decay != 0.0:
             first = not fold
             for a in self.aggregators:
                 for v in a.vars.values():
                     ops.call("gs_sumsq_scaled", v.value.ptr, v.size, 0.5 * self.weight_decay / B, self.loss_dev.data_ptr(),
-                             0 if first else 1, e.stream)
+                             0 if first else 1, self.engine.stream)
                     first = False
             self._loss_accumulate = not fold
 
@@ -384,21 +384,10 @@ class SampleAndAggregate(object):
         # clock untouched until the backward pass has run (this path runs without dropout: always folded when given)
         fold = epilogue is not None
         self._epilogue_folded = fold
-        counters = []
-        if fold:
-            counters = [(e.step_dev, epilogue.get("step", 0)), (e.sample_clock_dev, epilogue.get("clock", 0)),
-                        (epilogue.get("cursor"), epilogue.get("cursor_delta", 0))]
+        counters = self._epilogue_counters(epilogue) if fold else []
         ops.linkpred_tail_neg(desc, loss_out=self.loss_dev if fold else None, accumulate=False,
                               mrr_out=self.mrr_dev if fold else None, counters=counters, jobs=neg_jobs, stream=e.stream)
-        self._loss_accumulate = False
-        if self.weight_decay != 0.0:
-            first = not fold
-            for a in self.aggregators:
-                for v in a.vars.values():
-                    ops.call("gs_sumsq_scaled", v.value.ptr, v.size, 0.5 * self.weight_decay / B, self.loss_dev.data_ptr(),
-                             0 if first else 1, e.stream)
-                    first = False
-            self._loss_accumulate = not fold
+        self._weight_decay_loss(B, fold)
 
     def _backward_unsup(self, B, n_roots, fuse_adam, wgrad_jobs=None, epilogue=None):
         """Reverse schedule.  The epilogue (loss / mrr means + device counters) runs FIRST: the fan-out sampler of a later
@@ -731,9 +720,7 @@ class SampleAndAggregate(object):
         contiguous = inputs.data_ptr() == buf.data_ptr() and inputs.numel() == batch_size
         K = len(layer_infos)
         sampler0 = layer_infos[0].neigh_sampler
-        from .neigh_samplers import CSRAdjacency
-        fused = (contiguous and K <= 3 and all(li.neigh_sampler is sampler0 for li in layer_infos)
-                 and isinstance(sampler0.adj_info.current, CSRAdjacency) and getattr(self, "fuse_sampler", True))
+        fused = contiguous and self._fanout_fusable(layer_infos)
         stage = getattr(self, "_pending_stage", None)
         self._pending_stage = None
         if fused:
@@ -1029,13 +1016,11 @@ class Node2VecModel(object):
             self.target_embeds = torch.from_numpy(target).to(e.device)
             self.context_embeds = torch.from_numpy(ctx).to(e.device)
         self.context_bias = torch.zeros(self.dict_size, dtype=torch.float32, device=e.device)
-        # fixed unigram distribution ~ degree^0.75 as a uint32 cdf, as SampleAndAggregate.build; unique=True (:449-456)
-        w = np.power(self.degrees.astype(np.float64), 0.75)
-        if w.sum() <= 0:
+        # fixed unigram distribution ~ degree^0.75, as SampleAndAggregate.build; unique=True (:449-456)
+        if np.power(self.degrees.astype(np.float64), 0.75).sum() <= 0:
             raise ValueError("Node2VecModel: every degree is zero, there is nothing to draw negatives from")
-        c = np.cumsum(w) / w.sum()
-        cdf = np.minimum(np.floor(c * 4294967296.0), 4294967295.0).astype(np.uint32)
-        cdf[-1] = np.uint32(4294967295)
+        self._guide_bits = 18
+        cdf, guide = unigram_cdf(self.degrees, self._guide_bits)
         steps_up = np.concatenate([[0], cdf.astype(np.uint64)])
         reachable = int((steps_up[1:] > steps_up[:-1]).sum())
         if reachable < n_neg:
@@ -1044,12 +1029,7 @@ class Node2VecModel(object):
                              "sampling weight" % (n_neg, reachable))
         self._neg_cdf = torch.from_numpy(cdf.view(np.int32).copy()).to(e.device)
         self._n_cdf = int(cdf.shape[0])
-        # guide table of the inverse-cdf search, as SampleAndAggregate.build: guide[b] = first index whose cdf exceeds
-        # b << (32 - bits); a draw then searches a few entries instead of log2(N) dependent loads (same result)
-        self._guide_bits = 18
-        thr = (np.arange((1 << self._guide_bits) + 1, dtype=np.uint64) << np.uint64(32 - self._guide_bits))
-        guide = np.searchsorted(cdf.astype(np.uint64), thr, side="right")
-        self._neg_guide = torch.from_numpy(np.minimum(guide, len(cdf) - 1).astype(np.int32)).to(e.device)
+        self._neg_guide = torch.from_numpy(guide).to(e.device)
         self.neg_seed = 123
         self.clock_dev = torch.zeros(1, dtype=torch.int64, device=e.device)
         self.loss_dev = torch.zeros(1, dtype=torch.float32, device=e.device)

@@ -2,9 +2,8 @@
 :119-125), the affinities with or without bilinear weights (:68-92) and the MRR ranks of models.py:393-405 as fused
 gfx950 kernels that also produce the gradients w.r.t. the three groups of normalised embeddings.
 
-The default configuration (loss_fn='xent', bilinear_weights=False: what models.py:363-366 instantiates) runs
-gs_linkpred_norm_fwd_bwd (or, from the model, the fused tail); every other one runs gs_linkpred_loss_fwd_bwd
-(csrc/gs_linkpred_loss.hip).
+Every configuration runs the one head kernel, gs_linkpred_loss_fwd_bwd (csrc/gs_linkpred_loss.hip); the default one
+(loss_fn='xent', bilinear_weights=False: what models.py:363-366 instantiates) may run the model's fused tail instead.
 
 The skipgram loss keeps the reference's sign exactly: it is written `aff - log sum_j exp(neg_aff_j)` (:115-116), so
 MINIMISING it pushes the pairs apart.  That is the reference's own source and is not "fixed" here.  neg_sample_weights
@@ -49,64 +48,21 @@ class BipartiteEdgePredLayer(Layer):
         """The configuration of models.py:363-366: the xent kernels (and the model's fused tail) apply."""
         return self.loss_fn == 'xent' and not self.bilinear_weights
 
-    def loss_and_grads(self, outputs_all, batch_size, n_neg, scale, loss_rows, rr_rows, aff_all, d_outputs_all):
-        """outputs_all: Mat [2B + n_neg, d] = [outputs1 | outputs2 | neg_outputs] (l2-normalised).
-        Fills loss_rows (per-pair xent, :102-110), rr_rows (1/(rank+1), models.py:399-404), aff_all ([neg_aff | aff],
-        models.py:395-400) and d_outputs_all = scale * dLoss/d(outputs_all)."""
-        import ctypes
-        if not self.default_head:
-            raise ops._lib.GraphsageAmdError("loss_and_grads is the xent head on normalised rows; loss_fn=%r, "
-                                             "bilinear_weights=%r go through loss_and_grads_fused"
-                                             % (self.loss_fn, self.bilinear_weights))
-        e = self.engine
-        d = outputs_all.d
-        B = batch_size
-        n_slabs = (B + 3) // 4
-        slabs = e.ws_f32((self.name, "neg_slabs", B, n_neg, d), n_slabs * n_neg * d)
-        out_n = ctypes.c_int32()
-        ops.call("gs_linkpred_fwd_bwd", outputs_all.ptr, outputs_all.ld, B, d, n_neg, float(self.neg_sample_weights),
-                 float(scale), ops.ptr(loss_rows), ops.ptr(rr_rows), aff_all.ptr if aff_all is not None else None,
-                 aff_all.ld if aff_all is not None else 0, d_outputs_all.ptr, d_outputs_all.ld, ops.ptr(slabs),
-                 ctypes.byref(out_n), e.stream)
-        assert out_n.value == n_slabs
-        dneg = d_outputs_all.rows_slice(2 * B, 2 * B + n_neg)
-        ops.call("gs_reduce_slabs", ops.ptr(slabs), n_slabs, n_neg * d, n_neg, d, d, 0.0, None, 0, dneg.ptr, dneg.ld, 0,
-                 e.stream)
-
     def loss_and_grads_fused(self, z_all, outputs_all, batch_size, n_neg, scale, loss_rows, rr_rows, aff_all, d_z_all,
                              epilogue=None):
         """z_all: Mat [2B + n_neg, d] RAW aggregator outputs.  One launch (+ a small one for the negatives' rows):
-        outputs_all = l2_normalize(z_all) (models.py:368-370), loss_rows / rr_rows / aff_all as loss_and_grads, and
-        d_z_all = scale * dLoss/d(z_all) (the gradient carried back through the normalisation).
+        outputs_all = l2_normalize(z_all) (models.py:368-370), loss_rows (the per-pair loss), rr_rows (1/(rank+1),
+        models.py:399-404), aff_all ([neg_aff | aff], models.py:395-400) and d_z_all = scale * dLoss/d(z_all) (the gradient
+        carried back through the normalisation).
         With bilinear weights the schedule is normalise | U = Y1 . W | the loss kernel on (U, Y2, Yneg) | dY1 = dU . W^T |
         normalisation backward; `bilinear_wgrad()` then queues dW = Y1^T . dU with the step's other weight gradients."""
         e = self.engine
         d = z_all.d
         B = batch_size
-        n_slabs = (B + 3) // 4
-        slabs = e.ws_f32((self.name, "neg_slabs", B, n_neg, d), n_slabs * n_neg * d)
-        if not self.default_head:
-            return self._general_head(z_all, outputs_all, B, n_neg, scale, loss_rows, rr_rows, aff_all, d_z_all, slabs, epilogue)
-        args = (z_all.ptr, z_all.ld, B, d, n_neg, float(self.neg_sample_weights), float(scale),
-                outputs_all.ptr, outputs_all.ld, ops.ptr(loss_rows), ops.ptr(rr_rows),
-                aff_all.ptr if aff_all is not None else None, aff_all.ld if aff_all is not None else 0,
-                d_z_all.ptr, d_z_all.ld, ops.ptr(slabs))
-        if epilogue is None:
-            ops.call("gs_linkpred_norm_fwd_bwd", *args, e.stream)
-        else:
-            # `epilogue`: (loss_out, accumulate, mrr_out, [(counter, delta)] * 3) -- the step's loss / mrr means and device
-            # counters ride in the second launch
-            loss_out, accumulate, mrr_out, counters = epilogue
-            cargs = []
-            for c, dlt in counters:
-                cargs += [ops.ptr(c) if (c is not None and dlt) else None, int(dlt) if c is not None else 0]
-            ops.call("gs_linkpred_norm_fwd_bwd_step", *args, ops.ptr(loss_out), 1 if accumulate else 0, ops.ptr(mrr_out), *cargs,
-                     e.stream)
-
-    def _general_head(self, z_all, outputs_all, B, n_neg, scale, loss_rows, rr_rows, aff_all, d_z_all, slabs, epilogue):
-        e = self.engine
-        d = z_all.d
         n_rows = 2 * B + n_neg
+        slabs = e.ws_f32((self.name, "neg_slabs", B, n_neg, d), ((B + 3) // 4) * n_neg * d)
+        # `epilogue`: (loss_out, accumulate, mrr_out, [(counter, delta)] * 3) -- the step's loss / mrr means and device
+        # counters ride in the second launch
         common = dict(B=B, n_neg=n_neg, neg_weight=self.neg_sample_weights, margin=self.margin, scale=scale,
                       loss_rows=loss_rows, rr_rows=rr_rows, aff_all=aff_all, neg_slabs=slabs, epilogue=epilogue, stream=e.stream)
         if not self.bilinear_weights:

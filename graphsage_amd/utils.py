@@ -114,6 +114,20 @@ def build_csr_numpy(n_nodes, src, dst, keep=None):
     return rowptr, d.astype(np.int32)
 
 
+def unigram_cdf(degrees, guide_bits=18):
+    """The fixed unigram distribution ~ degree^0.75 of tf.nn.fixed_unigram_candidate_sampler (models.py:336-343, :449-456)
+    as the tables of the device's inverse-cdf search (csrc/gs_sample_dev.h: gs_unigram_pick) -> (cdf uint32 [n], guide int32
+    [2^guide_bits + 1]).  cdf[i] = floor(2^32 * P(node <= i)), the last entry 2^32 - 1; guide[b] = first index whose cdf
+    exceeds b << (32 - guide_bits): a draw r then searches [guide[r >> s], guide[(r >> s) + 1]] only (same result, 1-2
+    dependent loads at 18 bits -- a 1 MB table, ~1 node per bucket -- instead of log2(n)).  Needs one positive degree."""
+    w = np.power(np.asarray(degrees, dtype=np.float64), 0.75)
+    cdf = np.minimum(np.floor(np.cumsum(w) / w.sum() * 4294967296.0), 4294967295.0).astype(np.uint32)
+    cdf[-1] = np.uint32(4294967295)
+    thr = np.arange((1 << guide_bits) + 1, dtype=np.uint64) << np.uint64(32 - guide_bits)
+    guide = np.searchsorted(cdf.astype(np.uint64), thr, side="right")
+    return cdf, np.minimum(guide, len(cdf) - 1).astype(np.int32)
+
+
 def padded_from_csr(rowptr, col, n_nodes, max_degree, rng):
     """The reference's padded table (minibatch.py:227-259) from a CSR, vectorised:
     deg > max_degree -> sample max_degree WITHOUT replacement; 0 < deg < max_degree -> WITH

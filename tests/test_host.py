@@ -40,6 +40,35 @@ def test_error_reporting_through_c_abi():
     assert rc == -1 and b"gs_reduce_slabs" in lib.gs_last_error()
 
 
+@pytest.mark.parametrize("case", ["zeros", "single", "random"])
+def test_unigram_cdf_is_the_construction_it_replaces(case):
+    """utils.unigram_cdf == the cdf / guide construction that SampleAndAggregate.build and Node2VecModel each spelled out."""
+    from graphsage_amd.utils import unigram_cdf
+    rng = np.random.RandomState(3)
+    deg = {"zeros": np.array([0, 3, 0, 0, 7, 1, 0]), "single": np.array([0, 0, 5, 0]),
+           "random": rng.randint(0, 200, size=400)}[case]
+    w = np.power(np.asarray(deg, dtype=np.float64), 0.75)
+    c = np.cumsum(w) / w.sum()
+    cdf = np.minimum(np.floor(c * 4294967296.0), 4294967295.0).astype(np.uint32)
+    cdf[-1] = np.uint32(4294967295)
+    bits = 18
+    thr = (np.arange((1 << bits) + 1, dtype=np.uint64) << np.uint64(32 - bits))
+    guide = np.minimum(np.searchsorted(cdf.astype(np.uint64), thr, side="right"), len(cdf) - 1).astype(np.int32)
+    got_cdf, got_guide = unigram_cdf(deg)
+    assert got_cdf.dtype == np.uint32 and got_guide.dtype == np.int32 and got_guide.shape == ((1 << bits) + 1,)
+    assert np.array_equal(got_cdf, cdf) and np.array_equal(got_guide, guide)
+    # guide[b] = first index with cdf > b << 14 (the last index where none is)
+    first = np.searchsorted(cdf.astype(np.int64), np.arange((1 << bits) + 1, dtype=np.int64) << 14, side="right")
+    assert np.array_equal(got_guide, np.minimum(first, len(cdf) - 1))
+    for b in (0, 1, 777, (1 << bits) - 1):
+        assert got_guide[b] == int(np.argmax(cdf.astype(np.int64) > (b << 14)))
+    # zero-degree nodes own no draw: their cdf does not rise
+    steps = np.concatenate([[0], cdf.astype(np.int64)])
+    assert ((steps[1:] > steps[:-1]) <= (np.asarray(deg) > 0)).all()
+    g12 = unigram_cdf(deg, guide_bits=12)[1]
+    assert np.array_equal(g12, got_guide[::64])
+
+
 def test_cpp_csr_builder_matches_numpy():
     from graphsage_amd.utils import build_csr, build_csr_numpy
     rng = np.random.RandomState(0)
