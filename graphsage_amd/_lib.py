@@ -157,6 +157,8 @@ _PROTOS = {
                        c_int64, _P, _P, _P, _P, _P, _P],
     "gs_n2v_apply": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, c_int32,
                      _P, _P, _P, _P, _P, c_uint64, _P, c_uint64, _P],
+    "gs_csr_reduce_ws_bytes": [c_int64, c_int32, POINTER(c_int64)],
+    "gs_csr_reduce_fwd": [_P, _P],
 }
 
 
@@ -250,6 +252,23 @@ class LstmSeg(ctypes.Structure):
 
 
 assert ctypes.sizeof(LstmSeg) == 56      # static_assert in csrc/gs_lstm.hip (passed by pointer, not in gs_abi_struct_sizes)
+
+CSR_MEAN, CSR_MEAN_SELF, CSR_MAX = 0, 1, 2          # GS_CSR_* (ops of gs_csr_reduce_fwd)
+
+
+class CsrReduceDesc(ctypes.Structure):
+    """struct gs_csr_reduce_desc (include/graphsage_amd.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("items", c_void_p), ("splits", c_void_p), ("X", c_void_p),
+                ("out", c_void_p), ("ws", c_void_p),
+                ("n_rows", c_int64), ("nnz", c_int64), ("n_items", c_int64), ("n_split", c_int64),
+                ("ldx", c_int64), ("x_rows", c_int64), ("ldo", c_int64), ("ws_bytes", c_int64),
+                ("row0", c_int64), ("n", c_int64),
+                ("item0", c_int64), ("item1", c_int64), ("split0", c_int64), ("split1", c_int64), ("slot0", c_int64),
+                ("slot1", c_int64),
+                ("d", c_int32), ("op", c_int32), ("act", c_int32), ("split_len", c_int32)]
+
+
+assert ctypes.sizeof(CsrReduceDesc) == 200      # static_assert in csrc/gs_csr_reduce.hip (passed by pointer, as LstmSeg)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -354,6 +354,34 @@ class MeanAggregator(_SageBase):
             r += n
             row0 += n * s
 
+    def infer_full(self, graph, H):
+        """The layer for EVERY row of `graph` (inference.FullGraph) from ALL its neighbors: H [N + 1, d_in] -> [N + 1, n_out],
+        the pad row computed like any other; no dropout.  The mean is linear, so the narrower side is reduced: with concat and
+        output_dim < d_in the rows of H . W_neigh are averaged (602 -> 128 at Reddit's layer 0: 4.7 x fewer gathered bytes)."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in = self.output_dim, H.d
+        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
+        W_self, W_neigh = self.vars['self_weights'].value, self.vars['neigh_weights'].value
+        b = self.vars['bias'].value.buf if self.bias else None
+        if self.concat and not self.bias and o % 4 == 0 and o < d_in:
+            P = inf._table(e, graph.n_rows, o)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_neigh, P.rows_slice(r0, r0 + n), stream=e.stream)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                rows = out.rows_slice(r0, r0 + n)
+                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_self, rows.cols_slice(0, o), act=self.act_code,
+                         stream=e.stream)
+                graph.reduce(e, inf.CSR_MEAN, P, rows.cols_slice(o, 2 * o), r0, n, act=self.act_code)
+        else:
+            means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                graph.reduce(e, inf.CSR_MEAN, H, means, r0, n)
+                ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, means, None, n, W_self, W_neigh, o, self.concat, self.act_code,
+                                   b, out.rows_slice(r0, r0 + n), stream=e.stream)
+        e.sync()
+        return out
+
 
 class GCNAggregator(_SageBase):
     """Same matmul parameters for self and neighbor vectors (aggregators.py:66-116).
@@ -491,6 +519,30 @@ class GCNAggregator(_SageBase):
                               (h + 1 < len(neighs)), ("n", h))
             r += n
             row0 += n * s
+
+    def infer_full(self, graph, H):
+        """MeanAggregator.infer_full for the GCN layer: act(mean over {all neighbors} U {self} . W [+ b]) (aggregators.py:96-116).
+        The mean's weights sum to one, so when output_dim <= d_in the rows of H . W + b are averaged instead."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in = self.output_dim, H.d
+        out = inf._table(e, graph.n_rows, o)
+        W = self.vars['weights'].value
+        b = self.vars['bias'].value.buf if self.bias else None
+        if o % 4 == 0 and o <= d_in:
+            P = inf._table(e, graph.n_rows, o)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W, P.rows_slice(r0, r0 + n), bias=b, stream=e.stream)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                graph.reduce(e, inf.CSR_MEAN_SELF, P, out.rows_slice(r0, r0 + n), r0, n, act=self.act_code)
+        else:
+            means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
+            for r0, n in graph.windows(inf.WINDOW_ROWS):
+                graph.reduce(e, inf.CSR_MEAN_SELF, H, means, r0, n)
+                ops.sage_dense_fwd(None, None, means, None, n, None, W, o, False, self.act_code, b, out.rows_slice(r0, r0 + n),
+                                   stream=e.stream)
+        e.sync()
+        return out
 
 
 class _PoolingAggregator(_SageBase):
@@ -753,6 +805,28 @@ class _PoolingAggregator(_SageBase):
         ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
                             mask_y=prev_mask, stream=e.stream)
 
+    def infer_full(self, graph, H):
+        """MeanAggregator.infer_full for the pooling layers: the MLP (aggregators.py:176-179) runs once per NODE, then the hidden
+        table is max- / mean-reduced over every node's whole neighbor list, then the SAGE matmuls."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in, hid = self.output_dim, H.d, self.hidden_dim
+        mlp = self.mlp_layers[0]
+        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
+        Hh = inf._table(e, graph.n_rows, hid)
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            ops.gemm(False, False, n, hid, d_in, H.rows_slice(r0, r0 + n), mlp.vars['weights'].value, Hh.rows_slice(r0, r0 + n),
+                     bias=mlp.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
+        pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid)
+        b = self.vars['bias'].value.buf if self.bias else None
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            graph.reduce(e, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, pooled, r0, n)
+            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, pooled, None, n, self.vars['self_weights'].value,
+                               self.vars['neigh_weights'].value, o, self.concat, self.act_code, b, out.rows_slice(r0, r0 + n),
+                               stream=e.stream)
+        e.sync()
+        return out
+
 
 class MaxPoolingAggregator(_PoolingAggregator):
     """Aggregates via max-pooling over MLP functions (aggregators.py:119-195)."""
@@ -898,3 +972,7 @@ class SeqAggregator(_SageBase):
             hr += n * s
         ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=pull,
                             mask_y=prev_mask, stream=e.stream)
+
+    def infer_full(self, graph, H):
+        raise ops._lib.GraphsageAmdError("SeqAggregator has no full-neighborhood form: an LSTM over a random permutation of a "
+                                         "SAMPLE of the neighbors has no meaning over the whole list (use eval_step)")

@@ -1,0 +1,259 @@
+"""Exact, layer-wise, full-neighborhood inference.
+
+Training draws `num_samples` neighbors per node and recomputes a node's 2-hop tree in every batch it appears in.  Using a
+trained model asks for something else: layer 1 for ALL nodes from their WHOLE neighbor lists, then layer 2 from layer 1 --
+every node visited once per layer, no sampling noise.
+
+    graph = FullGraph.from_csr(rowptr, col, n_nodes)            # or FullGraph.from_padded(adj)
+    emb = model.embed_full(graph)                               # [N, d] l2-normalised (models.py:368-370)
+    emb, preds = sup_model.predict_full(graph)                  # + softmax / sigmoid head (supervised_models.py:86-93)
+
+`FullGraph` is a CSR adjacency over N + 1 rows (row N = the pad node) whose column ids have been checked ONCE, plus the
+work-item plan of the reduce kernel (gs_csr_reduce_fwd, csrc/gs_csr_reduce.hip).
+
+The pad-row rule.  The reference pads every adjacency row with the id N, and row N itself is [N, N, ...]
+(minibatch.py:227-245); the pad node's FEATURES are zero but its hidden states are not once a bias is trained
+(relu(0 . W + b) != 0).  So the pad row is computed like any other row, in every layer: `from_padded` keeps row N of the
+table as it is, `from_csr` gives the pad node -- and every node without neighbors, whose reference row is all pad -- the
+single neighbor N (a mean or max of identical entries is that entry).
+
+The split rule.  One wave reduces one work item; a row longer than `split_len` (512) edges is cut into items of at most that
+many, reduced by separate waves into a workspace and combined in segment order by a second small launch: a hub of thousands
+of neighbors does not outlive the launch, no float atomics, one fixed summation order.
+"""
+import numpy as np
+
+from . import ops
+from ._lib import CSR_MAX, CSR_MEAN, CSR_MEAN_SELF, GraphsageAmdError  # noqa: F401
+
+SPLIT_LEN = 512          # longest run of edges one wave reduces (rows beyond it are cut)
+
+
+def plan_work_items(rowptr, split_len=SPLIT_LEN):
+    """The work items of gs_csr_reduce_fwd for a CSR row pointer (NumPy, no device needed).
+
+    Returns (items, item_ptr, splits):
+      items    int64 [n_items, 4] = (row, first edge, count, partial slot or -1), rows ascending; a row of degree <= split_len
+               is one item (count 0 for an empty row); a longer row is cut into ceil(deg / split_len) items of at most split_len
+               edges with consecutive partial slots
+      item_ptr int64 [n_rows + 1]: the items of row r are items[item_ptr[r]: item_ptr[r + 1]]
+      splits   int64 [n_split, 3] = (row, first partial slot, partials) of the rows that were cut, rows ascending
+    """
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    L = int(split_len)
+    if L <= 0:
+        raise GraphsageAmdError("split_len must be positive")
+    n_rows = rowptr.shape[0] - 1
+    deg = np.diff(rowptr)
+    parts = np.where(deg > L, (deg + L - 1) // L, 1)
+    item_ptr = np.zeros(n_rows + 1, np.int64)
+    np.cumsum(parts, out=item_ptr[1:])
+    row = np.repeat(np.arange(n_rows, dtype=np.int64), parts)
+    k = np.arange(item_ptr[-1], dtype=np.int64) - item_ptr[row]
+    cut = np.flatnonzero(parts > 1)
+    first = np.zeros(cut.shape[0] + 1, np.int64)
+    np.cumsum(parts[cut], out=first[1:])
+    slot0 = np.full(n_rows, -1, np.int64)
+    slot0[cut] = first[:-1]
+    items = np.empty((row.shape[0], 4), np.int64)
+    items[:, 0] = row
+    items[:, 1] = rowptr[row] + k * L
+    items[:, 2] = np.minimum(L, deg[row] - k * L)
+    items[:, 3] = np.where(slot0[row] >= 0, slot0[row] + k, -1)
+    splits = np.stack([cut.astype(np.int64), first[:-1], parts[cut]], axis=1).reshape(-1, 3)
+    return items, item_ptr, splits
+
+
+def _is_torch(a):
+    return type(a).__module__.startswith("torch")
+
+
+class FullGraph(object):
+    """CSR adjacency over n_nodes + 1 rows (row n_nodes = the pad node), checked once, with its reduce plan."""
+
+    def __init__(self, rowptr, col, n_nodes, split_len=SPLIT_LEN):
+        self.n_nodes = int(n_nodes)
+        self.n_rows = self.n_nodes + 1
+        self.split_len = int(split_len)
+        self._on_device = _is_torch(rowptr)
+        if self._on_device != _is_torch(col):
+            raise GraphsageAmdError("FullGraph: rowptr and col must both be NumPy arrays or both device tensors")
+        if self._on_device:
+            import torch
+            if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.dim() != 1 or col.dim() != 1:
+                raise GraphsageAmdError("FullGraph: device CSR must be int64 rowptr / int32 col vectors")
+            self.rowptr, self.col = rowptr.contiguous(), col.contiguous()
+            rowptr_host = self.rowptr.cpu().numpy()
+        else:
+            self.rowptr = rowptr_host = np.ascontiguousarray(rowptr, dtype=np.int64)
+            col = np.asarray(col)
+            if col.size and (col.min() < np.iinfo(np.int32).min or col.max() > np.iinfo(np.int32).max):
+                raise GraphsageAmdError("FullGraph: column ids do not fit int32")
+            self.col = np.ascontiguousarray(col, dtype=np.int32)
+        self._check(rowptr_host)
+        self.nnz = int(rowptr_host[-1])
+        self.items, self.item_ptr, self.splits = plan_work_items(rowptr_host, self.split_len)
+        self._dev = {}
+
+    def _check(self, rowptr_host):
+        """rowptr non-decreasing from 0, rowptr[-1] == len(col), 0 <= col < n_rows: an id outside the table must never reach
+        the kernel."""
+        if rowptr_host.ndim != 1 or rowptr_host.shape[0] != self.n_rows + 1:
+            raise GraphsageAmdError("FullGraph: rowptr must have n_nodes + 2 = %d entries (got %s)"
+                                    % (self.n_rows + 1, rowptr_host.shape,))
+        if rowptr_host[0] != 0 or (np.diff(rowptr_host) < 0).any():
+            raise GraphsageAmdError("FullGraph: rowptr must start at 0 and be non-decreasing")
+        n_col = int(self.col.numel() if self._on_device else self.col.shape[0])
+        if int(rowptr_host[-1]) != n_col:
+            raise GraphsageAmdError("FullGraph: rowptr[-1] = %d but col has %d entries" % (int(rowptr_host[-1]), n_col))
+        if n_col:
+            lo, hi = int(self.col.min()), int(self.col.max())
+            if lo < 0 or hi >= self.n_rows:
+                raise GraphsageAmdError("FullGraph: column ids must lie in [0, %d] (found %d .. %d)" % (self.n_nodes, lo, hi))
+
+    # ------------------------------------------------------------------------------------------------ constructors
+    @classmethod
+    def from_padded(cls, adj, split_len=SPLIT_LEN):
+        """The reference's own multigraph: row v is adj[v] verbatim ([N + 1, max_degree] table of minibatch.py:227-259), the pad
+        row included.  With num_samples == max_degree the reference's forward pass is the full pass over this graph."""
+        adj = np.asarray(adj.cpu().numpy() if _is_torch(adj) else adj)
+        if adj.ndim != 2 or adj.shape[0] < 1:
+            raise GraphsageAmdError("FullGraph.from_padded: adj must be an [N + 1, max_degree] table")
+        rowptr = np.arange(adj.shape[0] + 1, dtype=np.int64) * adj.shape[1]
+        return cls(rowptr, adj.reshape(-1), adj.shape[0] - 1, split_len)
+
+    @classmethod
+    def from_csr(cls, rowptr, col, n_nodes, split_len=SPLIT_LEN):
+        """The true graph: rows 0 .. n_nodes - 1 are the CSR's neighbor lists; every node without neighbors and the pad node
+        n_nodes get the single neighbor n_nodes (the reference's all-pad row, minibatch.py:227-245).  NumPy arrays or
+        device-resident tensors (int64 rowptr [n_nodes + 1], int32 col)."""
+        n = int(n_nodes)
+        if _is_torch(rowptr):
+            import torch
+            if rowptr.numel() != n + 1:
+                raise GraphsageAmdError("FullGraph.from_csr: rowptr must have n_nodes + 1 entries")
+            rp = rowptr.to(torch.int64)
+            if int(rp[-1]) != col.numel() or int(rp[0]) != 0 or bool((rp[1:] < rp[:-1]).any()):
+                raise GraphsageAmdError("FullGraph.from_csr: rowptr must run from 0 to len(col) without decreasing")
+            deg = rp[1:] - rp[:-1]
+            new_deg = torch.cat([torch.where(deg == 0, torch.ones_like(deg), deg), torch.ones_like(deg[:1])])
+            new_rp = torch.zeros(n + 2, dtype=torch.int64, device=rp.device)
+            new_rp[1:] = torch.cumsum(new_deg, 0)
+            new_col = torch.full((int(new_rp[-1]),), n, dtype=torch.int32, device=rp.device)
+            if col.numel():
+                shift = torch.cumsum((deg == 0).to(torch.int64), 0) - (deg == 0).to(torch.int64)     # empty rows before each row
+                src_row = torch.repeat_interleave(torch.arange(n, device=rp.device), deg)
+                new_col[torch.arange(col.numel(), device=rp.device) + shift[src_row]] = col.to(torch.int32)
+            return cls(new_rp, new_col, n, split_len)
+        rp = np.asarray(rowptr, dtype=np.int64)
+        col = np.asarray(col)
+        if rp.ndim != 1 or rp.shape[0] != n + 1:
+            raise GraphsageAmdError("FullGraph.from_csr: rowptr must have n_nodes + 1 entries")
+        if rp[0] != 0 or (np.diff(rp) < 0).any() or int(rp[-1]) != col.shape[0]:
+            raise GraphsageAmdError("FullGraph.from_csr: rowptr must run from 0 to len(col) without decreasing")
+        deg = np.diff(rp)
+        new_deg = np.concatenate([np.where(deg == 0, 1, deg), [1]])
+        new_rp = np.zeros(n + 2, np.int64)
+        np.cumsum(new_deg, out=new_rp[1:])
+        new_col = np.full(int(new_rp[-1]), n, dtype=np.int64)
+        if col.shape[0]:
+            empty = (deg == 0).astype(np.int64)
+            shift = np.cumsum(empty) - empty
+            new_col[np.arange(col.shape[0]) + shift[np.repeat(np.arange(n), deg)]] = col
+        return cls(new_rp, new_col, n, split_len)
+
+    # ------------------------------------------------------------------------------------------------ host views
+    def lists(self):
+        """Neighbor list of every row (host copies; tests and oracles)."""
+        rp = self.rowptr.cpu().numpy() if self._on_device else self.rowptr
+        col = self.col.cpu().numpy() if self._on_device else self.col
+        return [col[rp[r]:rp[r + 1]] for r in range(self.n_rows)]
+
+    def window(self, row0, n):
+        """(item range, split range, slot range) of the rows [row0, row0 + n)."""
+        i0, i1 = int(self.item_ptr[row0]), int(self.item_ptr[row0 + n])
+        s0, s1 = (int(x) for x in np.searchsorted(self.splits[:, 0], [row0, row0 + n]))
+        t0 = int(self.splits[s0, 1]) if s0 < s1 else 0
+        t1 = int(self.splits[s1 - 1, 1] + self.splits[s1 - 1, 2]) if s0 < s1 else 0
+        return (i0, i1), (s0, s1), (t0, t1)
+
+    def windows(self, max_rows):
+        for r0 in range(0, self.n_rows, int(max_rows)):
+            yield r0, min(int(max_rows), self.n_rows - r0)
+
+    # ------------------------------------------------------------------------------------------------ device side
+    def on(self, device):
+        """(rowptr, col, items, splits) as tensors on `device` (uploaded once)."""
+        key = str(device)
+        if key not in self._dev:
+            import torch
+            up = (lambda a: a.to(device)) if self._on_device else (lambda a: torch.from_numpy(a).to(device))
+            col = up(self.col)
+            if col.numel() == 0:
+                col = torch.zeros(1, dtype=torch.int32, device=device)[:0]
+            splits = torch.from_numpy(self.splits).to(device) if self.splits.shape[0] else None
+            self._dev[key] = (up(self.rowptr), col, torch.from_numpy(self.items).to(device), splits)
+            torch.cuda.synchronize()
+        return self._dev[key]
+
+    def reduce(self, engine, op, X, out, row0, n, act=ops.ACT_IDENTITY):
+        """out[0:n] = op over the whole neighbor lists of rows [row0, row0 + n) of the rows of X ([>= n_rows, d] Mat)."""
+        if X.rows < self.n_rows:
+            raise GraphsageAmdError("FullGraph.reduce: the table has %d rows, the graph %d" % (X.rows, self.n_rows))
+        if out.rows < n or row0 < 0 or row0 + n > self.n_rows:
+            raise GraphsageAmdError("FullGraph.reduce: bad row window [%d, +%d)" % (row0, n))
+        rowptr, col, items, splits = self.on(engine.device)
+        item_r, split_r, slot_r = self.window(row0, n)
+        ws = None
+        if slot_r[1] > slot_r[0]:
+            words = ops.csr_reduce_ws_bytes(slot_r[1] - slot_r[0], X.d) // 4
+            ws = engine.ws_f32(("csr_reduce_ws",), max(1 << 16, 1 << (words - 1).bit_length()))     # few sizes, few buffers
+        ops.csr_reduce_fwd(rowptr, col, items, splits, self.n_rows, self.split_len, op, X, out, row0, n, item_r, split_r,
+                           slot_r, ws=ws, act=act, stream=engine.stream)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------- model passes
+WINDOW_ROWS = 32768      # rows per launch group: the per-window workspaces (means, pooled rows, partials) do not grow with N
+
+
+def _table(engine, rows, d, ld_multiple=4):
+    import torch
+    m = ops.Mat.zeros(rows, d, engine.device, ld_multiple)
+    torch.cuda.synchronize()          # the zero-fill ran on torch's stream; order it before the engine's
+    return m
+
+
+def check_graph(model, graph):
+    if not isinstance(graph, FullGraph):
+        raise GraphsageAmdError("full-neighborhood inference needs a FullGraph (FullGraph.from_csr / from_padded)")
+    if graph.n_rows != model.features.rows:
+        raise GraphsageAmdError("the graph has %d rows (N + 1), the feature table %d" % (graph.n_rows, model.features.rows))
+
+
+def layers_full(model, graph):
+    """hidden[K] of models.py:321-330 for EVERY row of the graph: [N + 1, dim_mult * dims[-1]] Mat (before l2_normalize)."""
+    check_graph(model, graph)
+    e = model.engine
+    e.sync()
+    H = model.features
+    for agg in model.aggregators:
+        H = agg.infer_full(graph, H)
+    return H
+
+
+def select_rows(model, table, nodes):
+    """(rows Mat [n, d], n): the rows `nodes` of a layer table (default: the N real nodes, in id order)."""
+    import torch
+    e = model.engine
+    if nodes is None:
+        return table.rows_slice(0, table.rows - 1), table.rows - 1
+    ids = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int64)
+    if ids.size and (ids.min() < 0 or ids.max() >= table.rows):
+        raise GraphsageAmdError("node ids must lie in [0, %d]" % (table.rows - 1))
+    ids_dev = torch.from_numpy(ids.astype(np.int32)).to(e.device)
+    torch.cuda.synchronize()
+    out = _table(e, max(ids.size, 1), table.d)
+    ops.gather_rows(table, ids_dev, out=out, stream=e.stream)
+    e.sync()
+    return out, int(ids.size)

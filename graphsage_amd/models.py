@@ -847,6 +847,18 @@ class SampleAndAggregate(object):
             agg.backward_hops(d_cur, pre_masked, d_prev=d_prev, prev_mask=mask, prev_offsets=prev_offsets)
             d_cur, pre_masked = d_prev, mask is not None
 
+    # ------------------------------------------------------------------------------ full-neighborhood inference
+    def embed_full(self, graph, nodes=None):
+        """l2-normalised embeddings (models.py:368-370) [n, d] (NumPy) of `nodes` (default: all N real nodes in id order) from
+        the exact layer-wise pass over `graph` (inference.FullGraph): every layer for every node from ALL its neighbors."""
+        from . import inference as inf
+        e = self.engine
+        rows, n = inf.select_rows(self, inf.layers_full(self, graph), nodes)
+        y = inf._table(e, max(n, 1), rows.d)
+        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
+        e.sync()
+        return y.numpy()[:n]
+
     # ------------------------------------------------------------------------------ step machinery (shared)
     def _samplers(self):
         seen = []

@@ -235,6 +235,30 @@ def mean_bwd(d_mean, n, s, scale, d_neigh, mask_y=None, accumulate=False, stream
     return d_neigh
 
 
+# ------------------------------------------------------------------------------------------ INF
+def csr_reduce_ws_bytes(n_slots, d):
+    """Bytes of the partials workspace gs_csr_reduce_fwd needs for n_slots segments of long rows at width d."""
+    out = ctypes.c_int64(0)
+    call("gs_csr_reduce_ws_bytes", n_slots, d, ctypes.byref(out))
+    return out.value
+
+
+def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, row0, n, item_range, split_range, slot_range,
+                   ws=None, act=ACT_IDENTITY, stream=None):
+    """gs_csr_reduce_fwd: out[r - row0] = mean | mean-with-self | max over the whole neighbor list of row r of X's rows, for the
+    window [row0, row0 + n) of a planned CSR graph (inference.FullGraph owns the plan and has checked the column ids)."""
+    q = _lib.CsrReduceDesc()
+    q.rowptr, q.col, q.items, q.splits = ptr(rowptr), ptr(col), ptr(items), ptr(splits)
+    q.X, q.out, q.ws = X.ptr, out.ptr, ptr(ws)
+    q.n_rows, q.nnz, q.n_items, q.n_split = n_rows, col.numel(), items.shape[0], (splits.shape[0] if splits is not None else 0)
+    q.ldx, q.x_rows, q.ldo, q.ws_bytes = X.ld, X.rows, out.ld, (4 * ws.numel() if ws is not None else 0)
+    q.row0, q.n = row0, n
+    (q.item0, q.item1), (q.split0, q.split1), (q.slot0, q.slot1) = item_range, split_range, slot_range
+    q.d, q.op, q.act, q.split_len = X.d, op, act, split_len
+    call("gs_csr_reduce_fwd", ctypes.addressof(q), _s(stream))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ K3
 def sage_dense_fwd(self_m, self_idx, agg, agg_idx, n, W_self, W_neigh, out_dim, concat, act, bias, out,
                    stream=None):

@@ -517,3 +517,27 @@ class SupervisedGraphsage(SampleAndAggregate):
     def predict(self):
         """sigmoid / softmax of the logits (supervised_models.py:122-126); filled by the last step."""
         return self.preds
+
+    def predict_full(self, graph, nodes=None):
+        """(embeddings [n, d], preds [n, C]) (NumPy) of `nodes` (default: all N real nodes) from the exact layer-wise pass over
+        `graph` (inference.FullGraph): l2_normalize, the prediction Dense and its softmax / sigmoid
+        (supervised_models.py:85-93, :122-126)."""
+        from . import inference as inf
+        e = self.engine
+        C = self.num_classes
+        rows, n = inf.select_rows(self, inf.layers_full(self, graph), nodes)
+        y = inf._table(e, max(n, 1), rows.d)
+        preds = inf._table(e, max(n, 1), C)
+        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
+        w = min(inf.WINDOW_ROWS, max(n, 1))
+        logits = e.ws_mat((self.name, "full_logits"), w, C)
+        no_labels = e.ws_mat((self.name, "full_no_labels"), w, C)          # gs_class_loss also forms the loss: unused here
+        loss_rows = e.ws_f32((self.name, "full_loss_rows"), w)
+        for r0 in range(0, n, w):
+            m = min(w, n - r0)
+            ops.gemm(False, False, m, C, y.d, y.rows_slice(r0, r0 + m), self.node_pred.vars['weights'].value, logits,
+                     bias=self.node_pred.vars['bias'].value.buf, stream=e.stream)
+            ops.class_loss(logits, no_labels, m, C, self.sigmoid_loss, loss_rows, preds=preds.rows_slice(r0, r0 + m),
+                           stream=e.stream)
+        e.sync()
+        return y.numpy()[:n], preds.numpy()[:n]

@@ -62,10 +62,48 @@ def build_flags(argv=None):
     p.add_argument('--feed_path', default='device',
                    help='device: epoch order + labels resident in HBM, host fetches only printed steps (CSR sampler); '
                         'host: the reference feed_dict path, one host round trip per step')
+    p.add_argument('--full_inference', type=b, nargs='?', const=True, default=False,
+                   help='after training: exact layer-wise inference over every node\'s WHOLE neighbor list on the test graph '
+                        '(predict_full) -> val_stats_full.txt / test_stats_full.txt; not for graphsage_seq')
     return p.parse_args(argv)
 
 
 FLAGS = None
+
+
+def refuse_full_inference(flags):
+    """--full_inference has no meaning for the models without a full-neighborhood form: say so before any work is done."""
+    if getattr(flags, "full_inference", False) and flags.model in ('n2v', 'graphsage_seq'):
+        raise SystemExit("--full_inference is not available with --model %s: %s" % (
+            flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v' else
+            "an LSTM over a random permutation of a neighbor sample has no full-neighborhood form"))
+
+
+def full_graph(minibatch, n_nodes):
+    """The test graph for full-neighborhood inference: the padded test table verbatim under --sampler padded, else the CSR."""
+    from .inference import FullGraph
+    if minibatch.test_adj is not None:
+        return FullGraph.from_padded(minibatch.test_adj)
+    return FullGraph.from_csr(minibatch.test_csr[0], minibatch.test_csr[1], n_nodes)
+
+
+def full_inference_stats(model, minibatch, n_nodes):
+    """Exact inference for every node at once (model.predict_full), scored on the validation and the test nodes."""
+    t_test = time.time()
+    _, preds = model.predict_full(full_graph(minibatch, n_nodes))
+    duration = time.time() - t_test
+    stats = []
+    for nodes in (minibatch.val_nodes, minibatch.test_nodes):
+        stats.append(calc_f1(minibatch.label_matrix[nodes], preds[nodes]) if len(nodes) else (0.0, 0.0))
+    print("Full-neighborhood validation stats:",
+          "f1_micro=", "{:.5f}".format(stats[0][0]),
+          "f1_macro=", "{:.5f}".format(stats[0][1]),
+          "time=", "{:.5f}".format(duration))
+    with open(log_dir() + "val_stats_full.txt", "w") as fp:
+        fp.write("f1_micro={:.5f} f1_macro={:.5f} time={:.5f}".format(stats[0][0], stats[0][1], duration))
+    with open(log_dir() + "test_stats_full.txt", "w") as fp:
+        fp.write("f1_micro={:.5f} f1_macro={:.5f}".format(stats[1][0], stats[1][1]))
+    return stats
 
 
 def f1_micro_macro(y_true, y_pred, multilabel):
@@ -329,12 +367,15 @@ def train(G):
     val_cost, val_f1_mic, val_f1_mac, duration = incremental_evaluate(model, minibatch, FLAGS.batch_size, test=True)
     with open(log_dir() + "test_stats.txt", "w") as fp:
         fp.write("loss={:.5f} f1_micro={:.5f} f1_macro={:.5f}".format(val_cost, val_f1_mic, val_f1_mac))
+    if FLAGS.full_inference:
+        full_inference_stats(model, minibatch, G.n_nodes)
     return val_f1_mic
 
 
 def main(argv=None):
     global FLAGS
     FLAGS = build_flags(argv)
+    refuse_full_inference(FLAGS)
     print("Loading training data..")
     G = load_graph()
     print("Done loading training data..")

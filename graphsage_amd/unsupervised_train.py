@@ -61,6 +61,9 @@ def build_flags(argv=None):
                         'ignored by --model n2v')
     p.add_argument('--bilinear_weights', action='store_true',
                    help='affinity u^T A v with a trainable A (prediction.py:68-92); ignored by --model n2v')
+    p.add_argument('--full_inference', type=b, nargs='?', const=True, default=False,
+                   help='after val.npy: exact layer-wise embeddings of ALL nodes from their whole neighbor lists on the test '
+                        'graph (embed_full) -> val_full.npy / val_full.txt; not for n2v / graphsage_seq')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     return p.parse_args(argv)
 
@@ -131,6 +134,20 @@ def save_val_embeddings(model, minibatch_iter, size, out_dir, mod=""):
     np.save(out_dir + name + mod + ".npy", val_embeddings)
     with open(out_dir + name + mod + ".txt", "w") as fp:
         fp.write("\n".join(map(str, nodes)))
+
+
+def save_full_embeddings(model, minibatch, out_dir):
+    """val_full.npy: the exact (full-neighborhood, layer-wise) embeddings of all N nodes in id order; val_full.txt: their
+    ORIGINAL ids, as val.txt lists them."""
+    from .supervised_train import full_graph
+    G = minibatch.G
+    emb = model.embed_full(full_graph(minibatch, G.n_nodes))
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    np.save(out_dir + "val_full.npy", emb)
+    ids = getattr(G, "node_ids", None)
+    with open(out_dir + "val_full.txt", "w") as fp:
+        fp.write("\n".join(str(ids[i] if ids is not None else i) for i in range(G.n_nodes)))
 
 
 def construct_placeholders():
@@ -237,6 +254,8 @@ def train(G, context_pairs):
     if FLAGS.save_embeddings:
         adj_info.assign(test_adj)
         save_val_embeddings(model, minibatch, FLAGS.validate_batch_size, log_dir())
+        if FLAGS.full_inference:
+            save_full_embeddings(model, minibatch, log_dir())
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
     return shadow_mrr
@@ -286,6 +305,7 @@ def main(argv=None):
     FLAGS = build_flags(argv)
     from . import utils
     from . import supervised_train as st
+    st.refuse_full_inference(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)
     G = st.load_graph()

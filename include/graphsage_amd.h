@@ -936,7 +936,48 @@ int gs_n2v_apply(float* target, int64_t ldt, float* context, int64_t ldc, float*
                  void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Host-side graph ingestion (C++, multithreaded): edge list -> CSR.  Replaces the networkx loops of
+ * INF  full-neighborhood inference: a variable-degree segmented reduce over a CSR adjacency (rowptr int64 [n_rows + 1],
+ *      col int32 [nnz], as gs_sample_uniform_csr), for the rows of a window [row0, row0 + n):
+ *        GS_CSR_MEAN       out[r - row0] = sum_e X[col[e]] / deg                       (aggregators.py:48, all neighbors)
+ *        GS_CSR_MEAN_SELF  out[r - row0] = (sum_e X[col[e]] + X[r]) / (deg + 1)        (the GCN mean, aggregators.py:96-99)
+ *        GS_CSR_MAX        out[r - row0] = max_e X[col[e]]                             (no arg-max: inference only)
+ *      over e in [rowptr[r], rowptr[r+1]); duplicate entries count as often as they occur; an empty row gives 0 (X[r] for
+ *      GS_CSR_MEAN_SELF); act = GS_ACT_RELU applies relu to the result.  fp32 rows, ld >= round_up(d, 4); columns at and
+ *      beyond round_up(d, 4) and rows outside the window are not written.
+ *      The launch follows a work-item plan built once per graph by the caller (graphsage_amd/inference.py):
+ *        items  int64 [n_items][4] = (row, first edge, count <= split_len, partial slot or -1), rows ascending, every row at
+ *               least one item (count 0 for an empty row); a row longer than split_len is cut into items of at most
+ *               split_len edges, numbered by consecutive partial slots;
+ *        splits int64 [n_split][3] = (row, first partial slot, partials) of those rows, rows ascending.
+ *      [item0, item1), [split0, split1) and [slot0, slot1) are the window's ranges.  Partials go to ws (gs_csr_reduce_ws_bytes
+ *      for slot1 - slot0 slots) and a second launch combines each long row's partials in slot order: no float atomics, a fixed
+ *      order of additions, bitwise reproducible.  EVERY col entry must lie in [0, n_rows) and x_rows >= n_rows: the caller
+ *      checks its graph once (the kernel does not look at the ids again).
+ *      gs_csr_reduce_desc is 200 bytes on every target (checked at compile time and by the binding; passed by pointer, not
+ *      part of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_CSR_MEAN 0
+#define GS_CSR_MEAN_SELF 1
+#define GS_CSR_MAX 2
+typedef struct gs_csr_reduce_desc {
+    const int64_t* rowptr;     /* device [n_rows + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const int64_t* items;      /* device [n_items][4] */
+    const int64_t* splits;     /* device [n_split][3]; nullable when n_split == 0 */
+    const float* X;            /* [x_rows, ldx] */
+    float* out;                /* [n, ldo]: row r of the window is out row r - row0 */
+    float* ws;                 /* partials of the window's long rows; nullable when it has none */
+    int64_t n_rows, nnz, n_items, n_split;
+    int64_t ldx, x_rows, ldo, ws_bytes;
+    int64_t row0, n;
+    int64_t item0, item1, split0, split1, slot0, slot1;
+    int32_t d, op, act, split_len;
+} gs_csr_reduce_desc;
+int gs_csr_reduce_ws_bytes(int64_t n_slots, int32_t d, int64_t* bytes_out_host);
+int gs_csr_reduce_fwd(const gs_csr_reduce_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
  * Adjacency lists come out sorted and de-duplicated (networkx.Graph semantics: one edge per node pair).
