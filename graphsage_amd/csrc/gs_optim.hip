@@ -52,6 +52,8 @@ extern "C" int gs_reduce_slabs(const float* slabs, int32_t n_slabs, int64_t slab
                                int64_t ld_slab, float weight_decay, const float* w, int64_t ldw, float* grad,
                                int64_t ldg, int accumulate, void* stream) {
     GS_REQUIRE(slabs && grad && n_slabs > 0 && rows > 0 && cols > 0, "gs_reduce_slabs: bad args");
+    GS_REQUIRE(ld_slab >= cols && ldg >= cols && (!w || ldw >= cols),
+               "gs_reduce_slabs: ld_slab, ldg and ldw must be >= cols (rows would overlap)");
     const int64_t total = (int64_t)rows * cols;
     int blocks = (int)std::min<int64_t>(gs_ceil_div(total, 32), 4096);
     hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, slabs, n_slabs, slab_stride,
