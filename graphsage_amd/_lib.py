@@ -146,6 +146,11 @@ _PROTOS = {
     "gs_finalize_step2": [_P, c_int64, c_float, _P, c_int, _P, c_float, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P],
     "gs_maxpool_sparse_wgrad": [_P, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, c_int64, c_int32, c_int32, _P,
                                 c_int64, _P],
+    "gs_pool2_transpose": [_P, c_int64, c_int32, c_int32, _P, c_int64, _P],
+    "gs_pool2_iota": [_P, c_int64, _P],
+    "gs_pool2_dgrad_t": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int64,
+                         _P],
+    "gs_pool2_dgrad": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int64, _P],
     "gs_stage_batch": [_P, c_int64, _P, c_int64, _P, _P, c_int64, c_int32, _P, c_int64, _P],
     "gs_lstm_lengths": [_P, c_int32, c_int32, _P, _P],
     "gs_lstm_fwd": [_P, c_int32, c_int32, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],

@@ -136,6 +136,75 @@ class _SageBase(Layer):
         ops.act_bwd(d_self_all, prev_mask.rows_slice(0, n_total) if prev_mask is not None else None, n_total,
                     d_self_all.d, act, d_prev.rows_slice(0, n_total), stream=e.stream)
 
+    def _dedup_wanted(self, x_all, rows_total):
+        """Run the pooling MLP once per DISTINCT sampled id of the step?  (_PoolingAggregator.call_hops)"""
+        dedup_min = getattr(self, "dedup_min_rows", None)
+        if dedup_min is None:
+            dedup_min = int(os.environ.get("GS_POOL_DEDUP_MIN_ROWS", "2048"))
+        return (x_all is not None and x_all.ids is not None and rows_total > dedup_min
+                and x_all.src.rows < (1 << 31)
+                and x_all.src.rows <= int(os.environ.get("GS_POOL_DEDUP_MAX_RATIO", "16")) * rows_total
+                and getattr(self, "dedup_pool", True))
+
+    def _mlp_distinct(self, mlp, hidden, x_all, rows_total, k):
+        """relu(X[uniq] . W + b) over the step's distinct ids: (H [rows_total, hidden] with the device count's leading rows
+        filled, inv [rows_total], count).  Records the kernel taken in last_pool_kernel."""
+        e = self.engine
+        X, ids, nv_rows = x_all.src, x_all.ids, x_all.src.rows
+        rank_ws = e.ws_i32((self.name, "dd_rank", k), 2 * nv_rows)       # [flags | ranks]: zero-initialised, self-cleaning
+        sums_ws = e.ws_i32((self.name, "dd_sums", k), 256)
+        uniq = e.ws_i32((self.name, "dd_uniq", k), rows_total)
+        inv = e.ws_i32((self.name, "dd_inv", k), rows_total)
+        cnt = e.ws_i32((self.name, "dd_count", k), 1)
+        ops.call("gs_unique_ids", ops.ptr(ids), rows_total, nv_rows, ops.ptr(rank_ws), ops.ptr(sums_ws), ops.ptr(uniq),
+                 ops.ptr(inv), ops.ptr(cnt), e.stream)
+        Hu = e.ws_mat((self.name, "H_unique", k), rows_total, hidden)
+        W, bmlp = mlp.vars['weights'].value, mlp.vars['bias'].value.buf
+        self.last_pool_kernel = None
+        if (e.split_pool and e.pool_f16 and not x_all.requires_grad and e.is_constant_table(X) and e.table16_fits(X)):
+            # ... on the fp16 matrix pipe, operands as two fp16 pieces each (fp32 accuracy class, half the matrix-pipe work of
+            # the three-piece form below, which is bound by the chip's POWER cap): the constant feature table is cut once.
+            # A table with trainable leading columns (identity features, rewritten behind every optimizer launch) is NOT
+            # constant -- its cut-once copy would be stale from the second step on -- and takes the three-piece kernel below,
+            # which cuts the rows it reads in registers.
+            self.last_pool_kernel = "split16"
+            X2, rexp = e.table16_of(X)
+            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
+            ops.call("gs_dense_fwd_rows_split16", ops.ptr(X2), ops.ptr(rexp), ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
+                     ops.ptr(e.split_of(mlp.vars['weights'], form="f16x2")), hidden, ACT_RELU, ops.ptr(bmlp),
+                     Hu.ptr, Hu.ld, ops.ptr(ws), 4 * ws.numel(), e.stream)
+        elif e.split_pool:
+            # the 51 GF of the pooling MLP on the bf16 matrix pipe, operands as three bf16 pieces (fp32 accuracy)
+            # (+ a workspace: the last, nearly empty round of its one-per-CU workgroups is cut along K, gs_split.hip)
+            self.last_pool_kernel = "split_bf16x3"
+            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
+            ops.call("gs_dense_fwd_rows_split_ws", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
+                     ops.ptr(e.split_of(mlp.vars['weights'])), hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld,
+                     ops.ptr(ws), 4 * ws.numel(), e.stream)
+        else:
+            self.last_pool_kernel = "fp32_mfma"
+            ops.call("gs_dense_fwd_rows_dev", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt), W.ptr, W.ld,
+                     hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld, e.stream)
+        return Hu, inv, cnt
+
+    def _sage_out(self, self_all, pooled, n_total, k):
+        """from_self / from_neighs matmuls + concat|add + bias + act over the pooled neighborhood vectors (all hops, one launch)."""
+        e = self.engine
+        n_out = self.output_dim * (2 if self.concat else 1)
+        out = e.ws_mat((self.name, "out", k), n_total, n_out)
+        b = self.vars['bias'].value.buf if self.bias else None
+        if e.stream_gemm and self.concat and n_total > 2048 and self.output_dim % 2 == 0:
+            # the stream form of the two contractions (split-K workgroups, no LDS staging, the self rows gathered in the A loads),
+            # with each term's own reduction length: 23 instead of 33 us for the Reddit step's layer 0
+            (ops.sage_dense_fwd_tiled3 if (e.tiled3_fwd and self.output_dim % 4 == 0) else ops.sage_dense_fwd_stream2)(
+                self_all.src, self_all.ids, pooled, n_total, self.vars['self_weights'].value, self.vars['neigh_weights'].value,
+                self.output_dim, self.act_code, b, out, stream=e.stream)
+        else:
+            ops.sage_dense_fwd(self_all.src, self_all.ids, pooled, None, n_total, self.vars['self_weights'].value,
+                               self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b, out,
+                               stream=e.stream)
+        return out
+
 
 class MeanAggregator(_SageBase):
     """Aggregates via mean followed by matmul and non-linearity (aggregators.py:6-64)."""
@@ -611,50 +680,10 @@ class _PoolingAggregator(_SageBase):
         # through an index (37 % fewer GEMM rows at Reddit's degree)
         # gs_unique_ids makes three passes over a flag word per TABLE row (independent of the batch): worth it while the table
         # is within a small multiple of the step's sampled rows (Reddit: 233 k rows for 133 k ids), not for 10^7-node graphs
-        dedup_min = getattr(self, "dedup_min_rows", None)
-        if dedup_min is None:
-            dedup_min = int(os.environ.get("GS_POOL_DEDUP_MIN_ROWS", "2048"))
-        dedup = (fused_pool and x_all is not None and x_all.ids is not None and rows_total > dedup_min
-                 and x_all.src.rows < (1 << 31)
-                 and x_all.src.rows <= int(os.environ.get("GS_POOL_DEDUP_MAX_RATIO", "16")) * rows_total
-                 and getattr(self, "dedup_pool", True))
+        dedup = fused_pool and self._dedup_wanted(x_all, rows_total)
         H = None
         if dedup:
-            X, ids, nv_rows = x_all.src, x_all.ids, x_all.src.rows
-            rank_ws = e.ws_i32((self.name, "dd_rank", k), 2 * nv_rows)       # [flags | ranks]: zero-initialised, self-cleaning
-            sums_ws = e.ws_i32((self.name, "dd_sums", k), 256)
-            uniq = e.ws_i32((self.name, "dd_uniq", k), rows_total)
-            inv = e.ws_i32((self.name, "dd_inv", k), rows_total)
-            cnt = e.ws_i32((self.name, "dd_count", k), 1)
-            ops.call("gs_unique_ids", ops.ptr(ids), rows_total, nv_rows, ops.ptr(rank_ws), ops.ptr(sums_ws), ops.ptr(uniq),
-                     ops.ptr(inv), ops.ptr(cnt), e.stream)
-            Hu = e.ws_mat((self.name, "H_unique", k), rows_total, self.hidden_dim)
-            W, bmlp = mlp.vars['weights'].value, mlp.vars['bias'].value.buf
-            self.last_pool_kernel = None
-            if (e.split_pool and e.pool_f16 and not x_all.requires_grad and e.is_constant_table(X) and e.table16_fits(X)):
-                # ... on the fp16 matrix pipe, operands as two fp16 pieces each (fp32 accuracy class, half the matrix-pipe work of
-                # the three-piece form below, which is bound by the chip's POWER cap): the constant feature table is cut once.
-                # A table with trainable leading columns (identity features, rewritten behind every optimizer launch) is NOT
-                # constant -- its cut-once copy would be stale from the second step on -- and takes the three-piece kernel below,
-                # which cuts the rows it reads in registers.
-                self.last_pool_kernel = "split16"
-                X2, rexp = e.table16_of(X)
-                ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
-                ops.call("gs_dense_fwd_rows_split16", ops.ptr(X2), ops.ptr(rexp), ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
-                         ops.ptr(e.split_of(mlp.vars['weights'], form="f16x2")), self.hidden_dim, ACT_RELU, ops.ptr(bmlp),
-                         Hu.ptr, Hu.ld, ops.ptr(ws), 4 * ws.numel(), e.stream)
-            elif e.split_pool:
-                # the 51 GF of the pooling MLP on the bf16 matrix pipe, operands as three bf16 pieces (fp32 accuracy)
-                # (+ a workspace: the last, nearly empty round of its one-per-CU workgroups is cut along K, gs_split.hip)
-                self.last_pool_kernel = "split_bf16x3"
-                ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
-                ops.call("gs_dense_fwd_rows_split_ws", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
-                         ops.ptr(e.split_of(mlp.vars['weights'])), self.hidden_dim, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld,
-                         ops.ptr(ws), 4 * ws.numel(), e.stream)
-            else:
-                self.last_pool_kernel = "fp32_mfma"
-                ops.call("gs_dense_fwd_rows_dev", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt), W.ptr, W.ld,
-                         self.hidden_dim, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld, e.stream)
+            Hu, inv, cnt = self._mlp_distinct(mlp, self.hidden_dim, x_all, rows_total, k)
             r = hr = 0
             for nv in neighs:
                 n, s, _ = nv.shape3
@@ -702,19 +731,7 @@ class _PoolingAggregator(_SageBase):
                                         stream=e.stream)                                             # reduce_mean (:259)
                 r += n
                 hr += n * s
-        n_out = self.output_dim * (2 if self.concat else 1)
-        out = e.ws_mat((self.name, "out", k), n_total, n_out)
-        b = self.vars['bias'].value.buf if self.bias else None
-        if e.stream_gemm and self.concat and n_total > 2048 and self.output_dim % 2 == 0:
-            # the stream form of the two contractions (split-K workgroups, no LDS staging, the self rows gathered in the A loads),
-            # with each term's own reduction length: 23 instead of 33 us for the Reddit step's layer 0
-            (ops.sage_dense_fwd_tiled3 if (e.tiled3_fwd and self.output_dim % 4 == 0) else ops.sage_dense_fwd_stream2)(
-                self_all.src, self_all.ids, pooled, n_total, self.vars['self_weights'].value, self.vars['neigh_weights'].value,
-                self.output_dim, self.act_code, b, out, stream=e.stream)
-        else:
-            ops.sage_dense_fwd(self_all.src, self_all.ids, pooled, None, n_total, self.vars['self_weights'].value,
-                               self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b, out,
-                               stream=e.stream)
+        out = self._sage_out(self_all, pooled, n_total, k)
         self._push((self_all, neighs, pieces, (H, rows_total), pooled, argmax, out, rate))
         return out
 
@@ -976,3 +993,251 @@ class SeqAggregator(_SageBase):
     def infer_full(self, graph, H):
         raise ops._lib.GraphsageAmdError("SeqAggregator has no full-neighborhood form: an LSTM over a random permutation of a "
                                          "SAMPLE of the neighbors has no meaning over the whole list (use eval_step)")
+
+
+class TwoMaxLayerPoolingAggregator(_SageBase):
+    """Aggregates via pooling over two MLP functions (aggregators.py:276-361): Dense(in -> hid1, relu), Dense(hid1 -> hid2,
+    relu) over every neighbor row, reduce_max over the s samples, then the SAGE matmuls.  hid1 / hid2 = 512 / 256 ("small")
+    or 1024 / 512 ("big").  Neither Dense is in aggregator.vars (no weight decay; still clipped and updated by Adam).
+
+    Layer 1 runs as _PoolingAggregator's MLP does (once per distinct id of the step where that pays) and is kept as H1; layer 2
+    and the reduce_max are one launch per hop (gs_dense_pool_max_fwd over H1), or layer 2 per distinct row and
+    gs_segment_max_gather_fwd.  Backward: the W2 gradient comes from the arg-max rows of H1 alone (gs_maxpool_sparse_wgrad),
+    and dH1 -- the pooled gradient taken back through W2 and the first relu to EVERY neighbor row -- from gs_pool2_dgrad
+    (`fuse_dgrad`; False, or a shape outside the kernel's range: gs_segment_max_bwd + gs_dense_dgrad + gs_act_bwd).
+
+    Dropout is refused: the reference drops the input of both Dense layers, and the second has no mask site here."""
+
+    def __init__(self, input_dim, output_dim, model_size="small", neigh_input_dim=None, dropout=0., bias=False,
+                 act=relu, name=None, concat=False, **kwargs):
+        super(TwoMaxLayerPoolingAggregator, self).__init__(**kwargs)
+        self.dropout = dropout
+        self.bias = bias
+        self.act = act
+        self.act_code = _act_code(act)
+        self.concat = concat
+        if neigh_input_dim is None:
+            neigh_input_dim = input_dim
+        if model_size == "small":
+            hidden_dim_1, hidden_dim_2 = 512, 256
+        elif model_size == "big":
+            hidden_dim_1, hidden_dim_2 = 1024, 512
+        else:
+            raise ops._lib.GraphsageAmdError("model_size must be 'small' or 'big'")
+        self.hidden_dim_1, self.hidden_dim_2 = hidden_dim_1, hidden_dim_2
+        self.mlp_layers = []
+        self.mlp_layers.append(Dense(input_dim=neigh_input_dim, output_dim=hidden_dim_1, act=relu, dropout=dropout,
+                                     sparse_inputs=False, logging=self.logging))
+        self.mlp_layers.append(Dense(input_dim=hidden_dim_1, output_dim=hidden_dim_2, act=relu, dropout=dropout,
+                                     sparse_inputs=False, logging=self.logging))
+        # the MLP weights are NOT part of aggregator.vars (aggregators.py:303-325) -> no weight decay
+        for layer in self.mlp_layers:
+            for v in layer.vars.values():
+                v.decay = False
+        scope = _scope(self.name, name)
+        e = self.engine
+        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((hidden_dim_2, output_dim)), decay=True)
+        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
+        if self.bias:
+            self.vars['bias'] = e.add_variable(scope + '/bias', zeros(((2 if concat else 1) * output_dim,)), decay=True)
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        self.neigh_input_dim = neigh_input_dim
+        self.fuse_dgrad = True          # dH1 by gs_pool2_dgrad; False = the three-launch composition
+        self.last_dgrad_kernel = None   # "pool2_dgrad" | "composed": what the last backward pass took
+        self.last_dgrad_indexed = None  # ... and whether it read H1 through the distinct-id index
+        self._saved = []
+
+    def prefetch(self, self_all, neighs, tag=0):
+        return None   # the pooling MLP needs the weights: nothing can run ahead
+
+    def prefetch_jobs(self, self_all, neighs, tag=0):
+        return None, []
+
+    def call_hops(self, self_all, neighs, means=None, side_jobs=None):
+        e = self.engine
+        if _rate(self.dropout) > 0:
+            raise ops._lib.GraphsageAmdError("dropout > 0 is not supported with the two-layer max-pooling aggregator "
+                                             "(graphsage_twomaxpool)")
+        _run_jobs(e, side_jobs)
+        n_total = self_all.n
+        k = len(self._saved)
+        mlp1, mlp2 = self.mlp_layers
+        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
+        W2, b2 = mlp2.vars['weights'].value, mlp2.vars['bias'].value.buf
+        flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
+        rows_total = sum(x.n for x in flat)
+        x_all = _contiguous(flat)
+        pieces = [x_all] if x_all is not None else flat
+        pooled = e.ws_mat((self.name, "pooled2", k), n_total, hid2)
+        argmax = e.ws_i32((self.name, "argmax2", k), n_total * hid2).view(n_total, hid2)
+        fused_pool = getattr(self, "fuse_pool", True) and all(nv.shape3[1] <= 64 for nv in neighs)
+        self.last_pool_kernel = self.last_unique = None
+        inv = None
+        if fused_pool and self._dedup_wanted(x_all, rows_total):
+            # layer 1, then layer 2, once per DISTINCT id of the step; the reduce_max picks rows through `inv`
+            H1, inv, cnt = self._mlp_distinct(mlp1, hid1, x_all, rows_total, k)
+            H2 = e.ws_mat((self.name, "H2_unique", k), rows_total, hid2)
+            ops.sage_dense_fwd(None, None, H1, None, rows_total, None, W2, hid2, False, ACT_RELU, b2, H2, stream=e.stream)
+            r = hr = 0
+            for nv in neighs:
+                n, s, _ = nv.shape3
+                pr, ar = pooled.rows_slice(r, r + n), argmax[r:r + n]
+                ops.call("gs_segment_max_gather_fwd", H2.ptr, H2.ld, inv.data_ptr() + 4 * hr, n, s, hid2, pr.ptr, pr.ld,
+                         ar.data_ptr(), argmax.stride(0), e.stream)
+                r += n
+                hr += n * s
+            self.last_unique = (cnt, rows_total)
+        else:
+            # h = Dense(reshape(neigh, [n*s, d]))   (aggregators.py:338-341, first layer): one GEMM over every neighbor row
+            H1 = e.ws_mat((self.name, "H1", k), rows_total, hid1)
+            r = 0
+            for x in pieces:
+                ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, mlp1.vars['weights'].value, hid1, False, ACT_RELU,
+                                   mlp1.vars['bias'].value.buf, H1.rows_slice(r, r + x.n), stream=e.stream)
+                r += x.n
+            H2 = None
+            if not fused_pool:
+                H2 = e.ws_mat((self.name, "H2", k), rows_total, hid2)
+                ops.sage_dense_fwd(None, None, H1, None, rows_total, None, W2, hid2, False, ACT_RELU, b2, H2, stream=e.stream)
+            r = hr = 0
+            for nv in neighs:
+                n, s, _ = nv.shape3
+                if fused_pool:         # second Dense + reduce_max (:341) in ONE launch: [n*s, hid2] never exists
+                    ops.dense_pool_max_fwd(H1.rows_slice(hr, hr + n * s), None, n, s, W2, b2, pooled.rows_slice(r, r + n),
+                                           argmax[r:r + n], stream=e.stream)
+                else:
+                    ops.segment_max_fwd(H2.rows_slice(hr, hr + n * s), n, s, pooled.rows_slice(r, r + n), argmax[r:r + n],
+                                        stream=e.stream)
+                r += n
+                hr += n * s
+        out = self._sage_out(self_all, pooled, n_total, k)
+        self._push((self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out))
+        return out
+
+    def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
+        e = self.engine
+        self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out = self._saved.pop()
+        n_total = self_all.n
+        k = len(self._saved)
+        o = self.output_dim
+        n_out = o * (2 if self.concat else 1)
+        mlp1, mlp2 = self.mlp_layers
+        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
+        W1, W2 = mlp1.vars['weights'], mlp2.vars['weights']
+        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
+        col_n = o if self.concat else 0
+        e.wgrad(self.vars['self_weights'], self_all.src, self_all.ids, dz, 0, n_total)
+        e.wgrad(self.vars['neigh_weights'], pooled, None, dz, col_n, n_total)
+        if self.bias:
+            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        d_pooled = e.ws_mat((self.name, "d_pooled2", k), n_total, hid2)
+        ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, d_pooled, stream=e.stream)
+        # reduce_max grad then the second Dense's relu grad: only the arg-max row of each (group, column), where pooled > 0
+        dpm = e.ws_mat((self.name, "d_pooled2_masked", k), n_total, hid2)
+        ops.act_bwd(d_pooled, pooled, n_total, hid2, ACT_RELU, dpm, stream=e.stream)
+        e.bgrad(mlp2.vars['bias'], dpm, n_total, hid2)           # column sums of dH2 == column sums of dpm
+        # the range of gs_pool2_dgrad, and of gs_maxpool_sparse_wgrad (16 s <= 4 min(512, round_up(hid2, 64))): at both model sizes
+        # that is s <= 64
+        s_max = max(nv.shape3[1] for nv in neighs)
+        fits = ops.pool2_dgrad_supported(s_max, hid1, hid2) and 16 * s_max <= 4 * min(512, (hid2 + 63) // 64 * 64)
+        fused = self.fuse_dgrad and fits
+        self.last_dgrad_kernel = "pool2_dgrad" if fused else "composed"
+        self.last_dgrad_indexed = inv is not None                # H1 held one row per distinct id, read through h_idx
+        dH1 = e.ws_mat((self.name, "dH1", k), rows_total, hid1)
+        H1x = H1                                                 # H1 per sampled row, for the dense forms
+        if fused:
+            W2T = e.ws_mat((self.name, "W2T"), hid2, hid1)       # this step's W2^T: re-made in every backward pass
+            ops.pool2_transpose(W2.value, W2T, stream=e.stream)
+        else:
+            dH2 = e.ws_mat((self.name, "dH2", k), rows_total, hid2)
+            if inv is not None:
+                H1x = e.ws_mat((self.name, "H1_rows", k), rows_total, hid1)
+                ops.gather_rows(H1, inv, out=H1x, stream=e.stream)
+        iota = None
+        if fits and inv is None:
+            # H1 holds one row per sampled row: gs_maxpool_sparse_wgrad reads each hop's slice of it through 0 .. n s - 1
+            n_iota = max(nv.shape3[0] * nv.shape3[1] for nv in neighs)
+            iota = ops.pool2_iota(e.ws_i32((self.name, "iota", k), n_iota), n_iota, stream=e.stream)
+        r = hr = 0
+        for nv in neighs:
+            n, s, _ = nv.shape3
+            dp, am = dpm.rows_slice(r, r + n), argmax[r:r + n]
+            dH = dH1.rows_slice(hr, hr + n * s)
+            if fused:
+                # the pooled gradient back through W2 and the first relu to every neighbor row, dH2 never formed
+                if inv is not None:
+                    ops.pool2_dgrad(dp, am, H1, inv[hr:hr + n * s], n, s, dH, W2T=W2T, stream=e.stream)
+                else:
+                    ops.pool2_dgrad(dp, am, H1.rows_slice(hr, hr + n * s), None, n, s, dH, W2T=W2T, stream=e.stream)
+            else:
+                d2, hx = dH2.rows_slice(hr, hr + n * s), H1x.rows_slice(hr, hr + n * s)
+                ops.segment_max_bwd(dp, pooled.rows_slice(r, r + n), am, n, s, d2, stream=e.stream)
+                ops.dense_dgrad(d2, 0, hid2, n * s, W2.value, dH, stream=e.stream)
+                ops.act_bwd(dH, hx, n * s, hid1, ACT_RELU, dH, stream=e.stream)
+            if fits:
+                # dW2 from the arg-max rows of H1 alone (dH2 = [n*s, hid2] has one non-zero per (group, column))
+                if inv is not None:
+                    e.sparse_pool_wgrad(W2, H1, inv[hr:hr + n * s], n, s, am, dp)
+                else:
+                    e.sparse_pool_wgrad(W2, H1.rows_slice(hr, hr + n * s), iota[:n * s], n, s, am, dp)
+            else:
+                e.wgrad(W2, H1x.rows_slice(hr, hr + n * s), None, dH2.rows_slice(hr, hr + n * s), 0, n * s)
+            r += n
+            hr += n * s
+        e.bgrad(mlp1.vars['bias'], dH1, rows_total, hid1)
+        r = 0
+        for x in pieces:
+            e.wgrad(W1, x.src, x.ids, dH1.rows_slice(r, r + x.n), 0, x.n)
+            r += x.n
+        if embed_sink is not None:
+            var, c = embed_sink                    # see MeanAggregator.backward_hops; every neighbor row has its own dH1
+            d_self_e = e.ws_mat((self.name, "d_self_e", k), n_total, c)
+            ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value.rows_slice(0, c), d_self_e, stream=e.stream)
+            e.scatter_grad(var, d_self_e, self_all.ids, n_total, 1, 1.0)
+            d_neigh_e = e.ws_mat((self.name, "d_neigh_e", k), rows_total, c)
+            ops.dense_dgrad(dH1, 0, hid1, rows_total, W1.value.rows_slice(0, c), d_neigh_e, stream=e.stream)
+            hr = 0
+            for nv in neighs:
+                n, s, _ = nv.shape3
+                e.scatter_grad(var, d_neigh_e.rows_slice(hr, hr + n * s), nv.ids, n * s, 1, 1.0)
+                hr += n * s
+        if d_prev is None:
+            return
+        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
+        ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value, d_self_all, stream=e.stream)
+        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
+        ops.dense_dgrad(dH1, 0, hid1, rows_total, W1.value, d_neigh, stream=e.stream)
+        segs, hr = [], 0
+        for h, nv in enumerate(neighs):         # every neighbor row has its own gradient row (s = 1)
+            n, s, _ = nv.shape3
+            segs.append((d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0))
+            hr += n * s
+        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
+                            mask_y=prev_mask, stream=e.stream)
+
+    def infer_full(self, graph, H):
+        """_PoolingAggregator.infer_full with both Dense layers run once per NODE, then the hid2-wide table is max-reduced over
+        every node's whole neighbor list, then the SAGE matmuls."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in = self.output_dim, H.d
+        mlp1, mlp2 = self.mlp_layers
+        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
+        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
+        Hh2 = inf._table(e, graph.n_rows, hid2)
+        Hh1 = e.ws_mat((self.name, "full_h1"), min(inf.WINDOW_ROWS, graph.n_rows), hid1)
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            ops.gemm(False, False, n, hid1, d_in, H.rows_slice(r0, r0 + n), mlp1.vars['weights'].value, Hh1.rows_slice(0, n),
+                     bias=mlp1.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
+            ops.gemm(False, False, n, hid2, hid1, Hh1.rows_slice(0, n), mlp2.vars['weights'].value, Hh2.rows_slice(r0, r0 + n),
+                     bias=mlp2.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
+        pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid2)
+        b = self.vars['bias'].value.buf if self.bias else None
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            graph.reduce(e, inf.CSR_MAX, Hh2, pooled, r0, n)
+            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, pooled, None, n, self.vars['self_weights'].value,
+                               self.vars['neigh_weights'].value, o, self.concat, self.act_code, b, out.rows_slice(r0, r0 + n),
+                               stream=e.stream)
+        e.sync()
+        return out

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .aggregators import GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator, SeqAggregator
+from .aggregators import (GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator, SeqAggregator,
+                          TwoMaxLayerPoolingAggregator)
 from .engine import get_engine
 from .inits import glorot
 from .layers import Rows, identity
@@ -38,6 +39,7 @@ _AGGREGATORS = {
     "meanpool": MeanPoolingAggregator,
     "gcn": GCNAggregator,
     "seq": SeqAggregator,
+    "twomaxpool": TwoMaxLayerPoolingAggregator,
 }
 
 

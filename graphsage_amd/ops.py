@@ -489,6 +489,39 @@ def maxpool_sparse_wgrad(X, ids, n, s, argmax, dpm, hidden, n_slabs, slabs_ptr, 
          hidden, n_slabs, slabs_ptr, ld_slab, _s(stream))
 
 
+def pool2_transpose(W, out, stream=None):
+    """gs_pool2_transpose: out [W.d, W.rows] = W^T."""
+    call("gs_pool2_transpose", W.ptr, W.ld, W.rows, W.d, out.ptr, out.ld, _s(stream))
+    return out
+
+
+def pool2_iota(out, n, stream=None):
+    """gs_pool2_iota: out[i] = i for i < n (int32 device tensor)."""
+    call("gs_pool2_iota", ptr(out), n, _s(stream))
+    return out
+
+
+def pool2_dgrad_supported(s, hid1, hid2):
+    """The range of gs_pool2_dgrad (GS_ENOTSUP outside it: compose segment_max_bwd + dense_dgrad + act_bwd)."""
+    return 1 <= s <= 64 and hid1 >= 4 and hid2 >= 4 and hid1 % 4 == 0 and hid2 % 4 == 0 and hid2 <= 1024
+
+
+def pool2_dgrad(dpm, argmax, H1, h_idx, n, s, dH1, W2=None, W2T=None, stream=None):
+    """gs_pool2_dgrad: dH1 [n*s, hid1] of the two-layer max-pool from dpm [n, hid2] and the arg-max, through W2 [hid1, hid2] and
+    the relu mask of H1 (rows through h_idx when given).  With W2T (= W2^T, pool2_transpose) the kernel is launched directly
+    (gs_pool2_dgrad_t); with W2 the library makes the copy for the call.  A shape outside pool2_dgrad_supported raises."""
+    hid1, hid2 = H1.d, dpm.d
+    if (W2 is None) == (W2T is None):
+        raise _lib.GraphsageAmdError("pool2_dgrad: give W2 or W2T (one of them)")
+    if W2T is not None:
+        call("gs_pool2_dgrad_t", dpm.ptr, dpm.ld, ptr(argmax), argmax.stride(0), W2T.ptr, W2T.ld, H1.ptr, H1.ld, ptr(h_idx), n, s,
+             hid1, hid2, dH1.ptr, dH1.ld, _s(stream))
+    else:
+        call("gs_pool2_dgrad", dpm.ptr, dpm.ld, ptr(argmax), argmax.stride(0), W2.ptr, W2.ld, H1.ptr, H1.ld, ptr(h_idx), n, s,
+             hid1, hid2, dH1.ptr, dH1.ld, _s(stream))
+    return dH1
+
+
 def scatter_add_rows(d, n, s, cols, scale, ids, table, stream=None):
     """table[ids[i*s + j], :cols] += scale * d[i, :cols]  (gradient of a row gather w.r.t. the gathered table)."""
     call("gs_scatter_add_rows", d.ptr, d.ld, n, s, cols, scale, ptr(ids), table.ptr, table.ld, _s(stream))

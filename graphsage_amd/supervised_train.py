@@ -79,6 +79,14 @@ def refuse_full_inference(flags):
             "an LSTM over a random permutation of a neighbor sample has no full-neighborhood form"))
 
 
+def refuse_dropout(flags):
+    """The two-layer max-pooling aggregator runs without dropout (its second Dense has no mask site): say so before any work."""
+    if flags.model == 'graphsage_twomaxpool' and getattr(flags, "dropout", 0.0) > 0:
+        from ._lib import GraphsageAmdError
+        raise GraphsageAmdError("--dropout > 0 is not supported with --model graphsage_twomaxpool (the reference drops the "
+                                "input of both Dense layers of the aggregator; only --dropout 0 is implemented)")
+
+
 def full_graph(minibatch, n_nodes):
     """The test graph for full-neighborhood inference: the padded test table verbatim under --sampler padded, else the CSR."""
     from .inference import FullGraph
@@ -247,7 +255,7 @@ def train(G):
                        SAGEInfo("node", sampler, FLAGS.samples_2, 2 * FLAGS.dim_2)]
         model = SupervisedGraphsage(num_classes, placeholders, features, adj_info, minibatch.deg,
                                     layer_infos=layer_infos, aggregator_type="gcn", concat=False, **kw)
-    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_seq'):   # :190-236
+    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_seq', 'graphsage_twomaxpool'):   # :190-236
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
         model = SupervisedGraphsage(num_classes, placeholders, features, adj_info, minibatch.deg,
@@ -376,6 +384,7 @@ def main(argv=None):
     global FLAGS
     FLAGS = build_flags(argv)
     refuse_full_inference(FLAGS)
+    refuse_dropout(FLAGS)
     print("Loading training data..")
     G = load_graph()
     print("Done loading training data..")

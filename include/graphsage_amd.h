@@ -38,6 +38,7 @@ extern "C" {
 #define GS_ACT_IDENTITY 0
 #define GS_ACT_RELU 1
 
+/* bumped when a struct layout or an existing signature changes; added entry points alone (gs_pool2_*) leave it as it is */
 #define GS_ABI_VERSION 12
 
 const char* gs_last_error(void);
@@ -380,6 +381,29 @@ int gs_segment_max_bwd(const float* d_pooled, int64_t ldd, const float* pooled, 
 int gs_maxpool_sparse_wgrad(const float* X, int64_t ldx, const int32_t* ids, int64_t n_groups, int32_t s, int32_t d,
                             const int32_t* argmax, int64_t lda, const float* d_pooled_masked, int64_t ldd,
                             int32_t hidden, int32_t n_slabs, float* slabs, int64_t ld_slab, void* stream);
+
+/* Two-layer max-pool (TwoMaxLayerPoolingAggregator, aggregators.py:276-361): the gradient of the FIRST dense layer's
+ * activations H1 from the gradient of the pooled SECOND layer, back through W2 and the first relu:
+ *   dH1[i*s + j, k] = H1[h(i*s + j), k] > 0 ?  sum over { c : argmax[i, c] == j } of d_pooled_masked[i, c] * W2[k, c]  :  0
+ * with d_pooled_masked = d_pooled2 * (pooled2 > 0) [n, hid2] (e.g. from gs_act_bwd), argmax [n, hid2] in [0, s) (a value
+ * outside collects nowhere), W2 [hid1, hid2] as the Dense stores it, h(r) = h_idx[r], or r when h_idx is NULL (h_idx: the
+ * `inv` of gs_unique_ids, H1 then holds one row per distinct node).  The sum runs in ascending c (columns whose
+ * d_pooled_masked is exactly 0 are skipped), so two launches give the same bits; every row of dH1 [n*s, hid1] is written, a
+ * row that won no column as zeros.  Equals gs_segment_max_bwd + gs_dense_dgrad + gs_act_bwd without the [n*s, hid2] matrix
+ * and with 1/s of the flops.  Needs 1 <= s <= 64, hid1 % 4 == 0, hid2 % 4 == 0, hid2 <= 1024; GS_ENOTSUP otherwise.
+ *   gs_pool2_transpose  out [cols, rows] = W [rows, cols]^T
+ *   gs_pool2_iota       out[i] = i for i < n (the row index gs_maxpool_sparse_wgrad wants over an H1 with one row per sample)
+ *   gs_pool2_dgrad_t    the kernel itself: reads W2T = W2^T [hid2, hid1] (rows coalesced along k)
+ *   gs_pool2_dgrad      takes W2: makes the transposed copy for the call (allocates, transposes, launches, waits, frees);
+ *                       not capturable into a graph -- a training step keeps W2T in a workspace and calls gs_pool2_dgrad_t */
+int gs_pool2_transpose(const float* W, int64_t ldw, int32_t rows, int32_t cols, float* out, int64_t ldo, void* stream);
+int gs_pool2_iota(int32_t* out, int64_t n, void* stream);
+int gs_pool2_dgrad_t(const float* d_pooled_masked, int64_t ldd, const int32_t* argmax, int64_t lda, const float* W2T,
+                     int64_t ldt, const float* H1, int64_t ldh, const int32_t* h_idx, int64_t n, int32_t s, int32_t hid1,
+                     int32_t hid2, float* dH1, int64_t ldo, void* stream);
+int gs_pool2_dgrad(const float* d_pooled_masked, int64_t ldd, const int32_t* argmax, int64_t lda, const float* W2, int64_t ldw,
+                   const float* H1, int64_t ldh, const int32_t* h_idx, int64_t n, int32_t s, int32_t hid1, int32_t hid2,
+                   float* dH1, int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K5  supervised head         replaces supervised_models.py:85 (l2_normalize), :111-118 (losses),
