@@ -13,11 +13,20 @@ MI355X-first addition: the reference calls the SAME aggregator once per hop of a
 hops are contiguous), and `backward_hops` is its hand-written reverse.  `_call` is `call_hops` with one hop.
 """
 import os
+from collections import namedtuple
+
+import torch
 
 from . import ops
 from .inits import glorot, zeros
 from .layers import SITE_MLP, SITE_NEIGH, SITE_SELF, Dense, Layer, Rows, _act_code, _rate, relu
-from .ops import ACT_IDENTITY, ACT_RELU
+from .ops import ACT_IDENTITY, ACT_RELU, Mat
+
+# What one call_hops leaves for its backward_hops, one record type per aggregator family.
+_MeanSaved = namedtuple("_MeanSaved", "self_all neighs means out rate self_in h0", defaults=(None, None))   # Mean and GCN
+_PoolSaved = namedtuple("_PoolSaved", "self_all neighs pieces rows_total H pooled argmax out rate")
+_Pool2Saved = namedtuple("_Pool2Saved", "self_all neighs pieces rows_total H1 inv pooled argmax out")
+_SeqSaved = namedtuple("_SeqSaved", "self_all neighs pieces rows_total segs lengths gates C Hp h_last out")
 
 
 def _scope(self_name, name):
@@ -25,7 +34,7 @@ def _scope(self_name, name):
     return self_name + ('/' + name if name is not None else '') + '_vars'
 
 
-def _contiguous(rows_list):
+def contiguous_rows(rows_list):
     """If the Rows views are adjacent slices of one buffer, return the single Rows covering all of them."""
     first = rows_list[0]
     total = first.n
@@ -43,13 +52,29 @@ def _contiguous(rows_list):
     if len(rows_list) == 1:
         return Rows(first.src, first.ids, first.n, first.requires_grad)
     if first.ids is not None:
-        import torch
         ids = torch.as_strided(first.ids, (total,), (1,))
         return Rows(first.src, ids, total, first.requires_grad)
-    import torch
-    from .ops import Mat
     buf = torch.as_strided(first.src.buf, (total, first.src.buf.shape[1]), first.src.buf.stride())
     return Rows(Mat(buf, first.src.d), None, total, first.requires_grad)
+
+
+def _hops(neighs):
+    """(h, nv, n, s, r, hr) per hop: r is the offset of the hop's n group rows among all hops', hr that of its n * s
+    sampled rows."""
+    r = hr = 0
+    for h, nv in enumerate(neighs):
+        n, s, _ = nv.shape3
+        yield h, nv, n, s, r, hr
+        r += n
+        hr += n * s
+
+
+def _flatten(neighs):
+    """Every hop's neighbors as [n * s, d] rows: (flat, x_all, pieces, rows_total).  x_all is the one view over all hops when
+    they are adjacent (else None); pieces is what a contraction over every neighbor row runs on, [x_all] or flat."""
+    flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
+    x_all = contiguous_rows(flat)
+    return flat, x_all, ([x_all] if x_all is not None else flat), sum(x.n for x in flat)
 
 
 def _run_jobs(e, jobs):
@@ -59,8 +84,50 @@ def _run_jobs(e, jobs):
                  e.stream)
 
 
+def _pieces_fwd(e, pieces, W, bias, width, act, out):
+    """out = act(X . W + bias) over every neighbor row, one contraction per contiguous piece of the rows (_flatten)."""
+    r = 0
+    for x in pieces:
+        ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, W, width, False, act, bias, out.rows_slice(r, r + x.n),
+                           stream=e.stream)
+        r += x.n
+
+
+def _pieces_wgrad(e, var, pieces, d_rows):
+    """Queue the weight gradient of _pieces_fwd's W from d_rows, one operand per piece."""
+    r = 0
+    for x in pieces:
+        e.wgrad(var, x.src, x.ids, d_rows.rows_slice(r, r + x.n), 0, x.n)
+        r += x.n
+
+
 class _SageBase(Layer):
-    """Shared plumbing: saved-activation stack, activation backward, masked scatter of input gradients."""
+    """Shared plumbing: construction, saved-activation stack, the SAGE output layer and its backward, masked scatter of
+    input gradients."""
+
+    # Switches (set on an instance by models, tests and A/B scripts) and records of what the last call took (read by tests and
+    # bench.py) are class attributes of the class whose code reads or writes them, each declared once with its default.
+
+    def _init_sage(self, input_dim, output_dim, neigh_input_dim, dropout, bias, act, concat, name, neigh_rows, bias_cols,
+                   self_weights=True):
+        """The attributes every aggregator has and the SAGE variables, in the reference's creation order: neighbor weights
+        [neigh_rows, output_dim], self weights [input_dim, output_dim] (GCN has none), bias [bias_cols]."""
+        self.dropout = dropout
+        self.bias = bias
+        self.act = act
+        self.act_code = _act_code(act)
+        self.concat = concat
+        self.input_dim = input_dim
+        self.output_dim = output_dim
+        self.neigh_input_dim = neigh_input_dim
+        scope = _scope(self.name, name)
+        e = self.engine
+        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((neigh_rows, output_dim)), decay=True)
+        if self_weights:
+            self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
+        if self.bias:
+            self.vars['bias'] = e.add_variable(scope + '/bias', zeros((bias_cols,)), decay=True)
+        self._saved = []
 
     def _push(self, rec):
         self._saved.append(rec)
@@ -75,6 +142,26 @@ class _SageBase(Layer):
 
     def reset(self):
         del self._saved[:]
+
+    def prefetch(self, self_all, neighs, tag=0):
+        return None   # the neighborhood vector needs the weights (pooling MLP, recurrence): nothing can run ahead
+
+    def prefetch_jobs(self, self_all, neighs, tag=0):
+        return None, []
+
+    def _mean_jobs(self, self_all, neighs, tag, self_term):
+        """prefetch() of the mean aggregators, but only DESCRIBED: the gather+mean launches (one per hop) as jobs that can be
+        issued inside another kernel's launch (horizontal fusion).  self_term: the GCN mean over {neighbors} U {self}.
+        Returns (means, jobs)."""
+        self._no_dropout_here("the prefetch pipeline")
+        e = self.engine
+        means = e.ws_mat((self.name, "mean", len(self._saved), tag), self_all.n, neighs[0].shape3[2], ld_multiple=32)
+        jobs = []
+        for h, nv, n, s, r, hr in _hops(neighs):
+            sv = self_all.slice(r, r + n) if self_term else None
+            jobs.append(ops.gather_job(nv.src, nv.ids, n, s, means.rows_slice(r, r + n),
+                                       self_src=sv.src if self_term else None, self_idx=sv.ids if self_term else None))
+        return means, jobs
 
     # ---- dropout (tf.nn.dropout on the aggregator inputs, aggregators.py:46-47,104-105; layers.py:107) ----
     def _drop(self, rate, role, k, row0=0):
@@ -119,7 +206,7 @@ class _SageBase(Layer):
     def backward(self, d_out, pre_masked=False):
         """Single-hop reverse of `_call`: returns raw (d_self [n, d], d_neigh [n*s, d]) when the inputs
         require gradients, else (None, None)."""
-        self_all, neighs = self._saved[-1][0], self._saved[-1][1]
+        self_all, neighs = self._saved[-1].self_all, self._saved[-1].neighs
         need = self_all.requires_grad or neighs[0].requires_grad
         if not need:
             self.backward_hops(d_out, pre_masked)
@@ -135,57 +222,6 @@ class _SageBase(Layer):
         act = ACT_RELU if prev_mask is not None else ACT_IDENTITY
         ops.act_bwd(d_self_all, prev_mask.rows_slice(0, n_total) if prev_mask is not None else None, n_total,
                     d_self_all.d, act, d_prev.rows_slice(0, n_total), stream=e.stream)
-
-    def _dedup_wanted(self, x_all, rows_total):
-        """Run the pooling MLP once per DISTINCT sampled id of the step?  (_PoolingAggregator.call_hops)"""
-        dedup_min = getattr(self, "dedup_min_rows", None)
-        if dedup_min is None:
-            dedup_min = int(os.environ.get("GS_POOL_DEDUP_MIN_ROWS", "2048"))
-        return (x_all is not None and x_all.ids is not None and rows_total > dedup_min
-                and x_all.src.rows < (1 << 31)
-                and x_all.src.rows <= int(os.environ.get("GS_POOL_DEDUP_MAX_RATIO", "16")) * rows_total
-                and getattr(self, "dedup_pool", True))
-
-    def _mlp_distinct(self, mlp, hidden, x_all, rows_total, k):
-        """relu(X[uniq] . W + b) over the step's distinct ids: (H [rows_total, hidden] with the device count's leading rows
-        filled, inv [rows_total], count).  Records the kernel taken in last_pool_kernel."""
-        e = self.engine
-        X, ids, nv_rows = x_all.src, x_all.ids, x_all.src.rows
-        rank_ws = e.ws_i32((self.name, "dd_rank", k), 2 * nv_rows)       # [flags | ranks]: zero-initialised, self-cleaning
-        sums_ws = e.ws_i32((self.name, "dd_sums", k), 256)
-        uniq = e.ws_i32((self.name, "dd_uniq", k), rows_total)
-        inv = e.ws_i32((self.name, "dd_inv", k), rows_total)
-        cnt = e.ws_i32((self.name, "dd_count", k), 1)
-        ops.call("gs_unique_ids", ops.ptr(ids), rows_total, nv_rows, ops.ptr(rank_ws), ops.ptr(sums_ws), ops.ptr(uniq),
-                 ops.ptr(inv), ops.ptr(cnt), e.stream)
-        Hu = e.ws_mat((self.name, "H_unique", k), rows_total, hidden)
-        W, bmlp = mlp.vars['weights'].value, mlp.vars['bias'].value.buf
-        self.last_pool_kernel = None
-        if (e.split_pool and e.pool_f16 and not x_all.requires_grad and e.is_constant_table(X) and e.table16_fits(X)):
-            # ... on the fp16 matrix pipe, operands as two fp16 pieces each (fp32 accuracy class, half the matrix-pipe work of
-            # the three-piece form below, which is bound by the chip's POWER cap): the constant feature table is cut once.
-            # A table with trainable leading columns (identity features, rewritten behind every optimizer launch) is NOT
-            # constant -- its cut-once copy would be stale from the second step on -- and takes the three-piece kernel below,
-            # which cuts the rows it reads in registers.
-            self.last_pool_kernel = "split16"
-            X2, rexp = e.table16_of(X)
-            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
-            ops.call("gs_dense_fwd_rows_split16", ops.ptr(X2), ops.ptr(rexp), ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
-                     ops.ptr(e.split_of(mlp.vars['weights'], form="f16x2")), hidden, ACT_RELU, ops.ptr(bmlp),
-                     Hu.ptr, Hu.ld, ops.ptr(ws), 4 * ws.numel(), e.stream)
-        elif e.split_pool:
-            # the 51 GF of the pooling MLP on the bf16 matrix pipe, operands as three bf16 pieces (fp32 accuracy)
-            # (+ a workspace: the last, nearly empty round of its one-per-CU workgroups is cut along K, gs_split.hip)
-            self.last_pool_kernel = "split_bf16x3"
-            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
-            ops.call("gs_dense_fwd_rows_split_ws", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
-                     ops.ptr(e.split_of(mlp.vars['weights'])), hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld,
-                     ops.ptr(ws), 4 * ws.numel(), e.stream)
-        else:
-            self.last_pool_kernel = "fp32_mfma"
-            ops.call("gs_dense_fwd_rows_dev", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt), W.ptr, W.ld,
-                     hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld, e.stream)
-        return Hu, inv, cnt
 
     def _sage_out(self, self_all, pooled, n_total, k):
         """from_self / from_neighs matmuls + concat|add + bias + act over the pooled neighborhood vectors (all hops, one launch)."""
@@ -205,30 +241,83 @@ class _SageBase(Layer):
                                stream=e.stream)
         return out
 
+    def _sage_bwd(self, d_out, out, n_total, pre_masked, self_src, self_ids, neigh_vecs):
+        """Reverse of the SAGE output layer up to its weights: dz = act'(out) * d_out, then the self-weight, neighbor-weight and
+        bias gradients QUEUED in that order (the slab order inside the grouped weight-gradient launch follows it).  The self
+        operand is rows `self_ids` of `self_src`, the neighbor operand the dense `neigh_vecs`.  Returns (dz, col_n), col_n the
+        first column of dz that belongs to the neighbor term."""
+        e = self.engine
+        o = self.output_dim
+        n_out = o * (2 if self.concat else 1)
+        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
+        col_n = o if self.concat else 0
+        e.wgrad(self.vars['self_weights'], self_src, self_ids, dz, 0, n_total)
+        e.wgrad(self.vars['neigh_weights'], neigh_vecs, None, dz, col_n, n_total)
+        if self.bias:
+            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        return dz, col_n
+
+    def _row_input_grads(self, saved, k, dz, d_rows, width, W1, embed_sink, d_prev, prev_mask, prev_offsets, drop=None):
+        """Input gradients of an aggregator whose every neighbor row went through a first layer `W1` [neigh_in, width] of its
+        own, so that each has its own gradient row in d_rows [rows_total, width]; the self rows only through W_self.  `drop`
+        makes the dropout descriptor of those neighbor rows (None: they were not dropped; these aggregators never drop self).
+        With embed_sink the leading columns go to the identity-feature table; with d_prev everything, in ONE pull launch."""
+        e = self.engine
+        self_all, neighs, rows_total = saved.self_all, saved.neighs, saved.rows_total
+        n_total, o = self_all.n, self.output_dim
+        W_self = self.vars['self_weights'].value
+        if embed_sink is not None:
+            var, c = embed_sink                    # see MeanAggregator.backward_hops
+            d_self_e = e.ws_mat((self.name, "d_self_e", k), n_total, c)
+            ops.dense_dgrad(dz, 0, o, n_total, W_self.rows_slice(0, c), d_self_e, stream=e.stream)
+            e.scatter_grad(var, d_self_e, self_all.ids, n_total, 1, 1.0)
+            d_neigh_e = e.ws_mat((self.name, "d_neigh_e", k), rows_total, c)
+            ops.dense_dgrad(d_rows, 0, width, rows_total, W1.rows_slice(0, c), d_neigh_e, stream=e.stream)
+            if drop is not None:
+                ops.dropout_rows(d_neigh_e, None, rows_total, drop(), d_neigh_e, stream=e.stream)
+            for h, nv, n, s, r, hr in _hops(neighs):
+                e.scatter_grad(var, d_neigh_e.rows_slice(hr, hr + n * s), nv.ids, n * s, 1, 1.0)
+        if d_prev is None:
+            return
+        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
+        ops.dense_dgrad(dz, 0, o, n_total, W_self, d_self_all, stream=e.stream)
+        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
+        ops.dense_dgrad(d_rows, 0, width, rows_total, W1, d_neigh, stream=e.stream)
+        if drop is not None:
+            ops.dropout_rows(d_neigh, None, rows_total, drop(), d_neigh, stream=e.stream)
+        # every neighbor row has its own gradient row (s = 1)
+        segs = [(d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0) for h, nv, n, s, r, hr in _hops(neighs)]
+        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
+                            mask_y=prev_mask, stream=e.stream)
+
+    def _infer_reduce_sage(self, graph, csr_op, table, reduced, H, out):
+        """Tail of infer_full, per window of rows: `table` reduced over every row's whole neighbor list into `reduced`, then the
+        SAGE matmuls over [H rows | reduced].  Returns `out` once the stream has drained."""
+        from . import inference as inf
+        e = self.engine
+        b = self.vars['bias'].value.buf if self.bias else None
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            graph.reduce(e, csr_op, table, reduced, r0, n)
+            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, reduced, None, n, self.vars['self_weights'].value,
+                               self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b,
+                               out.rows_slice(r0, r0 + n), stream=e.stream)
+        e.sync()
+        return out
+
 
 class MeanAggregator(_SageBase):
     """Aggregates via mean followed by matmul and non-linearity (aggregators.py:6-64)."""
+    layer1_z = True            # switch: the last layer as ONE gs_sage_tail_z launch where _last_layer_z allows it
+    wgrad_ids = None           # the step's private copy of the self ids for the next weight gradient (set by the model)
+    last_fused_launch = None   # record: (re-issuable launch, description) of the last horizontally fused forward
 
     def __init__(self, input_dim, output_dim, neigh_input_dim=None, dropout=0., bias=False, act=relu,
                  name=None, concat=False, **kwargs):
         super(MeanAggregator, self).__init__(**kwargs)
-        self.dropout = dropout
-        self.bias = bias
-        self.act = act
-        self.act_code = _act_code(act)
-        self.concat = concat
         if neigh_input_dim is None:
             neigh_input_dim = input_dim
-        scope = _scope(self.name, name)
-        e = self.engine
-        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((neigh_input_dim, output_dim)), decay=True)
-        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
-        if self.bias:
-            self.vars['bias'] = e.add_variable(scope + '/bias', zeros(((2 if concat else 1) * output_dim,)), decay=True)
-        self.input_dim = input_dim
-        self.output_dim = output_dim
-        self.neigh_input_dim = neigh_input_dim
-        self._saved = []
+        self._init_sage(input_dim, output_dim, neigh_input_dim, dropout, bias, act, concat, name,
+                        neigh_rows=neigh_input_dim, bias_cols=(2 if concat else 1) * output_dim)
 
     def prefetch(self, self_all, neighs, tag=0):
         """The weight-free half of the call: reduce_mean(neigh_vecs, axis=1) (aggregators.py:48) fused with the row
@@ -239,45 +328,28 @@ class MeanAggregator(_SageBase):
         k = len(self._saved)
         rate = _rate(self.dropout)
         means = e.ws_mat((self.name, "mean", k, tag), n_total, d, ld_multiple=32)      # whole 128-byte lines per row
-        r = row0 = 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             ops.gather_mean_fwd(nv.src, nv.ids, n, s, out=means.rows_slice(r, r + n),
-                                drop=self._drop(rate, SITE_NEIGH, k, row0), stream=e.stream)   # dropout(neigh_vecs) (:46)
-            r += n
-            row0 += n * s
-        assert r == n_total
+                                drop=self._drop(rate, SITE_NEIGH, k, hr), stream=e.stream)     # dropout(neigh_vecs) (:46)
+        assert sum(nv.shape3[0] for nv in neighs) == n_total
         return means
 
     def prefetch_jobs(self, self_all, neighs, tag=0):
-        """Like prefetch(), but only DESCRIBES the gather+mean launches (one per hop) so that they can be issued
-        inside another kernel's launch (horizontal fusion).  Returns (means, jobs)."""
-        self._no_dropout_here("the prefetch pipeline")
-        e = self.engine
-        n_total = self_all.n
-        d = neighs[0].shape3[2]
-        means = e.ws_mat((self.name, "mean", len(self._saved), tag), n_total, d, ld_multiple=32)
-        jobs, r = [], 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
-            jobs.append(ops.gather_job(nv.src, nv.ids, n, s, means.rows_slice(r, r + n)))
-            r += n
-        return means, jobs
+        return self._mean_jobs(self_all, neighs, tag, self_term=False)
 
     def _last_layer_z(self, self_all, neighs, rate, means):
         """Can this call be ONE gs_sage_tail_z launch?  A last layer (identity act, concat, no bias, no dropout) over ONE hop
         whose inputs are the dense rows [self (n) | neighbors (n s)] of one buffer -- the layer-1 call of every two-layer
         mean model (models.py:321-328).  Returns that buffer as a Mat, or None."""
         if (means is not None or rate > 0 or len(neighs) != 1 or not self.concat or self.bias or self.act_code != ACT_IDENTITY
-                or self_all.ids is not None or neighs[0].ids is not None or not getattr(self, "layer1_z", True)):
+                or self_all.ids is not None or neighs[0].ids is not None or not self.layer1_z):
             return None
         n, s, d = neighs[0].shape3
         a, b = self_all.src, neighs[0].src
         if (n != self_all.n or s > 11 or a.ld != b.ld or a.d != d or b.d != d or (n + n * s) * a.ld >= (1 << 31)
                 or b.buf.data_ptr() != a.buf.data_ptr() + 4 * n * a.ld or not ops.sage_tail_supported(d, self.output_dim, 1)):
             return None
-        import torch
-        return ops.Mat(torch.as_strided(a.buf, (n + n * s, a.buf.shape[1]), a.buf.stride()), d)
+        return Mat(torch.as_strided(a.buf, (n + n * s, a.buf.shape[1]), a.buf.stride()), d)
 
     def call_hops(self, self_all, neighs, means=None, side_jobs=None):
         e = self.engine
@@ -293,7 +365,7 @@ class MeanAggregator(_SageBase):
             out = e.ws_mat((self.name, "out", k), n_total, 2 * self.output_dim)
             ops.sage_tail_z(h0, n_total, s, self.vars['self_weights'].value, self.vars['neigh_weights'].value, self.output_dim,
                             means, out, jobs=side_jobs, stream=e.stream)
-            self._push((self_all, neighs, means, out, rate, self_all, h0))
+            self._push(_MeanSaved(self_all, neighs, means, out, rate, self_all, h0))
             return out
         if means is None:
             means = self.prefetch(self_all, neighs)
@@ -342,7 +414,7 @@ class MeanAggregator(_SageBase):
             ops.sage_dense_fwd(self_in.src, self_in.ids, means, None, n_total, self.vars['self_weights'].value,
                                self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b, out,
                                stream=e.stream)
-        self._push((self_all, neighs, means, out, rate, self_in, None))
+        self._push(_MeanSaved(self_all, neighs, means, out, rate, self_in, None))
         return out
 
     def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
@@ -351,18 +423,12 @@ class MeanAggregator(_SageBase):
         n_total = self_all.n
         k = len(self._saved)
         o = self.output_dim
-        n_out = o * (2 if self.concat else 1)
-        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
-        col_n = o if self.concat else 0
         # (wgrad_ids: the step's private copy of these ids, made by the fused tail launch when a later step's sampler rides in
         #  the weight-gradient launch and refills the id buffer meanwhile -- SupervisedGraphsage._forward)
-        wg_ids = getattr(self, "wgrad_ids", None)
+        wg_ids = self.wgrad_ids
         self.wgrad_ids = None
-        e.wgrad(self.vars['self_weights'], self_in.src, wg_ids if (wg_ids is not None and self_in.ids is not None) else self_in.ids,
-                dz, 0, n_total)
-        e.wgrad(self.vars['neigh_weights'], means, None, dz, col_n, n_total)
-        if self.bias:
-            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        dz, col_n = self._sage_bwd(d_out, out, n_total, pre_masked, self_in.src,
+                                   wg_ids if (wg_ids is not None and self_in.ids is not None) else self_in.ids, means)
         if embed_sink is not None:
             # layer 0 over a table whose leading c columns are trainable (identity features): only those columns of
             # the input gradients are formed ([n, c] = dz . W[:c]^T) and scattered per sampled id, 1/s per neighbor
@@ -373,12 +439,8 @@ class MeanAggregator(_SageBase):
             ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value.rows_slice(0, c), d_means_e,
                             stream=e.stream)
             self._sink(var, d_self_e, self_all.ids, n_total, 1, 1.0, rate, SITE_SELF, k, 0, "s")
-            r = row0 = 0
-            for h, nv in enumerate(neighs):
-                n, s, _ = nv.shape3
-                self._sink(var, d_means_e.rows_slice(r, r + n), nv.ids, n, s, 1.0 / s, rate, SITE_NEIGH, k, row0, ("n", h))
-                r += n
-                row0 += n * s
+            for h, nv, n, s, r, hr in _hops(neighs):
+                self._sink(var, d_means_e.rows_slice(r, r + n), nv.ids, n, s, 1.0 / s, rate, SITE_NEIGH, k, hr, ("n", h))
         if d_prev is None:
             return
         d_in = self.input_dim
@@ -402,26 +464,18 @@ class MeanAggregator(_SageBase):
             ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, d_means_all, stream=e.stream)
         if rate == 0:
             # ONE launch: d_prev = relu'(prev) * (d_self on the self rows + d_means / s broadcast over each hop's samples)
-            segs, r = [], 0
-            for h, nv in enumerate(neighs):
-                n, s, _ = nv.shape3
-                segs.append((d_means_all.rows_slice(r, r + n), prev_offsets[h + 1], n, s, 1.0 / s))
-                r += n
+            segs = [(d_means_all.rows_slice(r, r + n), prev_offsets[h + 1], n, s, 1.0 / s) for h, nv, n, s, r, hr in _hops(neighs)]
             ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
                                 mask_y=prev_mask, stream=e.stream)
             return
         ops.dropout_rows(d_self_all, None, n_total, self._drop(rate, SITE_SELF, k), d_self_all, stream=e.stream)
         self._scatter_self(d_self_all, n_total, d_prev, prev_mask)
-        r = row0 = 0
-        for h, nv in enumerate(neighs):
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             r0 = prev_offsets[h + 1]
             dst = d_prev.rows_slice(r0, r0 + n * s)
             mask = prev_mask.rows_slice(r0, r0 + n * s) if prev_mask is not None else None
-            self._bwd_dropped(d_means_all.rows_slice(r, r + n), n, s, 1.0 / s, rate, SITE_NEIGH, k, row0, dst, mask,
+            self._bwd_dropped(d_means_all.rows_slice(r, r + n), n, s, 1.0 / s, rate, SITE_NEIGH, k, hr, dst, mask,
                               (h + 1 < len(neighs)), ("n", h))
-            r += n
-            row0 += n * s
 
     def infer_full(self, graph, H):
         """The layer for EVERY row of `graph` (inference.FullGraph) from ALL its neighbors: H [N + 1, d_in] -> [N + 1, n_out],
@@ -431,23 +485,18 @@ class MeanAggregator(_SageBase):
         e = self.engine
         o, d_in = self.output_dim, H.d
         out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
-        W_self, W_neigh = self.vars['self_weights'].value, self.vars['neigh_weights'].value
-        b = self.vars['bias'].value.buf if self.bias else None
-        if self.concat and not self.bias and o % 4 == 0 and o < d_in:
-            P = inf._table(e, graph.n_rows, o)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_neigh, P.rows_slice(r0, r0 + n), stream=e.stream)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                rows = out.rows_slice(r0, r0 + n)
-                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_self, rows.cols_slice(0, o), act=self.act_code,
-                         stream=e.stream)
-                graph.reduce(e, inf.CSR_MEAN, P, rows.cols_slice(o, 2 * o), r0, n, act=self.act_code)
-        else:
+        if not (self.concat and not self.bias and o % 4 == 0 and o < d_in):
             means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                graph.reduce(e, inf.CSR_MEAN, H, means, r0, n)
-                ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, means, None, n, W_self, W_neigh, o, self.concat, self.act_code,
-                                   b, out.rows_slice(r0, r0 + n), stream=e.stream)
+            return self._infer_reduce_sage(graph, inf.CSR_MEAN, H, means, H, out)
+        W_self, W_neigh = self.vars['self_weights'].value, self.vars['neigh_weights'].value
+        P = inf._table(e, graph.n_rows, o)
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_neigh, P.rows_slice(r0, r0 + n), stream=e.stream)
+        for r0, n in graph.windows(inf.WINDOW_ROWS):
+            rows = out.rows_slice(r0, r0 + n)
+            ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_self, rows.cols_slice(0, o), act=self.act_code,
+                     stream=e.stream)
+            graph.reduce(e, inf.CSR_MEAN, P, rows.cols_slice(o, 2 * o), r0, n, act=self.act_code)
         e.sync()
         return out
 
@@ -459,34 +508,15 @@ class GCNAggregator(_SageBase):
     def __init__(self, input_dim, output_dim, neigh_input_dim=None, dropout=0., bias=False, act=relu, name=None,
                  concat=False, **kwargs):
         super(GCNAggregator, self).__init__(**kwargs)
-        self.dropout = dropout
-        self.bias = bias
-        self.act = act
-        self.act_code = _act_code(act)
-        self.concat = concat
         if neigh_input_dim is None:
             neigh_input_dim = input_dim
-        scope = _scope(self.name, name)
-        e = self.engine
-        self.vars['weights'] = e.add_variable(scope + '/neigh_weights', glorot((neigh_input_dim, output_dim)), decay=True)
-        if self.bias:
-            self.vars['bias'] = e.add_variable(scope + '/bias', zeros((output_dim,)), decay=True)
-        self.input_dim = input_dim
-        self.output_dim = output_dim
-        self._saved = []
+        self._init_sage(input_dim, output_dim, neigh_input_dim, dropout, bias, act, concat, name,
+                        neigh_rows=neigh_input_dim, bias_cols=output_dim, self_weights=False)
+        # ONE matrix, named as the reference names it (scope + '/neigh_weights') but held under the key 'weights'
+        self.vars = {('weights' if key == 'neigh_weights' else key): v for key, v in self.vars.items()}
 
     def prefetch_jobs(self, self_all, neighs, tag=0):
-        self._no_dropout_here("the prefetch pipeline")
-        e = self.engine
-        d = neighs[0].shape3[2]
-        means = e.ws_mat((self.name, "mean", len(self._saved), tag), self_all.n, d, ld_multiple=32)
-        jobs, r = [], 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
-            sv = self_all.slice(r, r + n)
-            jobs.append(ops.gather_job(nv.src, nv.ids, n, s, means.rows_slice(r, r + n), self_src=sv.src, self_idx=sv.ids))
-            r += n
-        return means, jobs
+        return self._mean_jobs(self_all, neighs, tag, self_term=True)
 
     def prefetch(self, self_all, neighs, tag=0):
         """mean over {neighbors} U {self}  (aggregators.py:106-107); weight-free, so it can run ahead of time."""
@@ -497,14 +527,10 @@ class GCNAggregator(_SageBase):
         rate = _rate(self.dropout)
         means = e.ws_mat((self.name, "mean", k, tag), n_total, d, ld_multiple=32)      # whole 128-byte lines per row
         self_in = self._drop_self(self_all, rate, k) if rate > 0 else self_all            # dropout(self_vecs) (:105)
-        r = row0 = 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             sv = self_in.slice(r, r + n)
             ops.gather_mean_fwd(nv.src, nv.ids, n, s, out=means.rows_slice(r, r + n), self_src=sv.src,
-                                self_idx=sv.ids, drop=self._drop(rate, SITE_NEIGH, k, row0), stream=e.stream)
-            r += n
-            row0 += n * s
+                                self_idx=sv.ids, drop=self._drop(rate, SITE_NEIGH, k, hr), stream=e.stream)
         return means
 
     def call_hops(self, self_all, neighs, means=None, side_jobs=None):
@@ -530,12 +556,12 @@ class GCNAggregator(_SageBase):
         else:
             ops.sage_dense_fwd(None, None, means, None, n_total, None, self.vars['weights'].value, self.output_dim, False,
                                self.act_code, b, out, stream=e.stream)
-        self._push((self_all, neighs, means, out, rate))
+        self._push(_MeanSaved(self_all, neighs, means, out, rate))
         return out
 
     def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
         e = self.engine
-        self_all, neighs, means, out, rate = self._saved.pop()
+        self_all, neighs, means, out, rate, _, _ = self._saved.pop()
         n_total = self_all.n
         k = len(self._saved)
         dz = self._dz(d_out, out, n_total, self.output_dim, pre_masked)
@@ -547,14 +573,10 @@ class GCNAggregator(_SageBase):
             d_means_e = e.ws_mat((self.name, "d_means_e", k), n_total, c)
             ops.dense_dgrad(dz, 0, self.output_dim, n_total, self.vars['weights'].value.rows_slice(0, c), d_means_e,
                             stream=e.stream)
-            r = row0 = 0
-            for h, nv in enumerate(neighs):
-                n, s, _ = nv.shape3
+            for h, nv, n, s, r, hr in _hops(neighs):
                 dm = d_means_e.rows_slice(r, r + n)
                 self._sink(var, dm, self_all.slice(r, r + n).ids, n, 1, 1.0 / (s + 1), rate, SITE_SELF, k, r, ("s", h))
-                self._sink(var, dm, nv.ids, n, s, 1.0 / (s + 1), rate, SITE_NEIGH, k, row0, ("n", h))
-                r += n
-                row0 += n * s
+                self._sink(var, dm, nv.ids, n, s, 1.0 / (s + 1), rate, SITE_NEIGH, k, hr, ("n", h))
         if d_prev is None:
             return
         d = means.d
@@ -562,32 +584,23 @@ class GCNAggregator(_SageBase):
         ops.dense_dgrad(dz, 0, self.output_dim, n_total, self.vars['weights'].value, d_means, stream=e.stream)
         if rate == 0:
             # ONE launch; the self term of hop h is one more "neighbor" of weight 1/(s+1)
-            segs, r = [], 0
-            for h, nv in enumerate(neighs):
-                n, s, _ = nv.shape3
+            segs = []
+            for h, nv, n, s, r, hr in _hops(neighs):
                 dm = d_means.rows_slice(r, r + n)
                 segs.append((dm, r, n, 1, 1.0 / (s + 1)))
                 segs.append((dm, prev_offsets[h + 1], n, s, 1.0 / (s + 1)))
-                r += n
             ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, segments=segs, mask_y=prev_mask, stream=e.stream)
             return
-        r = 0
-        for h, nv in enumerate(neighs):           # self parts first: d_self = d_means / (s + 1)
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):           # self parts first: d_self = d_means / (s + 1)
             mask = prev_mask.rows_slice(r, r + n) if prev_mask is not None else None
             self._bwd_dropped(d_means.rows_slice(r, r + n), n, 1, 1.0 / (s + 1), rate, SITE_SELF, k, r,
                               d_prev.rows_slice(r, r + n), mask, False, ("s", h))
-            r += n
-        r = row0 = 0
-        for h, nv in enumerate(neighs):
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             r0 = prev_offsets[h + 1]
             dst = d_prev.rows_slice(r0, r0 + n * s)
             mask = prev_mask.rows_slice(r0, r0 + n * s) if prev_mask is not None else None
-            self._bwd_dropped(d_means.rows_slice(r, r + n), n, s, 1.0 / (s + 1), rate, SITE_NEIGH, k, row0, dst, mask,
+            self._bwd_dropped(d_means.rows_slice(r, r + n), n, s, 1.0 / (s + 1), rate, SITE_NEIGH, k, hr, dst, mask,
                               (h + 1 < len(neighs)), ("n", h))
-            r += n
-            row0 += n * s
 
     def infer_full(self, graph, H):
         """MeanAggregator.infer_full for the GCN layer: act(mean over {all neighbors} U {self} . W [+ b]) (aggregators.py:96-116).
@@ -605,6 +618,7 @@ class GCNAggregator(_SageBase):
             for r0, n in graph.windows(inf.WINDOW_ROWS):
                 graph.reduce(e, inf.CSR_MEAN_SELF, P, out.rows_slice(r0, r0 + n), r0, n, act=self.act_code)
         else:
+            # (not _infer_reduce_sage: one matrix and no self operand)
             means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
             for r0, n in graph.windows(inf.WINDOW_ROWS):
                 graph.reduce(e, inf.CSR_MEAN_SELF, H, means, r0, n)
@@ -614,49 +628,102 @@ class GCNAggregator(_SageBase):
         return out
 
 
-class _PoolingAggregator(_SageBase):
-    """relu-MLP over every neighbor row, pooled over the s samples, then the SAGE matmuls
-    (aggregators.py:119-195 for max, :197-273 for mean)."""
-    POOL = "max"
+class _PoolBase(_SageBase):
+    """What the one- and two-layer pooling aggregators share: the relu-Dense stack over every neighbor row (widths by
+    model_size, _WIDTHS) created BEFORE the SAGE variables, as the reference creates them."""
+    _WIDTHS = {}
+    fuse_pool = True           # switch: Dense + reduce_max in one launch per hop (False: the [n*s, hidden] rows go to HBM)
+    dedup_pool = True          # switch: the first Dense once per DISTINCT sampled id where _dedup_wanted says it pays
+    dedup_min_rows = None      # ... sampled rows above which it pays; None = read GS_POOL_DEDUP_MIN_ROWS (2048) at call time
+    last_pool_kernel = None    # record: "split16" | "split_bf16x3" | "fp32_mfma", the distinct-id kernel taken (_mlp_distinct)
+    last_unique = None         # record: (device count of distinct ids, sampled rows) of the last distinct-id forward
 
     def __init__(self, input_dim, output_dim, model_size="small", neigh_input_dim=None, dropout=0., bias=False,
                  act=relu, name=None, concat=False, **kwargs):
-        super(_PoolingAggregator, self).__init__(**kwargs)
-        self.dropout = dropout
-        self.bias = bias
-        self.act = act
-        self.act_code = _act_code(act)
-        self.concat = concat
+        super(_PoolBase, self).__init__(**kwargs)
         if neigh_input_dim is None:
             neigh_input_dim = input_dim
-        if model_size == "small":
-            hidden_dim = self.hidden_dim = 512
-        elif model_size == "big":
-            hidden_dim = self.hidden_dim = 1024
-        else:
+        if model_size not in self._WIDTHS:
             raise ops._lib.GraphsageAmdError("model_size must be 'small' or 'big'")
+        self._widths = self._WIDTHS[model_size]
         self.mlp_layers = []
-        self.mlp_layers.append(Dense(input_dim=neigh_input_dim, output_dim=hidden_dim, act=relu, dropout=dropout,
-                                     sparse_inputs=False, logging=self.logging))
-        # the MLP weights are NOT part of aggregator.vars (aggregators.py:144-159) -> no weight decay
-        for v in self.mlp_layers[0].vars.values():
-            v.decay = False
-        scope = _scope(self.name, name)
+        for d_from, d_to in zip((neigh_input_dim,) + self._widths, self._widths):
+            self.mlp_layers.append(Dense(input_dim=d_from, output_dim=d_to, act=relu, dropout=dropout,
+                                         sparse_inputs=False, logging=self.logging))
+        # the MLP weights are NOT part of aggregator.vars (aggregators.py:144-159, :303-325) -> no weight decay
+        for layer in self.mlp_layers:
+            for v in layer.vars.values():
+                v.decay = False
+        self._init_sage(input_dim, output_dim, neigh_input_dim, dropout, bias, act, concat, name,
+                        neigh_rows=self._widths[-1], bias_cols=(2 if concat else 1) * output_dim)
+
+    def _dedup_wanted(self, x_all, rows_total):
+        """Run the pooling MLP once per DISTINCT sampled id of the step?  (the call_hops of both pooling classes)"""
+        dedup_min = self.dedup_min_rows
+        if dedup_min is None:
+            dedup_min = int(os.environ.get("GS_POOL_DEDUP_MIN_ROWS", "2048"))
+        return (x_all is not None and x_all.ids is not None and rows_total > dedup_min
+                and x_all.src.rows < (1 << 31)
+                and x_all.src.rows <= int(os.environ.get("GS_POOL_DEDUP_MAX_RATIO", "16")) * rows_total
+                and self.dedup_pool)
+
+    def _mlp_distinct(self, mlp, hidden, x_all, rows_total, k):
+        """relu(X[uniq] . W + b) over the step's distinct ids: (H [rows_total, hidden] with the device count's leading rows
+        filled, inv [rows_total], count).  Records the kernel taken in last_pool_kernel."""
         e = self.engine
-        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((hidden_dim, output_dim)), decay=True)
-        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
-        if self.bias:
-            self.vars['bias'] = e.add_variable(scope + '/bias', zeros(((2 if concat else 1) * output_dim,)), decay=True)
-        self.input_dim = input_dim
-        self.output_dim = output_dim
-        self.neigh_input_dim = neigh_input_dim
-        self._saved = []
+        X, ids, nv_rows = x_all.src, x_all.ids, x_all.src.rows
+        rank_ws = e.ws_i32((self.name, "dd_rank", k), 2 * nv_rows)       # [flags | ranks]: zero-initialised, self-cleaning
+        sums_ws = e.ws_i32((self.name, "dd_sums", k), 256)
+        uniq = e.ws_i32((self.name, "dd_uniq", k), rows_total)
+        inv = e.ws_i32((self.name, "dd_inv", k), rows_total)
+        cnt = e.ws_i32((self.name, "dd_count", k), 1)
+        ops.call("gs_unique_ids", ops.ptr(ids), rows_total, nv_rows, ops.ptr(rank_ws), ops.ptr(sums_ws), ops.ptr(uniq),
+                 ops.ptr(inv), ops.ptr(cnt), e.stream)
+        Hu = e.ws_mat((self.name, "H_unique", k), rows_total, hidden)
+        W, bmlp = mlp.vars['weights'].value, mlp.vars['bias'].value.buf
+        self.last_pool_kernel = None
+        if (e.split_pool and e.pool_f16 and not x_all.requires_grad and e.is_constant_table(X) and e.table16_fits(X)):
+            # ... on the fp16 matrix pipe, operands as two fp16 pieces each (fp32 accuracy class, half the matrix-pipe work of
+            # the three-piece form below, which is bound by the chip's POWER cap): the constant feature table is cut once.
+            # A table with trainable leading columns (identity features, rewritten behind every optimizer launch) is NOT
+            # constant -- its cut-once copy would be stale from the second step on -- and takes the three-piece kernel below,
+            # which cuts the rows it reads in registers.
+            self.last_pool_kernel = "split16"
+            X2, rexp = e.table16_of(X)
+            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
+            ops.call("gs_dense_fwd_rows_split16", ops.ptr(X2), ops.ptr(rexp), ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
+                     ops.ptr(e.split_of(mlp.vars['weights'], form="f16x2")), hidden, ACT_RELU, ops.ptr(bmlp),
+                     Hu.ptr, Hu.ld, ops.ptr(ws), 4 * ws.numel(), e.stream)
+        elif e.split_pool:
+            # the 51 GF of the pooling MLP on the bf16 matrix pipe, operands as three bf16 pieces (fp32 accuracy)
+            # (+ a workspace: the last, nearly empty round of its one-per-CU workgroups is cut along K, gs_split.hip)
+            self.last_pool_kernel = "split_bf16x3"
+            ws = e.ws_f32((self.name, "split_ws"), ops.split_tiled_ws_words())
+            ops.call("gs_dense_fwd_rows_split_ws", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt),
+                     ops.ptr(e.split_of(mlp.vars['weights'])), hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld,
+                     ops.ptr(ws), 4 * ws.numel(), e.stream)
+        else:
+            self.last_pool_kernel = "fp32_mfma"
+            ops.call("gs_dense_fwd_rows_dev", X.ptr, X.ld, ops.ptr(uniq), X.d, rows_total, ops.ptr(cnt), W.ptr, W.ld,
+                     hidden, ACT_RELU, ops.ptr(bmlp), Hu.ptr, Hu.ld, e.stream)
+        return Hu, inv, cnt
 
-    def prefetch(self, self_all, neighs, tag=0):
-        return None   # the pooling MLP needs the weights: nothing can run ahead
+    def _max_gather(self, Hu, inv, neighs, width, pooled, argmax):
+        """reduce_max over each hop's s samples of the per-distinct-id rows Hu, picked through the index `inv`."""
+        e = self.engine
+        for h, nv, n, s, r, hr in _hops(neighs):
+            pr, ar = pooled.rows_slice(r, r + n), argmax[r:r + n]
+            ops.call("gs_segment_max_gather_fwd", Hu.ptr, Hu.ld, inv.data_ptr() + 4 * hr, n, s, width, pr.ptr, pr.ld,
+                     ar.data_ptr(), argmax.stride(0), e.stream)
 
-    def prefetch_jobs(self, self_all, neighs, tag=0):
-        return None, []
+
+class _PoolingAggregator(_PoolBase):
+    """relu-MLP over every neighbor row, pooled over the s samples, then the SAGE matmuls
+    (aggregators.py:119-195 for max, :197-273 for mean)."""
+    POOL = "max"
+    _WIDTHS = {"small": (512,), "big": (1024,)}
+    hidden_dim = property(lambda self: self._widths[0])
+    sparse_wgrad = True        # switch: layer 0's MLP weight gradient from the arg-max rows alone (gs_maxpool_sparse_wgrad)
 
     def call_hops(self, self_all, neighs, means=None, side_jobs=None):
         e = self.engine
@@ -665,16 +732,12 @@ class _PoolingAggregator(_SageBase):
         k = len(self._saved)
         rate = _rate(self.dropout)
         mlp = self.mlp_layers[0]
-        rows_total = sum(nv.shape3[0] * nv.shape3[1] for nv in neighs)
-        flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
-        x_all = _contiguous(flat)
-        pieces = [x_all] if x_all is not None else flat
+        flat, x_all, pieces, rows_total = _flatten(neighs)
         pooled = e.ws_mat((self.name, "pooled", k), n_total, self.hidden_dim)
         argmax = None
         if self.POOL == "max":
             argmax = e.ws_i32((self.name, "argmax", k), n_total * self.hidden_dim).view(n_total, self.hidden_dim)
-        fused_pool = (self.POOL == "max" and rate == 0 and getattr(self, "fuse_pool", True)
-                      and all(nv.shape3[1] <= 64 for nv in neighs))
+        fused_pool = self.POOL == "max" and rate == 0 and self.fuse_pool and all(nv.shape3[1] <= 64 for nv in neighs)
         # layer 0 (rows gathered from the feature table through the model's contiguous id buffer): the MLP of a node does
         # not depend on who sampled it -- run it once per DISTINCT id of the step and let the reduce_max pick rows
         # through an index (37 % fewer GEMM rows at Reddit's degree)
@@ -684,24 +747,14 @@ class _PoolingAggregator(_SageBase):
         H = None
         if dedup:
             Hu, inv, cnt = self._mlp_distinct(mlp, self.hidden_dim, x_all, rows_total, k)
-            r = hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
-                pr, ar = pooled.rows_slice(r, r + n), argmax[r:r + n]
-                ops.call("gs_segment_max_gather_fwd", Hu.ptr, Hu.ld, inv.data_ptr() + 4 * hr, n, s, self.hidden_dim, pr.ptr, pr.ld,
-                         ar.data_ptr(), argmax.stride(0), e.stream)
-                r += n
-                hr += n * s
+            self._max_gather(Hu, inv, neighs, self.hidden_dim, pooled, argmax)
             self.last_unique = (cnt, rows_total)
         elif fused_pool:
             # Dense (:176-179) + reduce_max (:181) in ONE launch per hop: the GEMM tiles hold whole neighbor groups and
             # reduce them in the epilogue, so the [n*s, hidden] activations never exist in HBM
-            r = 0
-            for nv, x in zip(neighs, flat):
-                n, s, _ = nv.shape3
+            for (h, nv, n, s, r, hr), x in zip(_hops(neighs), flat):
                 ops.dense_pool_max_fwd(x.src, x.ids, n, s, mlp.vars['weights'].value, mlp.vars['bias'].value.buf,
                                        pooled.rows_slice(r, r + n), argmax[r:r + n], stream=e.stream)
-                r += n
         else:
             # h_reshaped = Dense(reshape(neigh, [n*s, d]))   (aggregators.py:176-179): one GEMM over every neighbor row
             H = e.ws_mat((self.name, "H", k), rows_total, self.hidden_dim)
@@ -715,41 +768,27 @@ class _PoolingAggregator(_SageBase):
                     dropped.append(Rows(xd, None, x.n, x.requires_grad))
                     r += x.n
                 pieces = dropped
-            r = 0
-            for x in pieces:
-                ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, mlp.vars['weights'].value, self.hidden_dim, False,
-                                   ACT_RELU, mlp.vars['bias'].value.buf, H.rows_slice(r, r + x.n), stream=e.stream)
-                r += x.n
-            r = hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
+            _pieces_fwd(e, pieces, mlp.vars['weights'].value, mlp.vars['bias'].value.buf, self.hidden_dim, ACT_RELU, H)
+            for h, nv, n, s, r, hr in _hops(neighs):
                 if self.POOL == "max":
                     ops.segment_max_fwd(H.rows_slice(hr, hr + n * s), n, s, pooled.rows_slice(r, r + n), argmax[r:r + n],
                                         stream=e.stream)                                             # reduce_max (:181)
                 else:
                     ops.gather_mean_fwd(H.rows_slice(hr, hr + n * s), None, n, s, out=pooled.rows_slice(r, r + n),
                                         stream=e.stream)                                             # reduce_mean (:259)
-                r += n
-                hr += n * s
         out = self._sage_out(self_all, pooled, n_total, k)
-        self._push((self_all, neighs, pieces, (H, rows_total), pooled, argmax, out, rate))
+        self._push(_PoolSaved(self_all, neighs, pieces, rows_total, H, pooled, argmax, out, rate))
         return out
 
     def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
         e = self.engine
-        self_all, neighs, pieces, (H, rows_total), pooled, argmax, out, rate = self._saved.pop()
+        saved = self._saved.pop()
+        self_all, neighs, pieces, rows_total, H, pooled, argmax, out, rate = saved
         n_total = self_all.n
         k = len(self._saved)
-
         o = self.output_dim
-        n_out = o * (2 if self.concat else 1)
         mlp = self.mlp_layers[0]
-        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
-        col_n = o if self.concat else 0
-        e.wgrad(self.vars['self_weights'], self_all.src, self_all.ids, dz, 0, n_total)
-        e.wgrad(self.vars['neigh_weights'], pooled, None, dz, col_n, n_total)
-        if self.bias:
-            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        dz, col_n = self._sage_bwd(d_out, out, n_total, pre_masked, self_all.src, self_all.ids, pooled)
         d_pooled = e.ws_mat((self.name, "d_pooled", k), n_total, self.hidden_dim)
         ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, d_pooled, stream=e.stream)
         dpm = None
@@ -762,65 +801,27 @@ class _PoolingAggregator(_SageBase):
         threads = min(512, (self.hidden_dim + 63) // 64 * 64)
         sparse = (self.POOL == "max" and d_prev is None and embed_sink is None and rate == 0
                   and all(nv.ids is not None for nv in neighs)
-                  and getattr(self, "sparse_wgrad", True)
+                  and self.sparse_wgrad
                   and 16 * max(nv.shape3[1] for nv in neighs) <= 4 * threads)
         if sparse:
             # layer 0: the gathered feature rows need no gradient, so dH = [n*s, hidden] is never materialised; the
             # MLP weight gradient is accumulated straight from the arg-max rows (gs_maxpool_sparse_wgrad)
-            r = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
+            for h, nv, n, s, r, hr in _hops(neighs):
                 e.sparse_pool_wgrad(mlp.vars['weights'], nv.src, nv.ids, n, s, argmax[r:r + n], dpm.rows_slice(r, r + n))
-                r += n
             return
         dH = e.ws_mat((self.name, "dH", k), rows_total, self.hidden_dim)
-        r = hr = 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             if self.POOL == "max":
                 ops.segment_max_bwd(dpm.rows_slice(r, r + n), pooled.rows_slice(r, r + n), argmax[r:r + n], n, s,
                                     dH.rows_slice(hr, hr + n * s), stream=e.stream)
             else:
                 ops.mean_bwd(d_pooled.rows_slice(r, r + n), n, s, 1.0 / s, dH.rows_slice(hr, hr + n * s),
                              mask_y=H.rows_slice(hr, hr + n * s), stream=e.stream)
-            r += n
-            hr += n * s
         if self.POOL != "max":
             e.bgrad(mlp.vars['bias'], dH, rows_total, self.hidden_dim)
-        r = 0
-        for x in pieces:
-            e.wgrad(mlp.vars['weights'], x.src, x.ids, dH.rows_slice(r, r + x.n), 0, x.n)
-            r += x.n
-        if embed_sink is not None:
-            var, c = embed_sink                    # see MeanAggregator.backward_hops; every neighbor row has its own dH
-            d_self_e = e.ws_mat((self.name, "d_self_e", k), n_total, c)
-            ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value.rows_slice(0, c), d_self_e, stream=e.stream)
-            e.scatter_grad(var, d_self_e, self_all.ids, n_total, 1, 1.0)      # the pooling aggregators do not drop self
-            d_neigh_e = e.ws_mat((self.name, "d_neigh_e", k), rows_total, c)
-            ops.dense_dgrad(dH, 0, self.hidden_dim, rows_total, mlp.vars['weights'].value.rows_slice(0, c), d_neigh_e,
-                            stream=e.stream)
-            if rate > 0:
-                ops.dropout_rows(d_neigh_e, None, rows_total, self._drop(rate, SITE_MLP, k), d_neigh_e, stream=e.stream)
-            hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
-                e.scatter_grad(var, d_neigh_e.rows_slice(hr, hr + n * s), nv.ids, n * s, 1, 1.0)
-                hr += n * s
-        if d_prev is None:
-            return
-        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
-        ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value, d_self_all, stream=e.stream)
-        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
-        ops.dense_dgrad(dH, 0, self.hidden_dim, rows_total, mlp.vars['weights'].value, d_neigh, stream=e.stream)
-        if rate > 0:
-            ops.dropout_rows(d_neigh, None, rows_total, self._drop(rate, SITE_MLP, k), d_neigh, stream=e.stream)
-        segs, hr = [], 0
-        for h, nv in enumerate(neighs):         # every neighbor row has its own gradient row (s = 1)
-            n, s, _ = nv.shape3
-            segs.append((d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0))
-            hr += n * s
-        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
-                            mask_y=prev_mask, stream=e.stream)
+        _pieces_wgrad(e, mlp.vars['weights'], pieces, dH)
+        self._row_input_grads(saved, k, dz, dH, self.hidden_dim, mlp.vars['weights'].value, embed_sink, d_prev, prev_mask,
+                              prev_offsets, drop=(lambda: self._drop(rate, SITE_MLP, k)) if rate > 0 else None)
 
     def infer_full(self, graph, H):
         """MeanAggregator.infer_full for the pooling layers: the MLP (aggregators.py:176-179) runs once per NODE, then the hidden
@@ -835,14 +836,7 @@ class _PoolingAggregator(_SageBase):
             ops.gemm(False, False, n, hid, d_in, H.rows_slice(r0, r0 + n), mlp.vars['weights'].value, Hh.rows_slice(r0, r0 + n),
                      bias=mlp.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
         pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid)
-        b = self.vars['bias'].value.buf if self.bias else None
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            graph.reduce(e, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, pooled, r0, n)
-            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, pooled, None, n, self.vars['self_weights'].value,
-                               self.vars['neigh_weights'].value, o, self.concat, self.act_code, b, out.rows_slice(r0, r0 + n),
-                               stream=e.stream)
-        e.sync()
-        return out
+        return self._infer_reduce_sage(graph, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, pooled, H, out)
 
 
 class MaxPoolingAggregator(_PoolingAggregator):
@@ -874,43 +868,22 @@ class SeqAggregator(_SageBase):
     def __init__(self, input_dim, output_dim, model_size="small", neigh_input_dim=None, dropout=0., bias=False,
                  act=relu, name=None, concat=False, **kwargs):
         super(SeqAggregator, self).__init__(**kwargs)
-        self.dropout = dropout
-        self.bias = bias
-        self.act = act
-        self.act_code = _act_code(act)
-        self.concat = concat
         if neigh_input_dim is None:
             neigh_input_dim = input_dim
-        if model_size == "small":
-            hidden_dim = self.hidden_dim = 128
-        elif model_size == "big":
-            hidden_dim = self.hidden_dim = 256
-        else:
+        if model_size not in ("small", "big"):
             raise ops._lib.GraphsageAmdError("model_size must be 'small' or 'big'")
+        hidden_dim = self.hidden_dim = 128 if model_size == "small" else 256
         if bias and concat:
             # the reference adds a [output_dim] bias to the [n, 2 * output_dim] concatenation, which TF refuses
             raise ops._lib.GraphsageAmdError("SeqAggregator: bias needs concat=False (the bias has output_dim entries)")
-        scope = _scope(self.name, name)
+        self._init_sage(input_dim, output_dim, neigh_input_dim, dropout, bias, act, concat, name,
+                        neigh_rows=hidden_dim, bias_cols=output_dim)
         e = self.engine
-        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((hidden_dim, output_dim)), decay=True)
-        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
-        if self.bias:
-            self.vars['bias'] = e.add_variable(scope + '/bias', zeros((output_dim,)), decay=True)
         kernel = glorot((neigh_input_dim + hidden_dim, 4 * hidden_dim))       # BasicLSTMCell kernel (glorot over the whole)
         cell = self.name + '/rnn/basic_lstm_cell'
         self.lstm_wx = e.add_variable(cell + '/kernel_x', kernel[:neigh_input_dim], decay=False)
         self.lstm_wh = e.add_variable(cell + '/kernel_h', kernel[neigh_input_dim:], decay=False)
         self.lstm_b = e.add_variable(cell + '/bias', zeros((4 * hidden_dim,)), decay=False)
-        self.input_dim = input_dim
-        self.output_dim = output_dim
-        self.neigh_input_dim = neigh_input_dim
-        self._saved = []
-
-    def prefetch(self, self_all, neighs, tag=0):
-        return None   # the recurrence needs the weights: nothing can run ahead
-
-    def prefetch_jobs(self, self_all, neighs, tag=0):
-        return None, []
 
     def call_hops(self, self_all, neighs, means=None, side_jobs=None):
         e = self.engine
@@ -918,22 +891,12 @@ class SeqAggregator(_SageBase):
         n_total = self_all.n
         k = len(self._saved)
         H = self.hidden_dim
-        flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
-        x_all = _contiguous(flat)
-        pieces = [x_all] if x_all is not None else flat
-        rows_total = sum(x.n for x in flat)
+        _, _, pieces, rows_total = _flatten(neighs)
         # one recurrence segment per hop: n sequences of s steps, step rows in the hop's order of the flattened neighbors
-        segs, row0 = [], 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
-            segs.append((nv.src, nv.ids, n, s, row0))
-            row0 += n * s
+        segs = [(nv.src, nv.ids, n, s, hr) for h, nv, n, s, r, hr in _hops(neighs)]
         G = e.ws_mat((self.name, "lstm_gates", k), rows_total, 4 * H)
-        r = 0
-        for x in pieces:        # [x_t, h_{t-1}] . kernel + bias, the x_t half for every step at once
-            ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, self.lstm_wx.value, 4 * H, False, ACT_IDENTITY,
-                               self.lstm_b.value.buf, G.rows_slice(r, r + x.n), stream=e.stream)
-            r += x.n
+        # [x_t, h_{t-1}] . kernel + bias, the x_t half for every step at once
+        _pieces_fwd(e, pieces, self.lstm_wx.value, self.lstm_b.value.buf, 4 * H, ACT_IDENTITY, G)
         lengths = e.ws_i32((self.name, "lstm_len", k), n_total)
         ops.lstm_lengths(segs, neighs[0].shape3[2], lengths, stream=e.stream)
         C = e.ws_mat((self.name, "lstm_c", k), rows_total, H)
@@ -947,55 +910,34 @@ class SeqAggregator(_SageBase):
         ops.sage_dense_fwd(self_all.src, self_all.ids, h_last, None, n_total, self.vars['self_weights'].value,
                            self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b, out,
                            stream=e.stream)
-        self._push((self_all, neighs, pieces, segs, rows_total, lengths, G, C, Hp, h_last, out))
+        self._push(_SeqSaved(self_all, neighs, pieces, rows_total, segs, lengths, G, C, Hp, h_last, out))
         return out
 
     def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
         e = self.engine
-        self_all, neighs, pieces, segs, rows_total, lengths, A, C, Hp, h_last, out = self._saved.pop()
+        saved = self._saved.pop()
         if embed_sink is not None:
             raise ops._lib.GraphsageAmdError("SeqAggregator: trainable identity features are not supported")
+        self_all, neighs, pieces, rows_total, segs, lengths, A, C, Hp, h_last, out = saved
         n_total = self_all.n
         k = len(self._saved)
         H = self.hidden_dim
-        o = self.output_dim
-        n_out = o * (2 if self.concat else 1)
-        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
-        col_n = o if self.concat else 0
-        e.wgrad(self.vars['self_weights'], self_all.src, self_all.ids, dz, 0, n_total)
-        e.wgrad(self.vars['neigh_weights'], h_last, None, dz, col_n, n_total)
-        if self.bias:
-            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        dz, col_n = self._sage_bwd(d_out, out, n_total, pre_masked, self_all.src, self_all.ids, h_last)
         dh_last = e.ws_mat((self.name, "d_lstm_h_last", k), n_total, H)
-        ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, dh_last, stream=e.stream)
+        ops.dense_dgrad(dz, col_n, self.output_dim, n_total, self.vars['neigh_weights'].value, dh_last, stream=e.stream)
         wt = e.ws_f32((self.name, "lstm_wh_t"), 4 * H * H)
         dG = ops.lstm_bwd(segs, H, self.lstm_wh.value, wt, lengths, A, C, dh_last, A, stream=e.stream)   # dG over the gates
         e.wgrad(self.lstm_wh, Hp, None, dG, 0, rows_total)
         e.bgrad(self.lstm_b, dG, rows_total, 4 * H)
-        r = 0
-        for x in pieces:
-            e.wgrad(self.lstm_wx, x.src, x.ids, dG.rows_slice(r, r + x.n), 0, x.n)
-            r += x.n
-        if d_prev is None:
-            return
-        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
-        ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value, d_self_all, stream=e.stream)
-        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
-        ops.dense_dgrad(dG, 0, 4 * H, rows_total, self.lstm_wx.value, d_neigh, stream=e.stream)
-        pull, hr = [], 0
-        for h, nv in enumerate(neighs):         # every neighbor row has its own gradient row (s = 1)
-            n, s, _ = nv.shape3
-            pull.append((d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0))
-            hr += n * s
-        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=pull,
-                            mask_y=prev_mask, stream=e.stream)
+        _pieces_wgrad(e, self.lstm_wx, pieces, dG)
+        self._row_input_grads(saved, k, dz, dG, 4 * H, self.lstm_wx.value, None, d_prev, prev_mask, prev_offsets)
 
     def infer_full(self, graph, H):
         raise ops._lib.GraphsageAmdError("SeqAggregator has no full-neighborhood form: an LSTM over a random permutation of a "
                                          "SAMPLE of the neighbors has no meaning over the whole list (use eval_step)")
 
 
-class TwoMaxLayerPoolingAggregator(_SageBase):
+class TwoMaxLayerPoolingAggregator(_PoolBase):
     """Aggregates via pooling over two MLP functions (aggregators.py:276-361): Dense(in -> hid1, relu), Dense(hid1 -> hid2,
     relu) over every neighbor row, reduce_max over the s samples, then the SAGE matmuls.  hid1 / hid2 = 512 / 256 ("small")
     or 1024 / 512 ("big").  Neither Dense is in aggregator.vars (no weight decay; still clipped and updated by Adam).
@@ -1007,52 +949,12 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
     (`fuse_dgrad`; False, or a shape outside the kernel's range: gs_segment_max_bwd + gs_dense_dgrad + gs_act_bwd).
 
     Dropout is refused: the reference drops the input of both Dense layers, and the second has no mask site here."""
-
-    def __init__(self, input_dim, output_dim, model_size="small", neigh_input_dim=None, dropout=0., bias=False,
-                 act=relu, name=None, concat=False, **kwargs):
-        super(TwoMaxLayerPoolingAggregator, self).__init__(**kwargs)
-        self.dropout = dropout
-        self.bias = bias
-        self.act = act
-        self.act_code = _act_code(act)
-        self.concat = concat
-        if neigh_input_dim is None:
-            neigh_input_dim = input_dim
-        if model_size == "small":
-            hidden_dim_1, hidden_dim_2 = 512, 256
-        elif model_size == "big":
-            hidden_dim_1, hidden_dim_2 = 1024, 512
-        else:
-            raise ops._lib.GraphsageAmdError("model_size must be 'small' or 'big'")
-        self.hidden_dim_1, self.hidden_dim_2 = hidden_dim_1, hidden_dim_2
-        self.mlp_layers = []
-        self.mlp_layers.append(Dense(input_dim=neigh_input_dim, output_dim=hidden_dim_1, act=relu, dropout=dropout,
-                                     sparse_inputs=False, logging=self.logging))
-        self.mlp_layers.append(Dense(input_dim=hidden_dim_1, output_dim=hidden_dim_2, act=relu, dropout=dropout,
-                                     sparse_inputs=False, logging=self.logging))
-        # the MLP weights are NOT part of aggregator.vars (aggregators.py:303-325) -> no weight decay
-        for layer in self.mlp_layers:
-            for v in layer.vars.values():
-                v.decay = False
-        scope = _scope(self.name, name)
-        e = self.engine
-        self.vars['neigh_weights'] = e.add_variable(scope + '/neigh_weights', glorot((hidden_dim_2, output_dim)), decay=True)
-        self.vars['self_weights'] = e.add_variable(scope + '/self_weights', glorot((input_dim, output_dim)), decay=True)
-        if self.bias:
-            self.vars['bias'] = e.add_variable(scope + '/bias', zeros(((2 if concat else 1) * output_dim,)), decay=True)
-        self.input_dim = input_dim
-        self.output_dim = output_dim
-        self.neigh_input_dim = neigh_input_dim
-        self.fuse_dgrad = True          # dH1 by gs_pool2_dgrad; False = the three-launch composition
-        self.last_dgrad_kernel = None   # "pool2_dgrad" | "composed": what the last backward pass took
-        self.last_dgrad_indexed = None  # ... and whether it read H1 through the distinct-id index
-        self._saved = []
-
-    def prefetch(self, self_all, neighs, tag=0):
-        return None   # the pooling MLP needs the weights: nothing can run ahead
-
-    def prefetch_jobs(self, self_all, neighs, tag=0):
-        return None, []
+    _WIDTHS = {"small": (512, 256), "big": (1024, 512)}
+    hidden_dim_1 = property(lambda self: self._widths[0])
+    hidden_dim_2 = property(lambda self: self._widths[1])
+    fuse_dgrad = True          # switch: dH1 by gs_pool2_dgrad; False = the three-launch composition
+    last_dgrad_kernel = None   # record: "pool2_dgrad" | "composed", what the last backward pass took
+    last_dgrad_indexed = None  # ... and whether it read H1 through the distinct-id index
 
     def call_hops(self, self_all, neighs, means=None, side_jobs=None):
         e = self.engine
@@ -1065,13 +967,10 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
         mlp1, mlp2 = self.mlp_layers
         hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
         W2, b2 = mlp2.vars['weights'].value, mlp2.vars['bias'].value.buf
-        flat = [Rows(nv.src, nv.ids, nv.shape3[0] * nv.shape3[1], nv.requires_grad) for nv in neighs]
-        rows_total = sum(x.n for x in flat)
-        x_all = _contiguous(flat)
-        pieces = [x_all] if x_all is not None else flat
+        _, x_all, pieces, rows_total = _flatten(neighs)
         pooled = e.ws_mat((self.name, "pooled2", k), n_total, hid2)
         argmax = e.ws_i32((self.name, "argmax2", k), n_total * hid2).view(n_total, hid2)
-        fused_pool = getattr(self, "fuse_pool", True) and all(nv.shape3[1] <= 64 for nv in neighs)
+        fused_pool = self.fuse_pool and all(nv.shape3[1] <= 64 for nv in neighs)
         self.last_pool_kernel = self.last_unique = None
         inv = None
         if fused_pool and self._dedup_wanted(x_all, rows_total):
@@ -1079,58 +978,38 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
             H1, inv, cnt = self._mlp_distinct(mlp1, hid1, x_all, rows_total, k)
             H2 = e.ws_mat((self.name, "H2_unique", k), rows_total, hid2)
             ops.sage_dense_fwd(None, None, H1, None, rows_total, None, W2, hid2, False, ACT_RELU, b2, H2, stream=e.stream)
-            r = hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
-                pr, ar = pooled.rows_slice(r, r + n), argmax[r:r + n]
-                ops.call("gs_segment_max_gather_fwd", H2.ptr, H2.ld, inv.data_ptr() + 4 * hr, n, s, hid2, pr.ptr, pr.ld,
-                         ar.data_ptr(), argmax.stride(0), e.stream)
-                r += n
-                hr += n * s
+            self._max_gather(H2, inv, neighs, hid2, pooled, argmax)
             self.last_unique = (cnt, rows_total)
         else:
             # h = Dense(reshape(neigh, [n*s, d]))   (aggregators.py:338-341, first layer): one GEMM over every neighbor row
             H1 = e.ws_mat((self.name, "H1", k), rows_total, hid1)
-            r = 0
-            for x in pieces:
-                ops.sage_dense_fwd(None, None, x.src, x.ids, x.n, None, mlp1.vars['weights'].value, hid1, False, ACT_RELU,
-                                   mlp1.vars['bias'].value.buf, H1.rows_slice(r, r + x.n), stream=e.stream)
-                r += x.n
+            _pieces_fwd(e, pieces, mlp1.vars['weights'].value, mlp1.vars['bias'].value.buf, hid1, ACT_RELU, H1)
             H2 = None
             if not fused_pool:
                 H2 = e.ws_mat((self.name, "H2", k), rows_total, hid2)
                 ops.sage_dense_fwd(None, None, H1, None, rows_total, None, W2, hid2, False, ACT_RELU, b2, H2, stream=e.stream)
-            r = hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
+            for h, nv, n, s, r, hr in _hops(neighs):
                 if fused_pool:         # second Dense + reduce_max (:341) in ONE launch: [n*s, hid2] never exists
                     ops.dense_pool_max_fwd(H1.rows_slice(hr, hr + n * s), None, n, s, W2, b2, pooled.rows_slice(r, r + n),
                                            argmax[r:r + n], stream=e.stream)
                 else:
                     ops.segment_max_fwd(H2.rows_slice(hr, hr + n * s), n, s, pooled.rows_slice(r, r + n), argmax[r:r + n],
                                         stream=e.stream)
-                r += n
-                hr += n * s
         out = self._sage_out(self_all, pooled, n_total, k)
-        self._push((self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out))
+        self._push(_Pool2Saved(self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out))
         return out
 
     def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
         e = self.engine
-        self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out = self._saved.pop()
+        saved = self._saved.pop()
+        self_all, neighs, pieces, rows_total, H1, inv, pooled, argmax, out = saved
         n_total = self_all.n
         k = len(self._saved)
         o = self.output_dim
-        n_out = o * (2 if self.concat else 1)
         mlp1, mlp2 = self.mlp_layers
         hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
         W1, W2 = mlp1.vars['weights'], mlp2.vars['weights']
-        dz = self._dz(d_out, out, n_total, n_out, pre_masked)
-        col_n = o if self.concat else 0
-        e.wgrad(self.vars['self_weights'], self_all.src, self_all.ids, dz, 0, n_total)
-        e.wgrad(self.vars['neigh_weights'], pooled, None, dz, col_n, n_total)
-        if self.bias:
-            e.bgrad(self.vars['bias'], dz, n_total, n_out)
+        dz, col_n = self._sage_bwd(d_out, out, n_total, pre_masked, self_all.src, self_all.ids, pooled)
         d_pooled = e.ws_mat((self.name, "d_pooled2", k), n_total, hid2)
         ops.dense_dgrad(dz, col_n, o, n_total, self.vars['neigh_weights'].value, d_pooled, stream=e.stream)
         # reduce_max grad then the second Dense's relu grad: only the arg-max row of each (group, column), where pooled > 0
@@ -1159,9 +1038,7 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
             # H1 holds one row per sampled row: gs_maxpool_sparse_wgrad reads each hop's slice of it through 0 .. n s - 1
             n_iota = max(nv.shape3[0] * nv.shape3[1] for nv in neighs)
             iota = ops.pool2_iota(e.ws_i32((self.name, "iota", k), n_iota), n_iota, stream=e.stream)
-        r = hr = 0
-        for nv in neighs:
-            n, s, _ = nv.shape3
+        for h, nv, n, s, r, hr in _hops(neighs):
             dp, am = dpm.rows_slice(r, r + n), argmax[r:r + n]
             dH = dH1.rows_slice(hr, hr + n * s)
             if fused:
@@ -1183,38 +1060,9 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
                     e.sparse_pool_wgrad(W2, H1.rows_slice(hr, hr + n * s), iota[:n * s], n, s, am, dp)
             else:
                 e.wgrad(W2, H1x.rows_slice(hr, hr + n * s), None, dH2.rows_slice(hr, hr + n * s), 0, n * s)
-            r += n
-            hr += n * s
         e.bgrad(mlp1.vars['bias'], dH1, rows_total, hid1)
-        r = 0
-        for x in pieces:
-            e.wgrad(W1, x.src, x.ids, dH1.rows_slice(r, r + x.n), 0, x.n)
-            r += x.n
-        if embed_sink is not None:
-            var, c = embed_sink                    # see MeanAggregator.backward_hops; every neighbor row has its own dH1
-            d_self_e = e.ws_mat((self.name, "d_self_e", k), n_total, c)
-            ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value.rows_slice(0, c), d_self_e, stream=e.stream)
-            e.scatter_grad(var, d_self_e, self_all.ids, n_total, 1, 1.0)
-            d_neigh_e = e.ws_mat((self.name, "d_neigh_e", k), rows_total, c)
-            ops.dense_dgrad(dH1, 0, hid1, rows_total, W1.value.rows_slice(0, c), d_neigh_e, stream=e.stream)
-            hr = 0
-            for nv in neighs:
-                n, s, _ = nv.shape3
-                e.scatter_grad(var, d_neigh_e.rows_slice(hr, hr + n * s), nv.ids, n * s, 1, 1.0)
-                hr += n * s
-        if d_prev is None:
-            return
-        d_self_all = e.ws_mat((self.name, "d_self", k), n_total, self.input_dim)
-        ops.dense_dgrad(dz, 0, o, n_total, self.vars['self_weights'].value, d_self_all, stream=e.stream)
-        d_neigh = e.ws_mat((self.name, "d_neigh", k), rows_total, self.neigh_input_dim)
-        ops.dense_dgrad(dH1, 0, hid1, rows_total, W1.value, d_neigh, stream=e.stream)
-        segs, hr = [], 0
-        for h, nv in enumerate(neighs):         # every neighbor row has its own gradient row (s = 1)
-            n, s, _ = nv.shape3
-            segs.append((d_neigh.rows_slice(hr, hr + n * s), prev_offsets[h + 1], n * s, 1, 1.0))
-            hr += n * s
-        ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
-                            mask_y=prev_mask, stream=e.stream)
+        _pieces_wgrad(e, W1, pieces, dH1)
+        self._row_input_grads(saved, k, dz, dH1, hid1, W1.value, embed_sink, d_prev, prev_mask, prev_offsets)
 
     def infer_full(self, graph, H):
         """_PoolingAggregator.infer_full with both Dense layers run once per NODE, then the hid2-wide table is max-reduced over
@@ -1233,11 +1081,4 @@ class TwoMaxLayerPoolingAggregator(_SageBase):
             ops.gemm(False, False, n, hid2, hid1, Hh1.rows_slice(0, n), mlp2.vars['weights'].value, Hh2.rows_slice(r0, r0 + n),
                      bias=mlp2.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
         pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid2)
-        b = self.vars['bias'].value.buf if self.bias else None
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            graph.reduce(e, inf.CSR_MAX, Hh2, pooled, r0, n)
-            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, pooled, None, n, self.vars['self_weights'].value,
-                               self.vars['neigh_weights'].value, o, self.concat, self.act_code, b, out.rows_slice(r0, r0 + n),
-                               stream=e.stream)
-        e.sync()
-        return out
+        return self._infer_reduce_sage(graph, inf.CSR_MAX, Hh2, pooled, H, out)

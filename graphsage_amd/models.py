@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .aggregators import (GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator, SeqAggregator,
-                          TwoMaxLayerPoolingAggregator)
+                          TwoMaxLayerPoolingAggregator, contiguous_rows)
 from .engine import get_engine
 from .inits import glorot
 from .layers import Rows, identity
@@ -777,7 +777,6 @@ class SampleAndAggregate(object):
     def layer_inputs(self, hidden, layer, batch_size, num_samples, support_sizes, dims, concat):
         """(self_all, neighs, rows, offsets) of one layer: the contiguous self rows of all hops and the per-hop
         neighbor views reshaped as models.py:323-327."""
-        from .aggregators import _contiguous
         K = len(num_samples)
         n_hops = K - layer
         dim_mult = 2 if concat and (layer != 0) else 1
@@ -785,7 +784,7 @@ class SampleAndAggregate(object):
         for hop in range(n_hops):
             neigh_dims = [batch_size * support_sizes[hop], num_samples[K - hop - 1], dim_mult * dims[layer]]
             neighs.append(hidden[hop + 1].reshape(neigh_dims))
-        self_all = _contiguous(hidden[:n_hops])
+        self_all = contiguous_rows(hidden[:n_hops])
         rows = [hidden[h].n for h in range(n_hops + 1)]
         offsets = [0]
         for r in rows:
@@ -795,7 +794,6 @@ class SampleAndAggregate(object):
     def aggregate(self, samples, input_features, dims, num_samples, support_sizes, batch_size=None,
                   aggregators=None, name=None, concat=False, model_size="small", layer0_means=None,
                   layer0_side_jobs=None, _stop_after_layer=None, last_layer_side_jobs=None):
-        from .aggregators import _contiguous
         if batch_size is None:
             batch_size = samples[0].numel()
         features = input_features[0] if isinstance(input_features, (list, tuple)) else input_features

@@ -148,9 +148,9 @@ class SupervisedGraphsage(SampleAndAggregate):
             ids_copy = None
             agg0 = self.aggregators[0]
             agg0.wgrad_ids = None
-            if getattr(e, "_sampler_to_wgrad", False) and self.aggregator_type == "mean" and agg0._saved and agg0._saved[-1][5] is not None \
-                    and agg0._saved[-1][5].ids is not None:
-                src = agg0._saved[-1][5].ids                     # the rows layer 0's self term gathered: [roots | hop-1 ids]
+            if getattr(e, "_sampler_to_wgrad", False) and self.aggregator_type == "mean" and agg0._saved \
+                    and agg0._saved[-1].self_in is not None and agg0._saved[-1].self_in.ids is not None:
+                src = agg0._saved[-1].self_in.ids                # the rows layer 0's self term gathered: [roots | hop-1 ids]
                 dst = e.ws_i32(("wgrad_ids", self.name, n), src.numel())
                 ids_copy = (src, dst, src.numel())
                 agg0.wgrad_ids = dst[:src.numel()]
