@@ -829,7 +829,7 @@ extern "C" int gs_dense_fwd_rows_dev(const float* X, int64_t ldx, const int32_t*
     GS_CHECK_MAT(X, ldx, "gs_dense_fwd_rows_dev X");
     GS_CHECK_MAT(W, ldw, "gs_dense_fwd_rows_dev W");
     GS_CHECK_MAT(out, ldo, "gs_dense_fwd_rows_dev out");
-    GS_REQUIRE(idx && n_dev && n_max > 2048 && d > 0 && out_dim > 0 && ldx >= rup4(d) && ldw >= out_dim && ldo >= rup4(out_dim),
+    GS_REQUIRE(idx && n_dev && n_max > 2048 && d > 0 && out_dim > 0 && ldx >= rup4(d) && ldw >= rup4(out_dim) && ldo >= rup4(out_dim),
                "gs_dense_fwd_rows_dev: bad args (n_max must be > 2048: the tiled kernels)");
     GemmArgs g = {};
     g.t[0] = GemmTerm{X, idx, W, ldx, ldw, d};

@@ -145,6 +145,15 @@ int gs_mean_bwd(const float* d_mean, int64_t ldd, int64_t n, int32_t s, int32_t 
  * K3  dense contraction (fp32 MFMA, v_mfma_f32_32x32x2_f32)
  *     replaces tf.matmul at aggregators.py:51,53 (Mean), :110 (GCN), :183-184 (MaxPool),
  *     concat/add_n at :56-58, bias :61-62, act :64, and Dense._call layers.py:104-116
+ *
+ *     Operand contract of every entry point of this section and of gs_dense_pool_max_fwd / gs_dense_fwd_rows_dev: an operand is
+ *     read as whole float4, so columns up to round_up(width, 4) (from col0 where there is one) must be READABLE, but nothing
+ *     outside the logical operand is ever used -- pad columns, the columns next to a [col0, col0 + out_dim) slice (a column
+ *     slice of a wider matrix is a valid operand), table rows that no index names and rows beyond the row count may hold
+ *     anything, NaN included.  Outputs: the logical block is written, columns [N, round_up(N, 4)) are written as zeros except
+ *     by the split-K slab forms (gs_dense_wgrad*: logical columns only; a slab whose row slice is empty is zeros) and the
+ *     pooled / argmax outputs of gs_dense_pool_max_fwd (logical columns only, stored word by word: ldp, lda >= hidden is all
+ *     they need); no other word is touched.  tests/test_gemm_edges_gpu.py holds this.
  * ------------------------------------------------------------------------------------------- */
 
 /* out = act( [ self·W_self  ||  agg·W_neigh ] + bias )          concat != 0   (out is [n, 2*out_dim])
