@@ -94,6 +94,8 @@ _PROTOS = {
     "gs_dense_wgrad_grouped_tiled3_sample": [_P, c_int32, _P, c_int32, _P, _P],
     "gs_sage_dense_fwd_tiled3": [_P, c_int64, _P, c_int32, _P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int, _P,
                                  _P, c_int64, _P, c_int32, _P],
+    "gs_sage_dense_fwd_tiled3_means": [_P, c_int64, _P, c_int32, _P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, c_int32,
+                                       c_int, _P, _P, c_int64, _P, c_int32, c_int64, c_int32, _P, c_int64, _P],
     "gs_split_rows_bytes": [c_int32, c_int32, _P],
     "gs_split_rows": [_P, c_int64, c_int32, c_int32, _P, _P],
     "gs_dense_fwd_rows_split": [_P, c_int64, _P, c_int32, c_int64, _P, _P, c_int32, c_int, _P, _P, c_int64, _P],
@@ -110,6 +112,8 @@ _PROTOS = {
     "gs_sage_tail_fwd_bwd": [_P, _P, c_int32, _P],
     "gs_sage_tail_z": [_P, _P, c_int32, _P],
     "gs_sage_tail_dh0": [_P, _P, c_int32, _P],
+    "gs_sage_tail_fwd_bwd_means": [_P, _P, c_int32, _P],
+    "gs_sage_tail_z_means": [_P, _P, c_int32, _P],
     "gs_dropout_rows": [_P, c_int64, _P, c_int64, c_int32, _P, _P, c_int64, _P],
     "gs_gather_mean_dropout_fwd": [_P, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, c_int64, _P, _P],
     "gs_scatter_add_rows": [_P, c_int64, c_int64, c_int32, c_int32, c_float, _P, _P, c_int64, _P],
@@ -137,6 +141,7 @@ _PROTOS = {
                                       c_uint64, _P, c_uint64, _P, c_uint64, _P],
     "gs_linkpred_tail_supported": [c_int32, c_int32, c_int32],
     "gs_linkpred_tail": [_P, _P, c_int32, _P],
+    "gs_linkpred_tail_means": [_P, _P, c_int32, _P],
     "gs_linkpred_tail_neg": [_P, _P, c_int, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P, c_int32, _P],
     "gs_unique_ids": [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P],
     "gs_dense_fwd_rows_dev": [_P, c_int64, _P, c_int32, c_int64, _P, _P, c_int64, c_int32, c_int, _P, _P, c_int64, _P],

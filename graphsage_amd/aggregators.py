@@ -310,6 +310,9 @@ class MeanAggregator(_SageBase):
     layer1_z = True            # switch: the last layer as ONE gs_sage_tail_z launch where _last_layer_z allows it
     wgrad_ids = None           # the step's private copy of the self ids for the next weight gradient (set by the model)
     last_fused_launch = None   # record: (re-issuable launch, description) of the last horizontally fused forward
+    l1_means_out = None        # set by the model before a layer-0 call: the fused tail's `means` workspace [n_roots, 2 output_dim]
+    l1_means_written = False   # ... and whether that call's launch wrote it (the tail then takes its *_means entry)
+    last_fwd_entry = None      # record: library entry point of the last all-hops forward launch (tests)
 
     def __init__(self, input_dim, output_dim, neigh_input_dim=None, dropout=0., bias=False, act=relu,
                  name=None, concat=False, **kwargs):
@@ -356,6 +359,7 @@ class MeanAggregator(_SageBase):
         n_total = self_all.n
         k = len(self._saved)
         rate = _rate(self.dropout)
+        l1_means, self.l1_means_out, self.l1_means_written = self.l1_means_out, None, False
         h0 = self._last_layer_z(self_all, neighs, rate, means)
         if h0 is not None:
             # reduce_mean + both matmuls + concat (aggregators.py:48-58) of the last layer: ONE lean launch instead of a
@@ -379,9 +383,21 @@ class MeanAggregator(_SageBase):
             # horizontally fused launch: the contraction workgroups + the NEXT step's gather-mean waves share the CUs.
             # Stream form (gs_stream.hip): split-K workgroups without LDS staging, the self rows gathered in the A loads.
             tiled3 = stream_fwd and e.tiled3_fwd and self.output_dim % 4 == 0
+            # the rows are [roots | hop 1 (s consecutive rows per root)]: the launch can form the next layer's neighbor means
+            n_roots = neighs[0].shape3[0]
+            s1 = neighs[1].shape3[0] // max(n_roots, 1) if len(neighs) == 2 else 0
+            with_means = (tiled3 and l1_means is not None and 1 <= s1 <= 64 and n_total == n_roots * (1 + s1)
+                          and l1_means.rows >= n_roots and l1_means.d == n_out)
+            self.l1_means_written = with_means
+            self.last_fwd_entry = ("gs_sage_dense_fwd_tiled3_means" if with_means else "gs_sage_dense_fwd_tiled3" if tiled3 else
+                                   "gs_sage_dense_fwd_stream" if stream_fwd else "gs_sage_dense_fwd_cogather")
 
             def launch(jobs=list(side_jobs or ())):
-                if tiled3:
+                if with_means:
+                    ops.sage_dense_fwd_tiled3_means(self_all.src, self_all.ids, means, n_total, self.vars['self_weights'].value,
+                                                    self.vars['neigh_weights'].value, self.output_dim, self.act_code, b, out,
+                                                    n_roots, s1, l1_means, jobs, stream=e.stream)
+                elif tiled3:
                     # LDS-tiled, on the bf16 matrix pipe in the three-piece arithmetic (fp32 in and out, cut inside the kernel)
                     ops.sage_dense_fwd_tiled3(self_all.src, self_all.ids, means, n_total, self.vars['self_weights'].value,
                                               self.vars['neigh_weights'].value, self.output_dim, self.act_code, b, out, jobs,

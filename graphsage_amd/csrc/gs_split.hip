@@ -672,6 +672,12 @@ struct Fwd3Args {
     const float* bias;     // indexed by output column (incl. the concat offset), nullable
     int32_t act;
     int32_t tiles_m, tiles_n, n_tiles;     // n_tiles = tiles_m * tiles_n * nterms
+    // optional (gs_sage_dense_fwd_tiled3_means): the rows are [roots (n_roots) | hop 1 (n_roots * s), the s rows of a root
+    // consecutive]; the epilogue also writes means[root][term * N + col] = mean_j C[n_roots + root * s + j][term * N + col], the
+    // layer-1 neighbor means, from the finished tile.  Row tiling then: root_tiles tiles of 64 root rows, and hop tiles of
+    // gpt * s <= 64 rows (gpt whole groups) that start at row n_roots -- no group straddles two workgroups.
+    float* means;          // nullable: rows are tiled 64 by 64 from row 0
+    int32_t ldmeans, n_roots, s, root_tiles, gpt;
 };
 // independent 16-byte loads a RIDER wave of the two tiled launches keeps in flight (gs_gather_dev.h: run_gather_item)
 #ifndef T3_RIDER_U
@@ -720,14 +726,23 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     const int term = tile / per_term;
     const int it = tile - term * per_term;
     const int tile_m = it / g.tiles_n, tile_n = it - tile_m * g.tiles_n;
-    const int m0 = tile_m * F3_BM, n0 = tile_n * 128;
+    const int n0 = tile_n * 128;
+    // rows [m0, mend) of this tile; local rows beyond mend are clamped for the A loads and never stored
+    int m0 = tile_m * F3_BM, mend = min(m0 + F3_BM, g.M);
+    if (g.means) {
+        if (tile_m < g.root_tiles) mend = min(m0 + F3_BM, g.n_roots);
+        else {
+            m0 = g.n_roots + (tile_m - g.root_tiles) * g.gpt * g.s;
+            mend = min(m0 + g.gpt * g.s, g.M);
+        }
+    }
     const Fwd3Term& T = g.t[term];
-    const int K = T.K, N = g.N, M = g.M;
+    const int K = T.K, N = g.N;
     const int stages = (K + F3_KS - 1) / F3_KS;
     const int K4 = ((K + 3) >> 2) << 2;                        // readable columns of a row
     // ---- A: (row tid >> 2, float4 tid & 3) of the 64 x 16 stage tile, through registers
     const int arow = tid >> 2, aq = tid & 3;
-    const int grow = min(m0 + arow, M - 1);
+    const int grow = min(m0 + arow, mend - 1);
     const int64_t srow = T.a_idx ? (int64_t)T.a_idx[grow] : (int64_t)grow;
     const float* __restrict__ xrow = T.A + srow * T.lda;
     const int a_wr = (arow * F3_LDA + 4 * aq) * 2;
@@ -940,7 +955,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
         const int r = 8 * itr + r0;
         const int row = m0 + r;
         const f32x4 v = *reinterpret_cast<const f32x4*>(otile + r * 36 + c4);
-        if (row < M) {
+        if (row < mend) {
             float* dst = g.C + (int64_t)row * g.ldc + col_off + colg;
             if (colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
             else {
@@ -950,14 +965,38 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
             }
         }
     }
+    // ---- the layer-1 neighbor means of a hop tile's whole groups, from the staging tile (wave-private: no barrier): 8 lanes x
+    //      float4 = the wave's 32 columns, lane >> 3 = the group; zero start, j = 0..s-1, ONE multiply by 1/s -- the expression
+    //      (and so the bits) of the fused tail's z helpers (gs_tail_dev.h); every (root, column) belongs to exactly one wave
+    if (g.means && tile_m >= g.root_tiles && colg < N) {
+        const int s = g.s;
+        const int ngroups = (mend - m0) / s;
+        const int root0 = (tile_m - g.root_tiles) * g.gpt;
+        const float inv_s = 1.0f / (float)s;
+        for (int grp = r0; grp < ngroups; grp += 8) {
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            const float* src = otile + (grp * s) * 36 + c4;
+            for (int j = 0; j < s; ++j) v += *reinterpret_cast<const f32x4*>(src + j * 36);
+            v *= inv_s;
+            float* dst = g.means + (int64_t)(root0 + grp) * g.ldmeans + col_off + colg;
+            if (colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
+            else {
+                dst[0] = v.x;
+                if (colg + 1 < N) dst[1] = v.y;
+                if (colg + 2 < N) dst[2] = v.z;
+            }
+        }
+    }
     F3_STAMP(5);
     F3_STAMPV(7, wall_clock64());
 }
 
-extern "C" int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self, const float* agg,
-                                        int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self,
-                                        const float* W_neigh, int64_t ldw_neigh, int32_t out_dim, int act, const float* bias,
-                                        float* out, int64_t ldo, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+// l1_means == NULL: gs_sage_dense_fwd_tiled3; else gs_sage_dense_fwd_tiled3_means (see Fwd3Args.means)
+static int fwd_tiled3_impl(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self, const float* agg,
+                           int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self,
+                           const float* W_neigh, int64_t ldw_neigh, int32_t out_dim, int act, const float* bias,
+                           float* out, int64_t ldo, const gs_gather_desc* jobs_host, int32_t n_jobs, int64_t n_roots, int32_t s,
+                           float* l1_means, int64_t ld_means, void* stream) {
     if (n == 0 && n_jobs == 0) return GS_OK;
     GS_REQUIRE(agg && W_neigh && out && d_agg > 0 && out_dim > 0 && n >= 0 && n < (1ll << 30), "gs_sage_dense_fwd_tiled3: bad args");
     GS_REQUIRE(!self || (W_self && d_self > 0), "gs_sage_dense_fwd_tiled3: W_self / d_self missing");
@@ -981,6 +1020,17 @@ extern "C" int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, cons
     }
     g.M = (int32_t)n; g.N = out_dim; g.C = out; g.ldc = (int32_t)ldo; g.bias = bias; g.act = act;
     g.tiles_m = (int)gs_ceil_div(n, F3_BM);
+    if (l1_means) {
+        GS_REQUIRE(self, "gs_sage_dense_fwd_tiled3_means: the concat form (two terms) only");
+        GS_REQUIRE(n_roots > 0 && s >= 1 && s <= F3_BM && n == n_roots * (1 + (int64_t)s),
+                   "gs_sage_dense_fwd_tiled3_means: n must be n_roots * (1 + s), 1 <= s <= %d", F3_BM);
+        GS_CHECK_MAT(l1_means, ld_means, "gs_sage_dense_fwd_tiled3_means l1_means");
+        GS_REQUIRE(ld_means >= 2 * (int64_t)out_dim && ld_means < (1ll << 31), "gs_sage_dense_fwd_tiled3_means: ld_means must be >= 2 * out_dim");
+        g.means = l1_means; g.ldmeans = (int32_t)ld_means; g.n_roots = (int32_t)n_roots; g.s = s;
+        g.root_tiles = (int)gs_ceil_div(n_roots, F3_BM);
+        g.gpt = F3_BM / s;
+        g.tiles_m = g.root_tiles + (int)gs_ceil_div(n_roots, g.gpt);
+    }
     g.tiles_n = (int)gs_ceil_div(out_dim, 128);
     g.n_tiles = n > 0 ? g.tiles_m * g.tiles_n * g.nterms : 0;
     CoGatherS J = {};
@@ -994,6 +1044,25 @@ extern "C" int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, cons
     hipLaunchKernelGGL(sage_tiled3_fwd_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, g, J);
     GS_LAUNCH_CHECK("sage_tiled3_fwd_kernel");
     return GS_OK;
+}
+
+extern "C" int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self, const float* agg,
+                                        int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self,
+                                        const float* W_neigh, int64_t ldw_neigh, int32_t out_dim, int act, const float* bias,
+                                        float* out, int64_t ldo, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return fwd_tiled3_impl(self, ld_self, self_idx, d_self, agg, ld_agg, d_agg, n, W_self, ldw_self, W_neigh, ldw_neigh, out_dim, act,
+                           bias, out, ldo, jobs_host, n_jobs, 0, 0, nullptr, 0, stream);
+}
+
+extern "C" int gs_sage_dense_fwd_tiled3_means(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self,
+                                              const float* agg, int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self,
+                                              int64_t ldw_self, const float* W_neigh, int64_t ldw_neigh, int32_t out_dim, int act,
+                                              const float* bias, float* out, int64_t ldo, const gs_gather_desc* jobs_host,
+                                              int32_t n_jobs, int64_t n_roots, int32_t s, float* l1_means, int64_t ld_means,
+                                              void* stream) {
+    GS_REQUIRE(l1_means, "gs_sage_dense_fwd_tiled3_means: l1_means missing");
+    return fwd_tiled3_impl(self, ld_self, self_idx, d_self, agg, ld_agg, d_agg, n, W_self, ldw_self, W_neigh, ldw_neigh, out_dim, act,
+                           bias, out, ldo, jobs_host, n_jobs, n_roots, s, l1_means, ld_means, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradients, LDS-tiled

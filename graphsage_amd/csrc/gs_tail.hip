@@ -650,7 +650,8 @@ static int launch_tail(const TailArgs& a, const CoGatherS& J, int64_t gather_wav
     return a.C > 64 ? launch_tail_cw<D, O, 2>(a, J, gather_waves, st) : launch_tail_cw<D, O, 1>(a, J, gather_waves, st);
 }
 
-extern "C" int gs_sage_tail_fwd_bwd(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+// means_ready: gs_sage_tail_fwd_bwd_means (`means` is an input, see TailArgs.means_ready)
+static int tail_fwd_bwd_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, int means_ready, void* stream) {
     GS_REQUIRE(q, "gs_sage_tail_fwd_bwd: null descriptor");
     if (q->n == 0) return GS_OK;
     GS_REQUIRE(q->n > 0 && q->s > 0, "gs_sage_tail_fwd_bwd: bad sizes");
@@ -695,6 +696,11 @@ extern "C" int gs_sage_tail_fwd_bwd(const gs_tail_desc* q, const gs_gather_desc*
     a.train = q->train ? 1 : 0;
     a.z_ready = q->z_ready ? 1 : 0;
     a.gcn = q->gcn ? 1 : 0;
+    if (means_ready && q->gcn) {
+        gs_set_error("gs_sage_tail_fwd_bwd_means: the gcn form computes its own means (gs_sage_tail_fwd_bwd)");
+        return GS_ENOTSUP;
+    }
+    a.means_ready = means_ready ? 1 : 0;
     GS_REQUIRE(q->ids_copy_n >= 0 && (q->ids_copy_n == 0 || (q->ids_copy_src && q->ids_copy_dst)), "gs_sage_tail_fwd_bwd: ids_copy pointers missing");
     if (!q->z_ready) { a.ids_copy_src = q->ids_copy_src; a.ids_copy_dst = q->ids_copy_dst; a.ids_copy_n = q->ids_copy_n; }
     GS_REQUIRE(!q->gcn || (q->W_neigh == q->W_self + O && q->ldwn == q->ldws),
@@ -716,10 +722,18 @@ extern "C" int gs_sage_tail_fwd_bwd(const gs_tail_desc* q, const gs_gather_desc*
     return launch_tail<128, 64>(a, J, gw, st);
 }
 
+extern "C" int gs_sage_tail_fwd_bwd(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return tail_fwd_bwd_impl(q, jobs_host, n_jobs, 0, stream);
+}
+
+extern "C" int gs_sage_tail_fwd_bwd_means(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return tail_fwd_bwd_impl(q, jobs_host, n_jobs, 1, stream);
+}
+
 // Split form, first launch: z = [h_self . W_self | mean(h_neigh) . W_neigh] and the neighbor means of the descriptor (the
 // head / label / gradient fields are not touched), + gather riders.  Follow with gs_sage_tail_fwd_bwd on the same
 // descriptor with z_ready = 1.
-extern "C" int gs_sage_tail_z(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+static int tail_z_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, int means_ready, void* stream) {
     GS_REQUIRE(q, "gs_sage_tail_z: null descriptor");
     if (q->n == 0) return GS_OK;
     GS_REQUIRE(q->n > 0 && q->s > 0, "gs_sage_tail_z: bad sizes");
@@ -746,6 +760,11 @@ extern "C" int gs_sage_tail_z(const gs_tail_desc* q, const gs_gather_desc* jobs_
     a.means = q->means; a.ldm = q->ldm; a.z = q->z; a.ldz = q->ldz;
     a.z_ready = 1;
     a.gcn = q->gcn ? 1 : 0;
+    if (means_ready && q->gcn) {
+        gs_set_error("gs_sage_tail_z_means: the gcn form computes its own means (gs_sage_tail_z)");
+        return GS_ENOTSUP;
+    }
+    a.means_ready = means_ready ? 1 : 0;
     GS_REQUIRE(q->ids_copy_n >= 0 && (q->ids_copy_n == 0 || (q->ids_copy_src && q->ids_copy_dst)), "gs_sage_tail_z: ids_copy pointers missing");
     a.ids_copy_src = q->ids_copy_src; a.ids_copy_dst = q->ids_copy_dst; a.ids_copy_n = q->ids_copy_n;
     hipStream_t st = (hipStream_t)stream;
@@ -759,6 +778,14 @@ extern "C" int gs_sage_tail_z(const gs_tail_desc* q, const gs_gather_desc* jobs_
     if (D == 256 && O == 64) return launch_tail_z<256, 64>(a, J, gw, st);
     if (D == 128 && O == 128) return launch_tail_z<128, 128>(a, J, gw, st);
     return launch_tail_z<128, 64>(a, J, gw, st);
+}
+
+extern "C" int gs_sage_tail_z(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return tail_z_impl(q, jobs_host, n_jobs, 0, stream);
+}
+
+extern "C" int gs_sage_tail_z_means(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return tail_z_impl(q, jobs_host, n_jobs, 1, stream);
 }
 
 // The input gradients of a LAST mean layer from dLoss/dz (see sage_tail_dh0_kernel): desc fields used: h0, W_self, W_neigh,

@@ -45,6 +45,10 @@ struct TailArgs {
     int32_t pairB, pair_groups;
     // optional: ids_copy_dst[0 : ids_copy_n) = ids_copy_src[...], written by the launch's z-helper workgroups (gs_tail_desc)
     const int32_t* ids_copy_src; int32_t* ids_copy_dst; int64_t ids_copy_n;
+    // `means` is an INPUT: the layer-0 forward launch wrote it (gs_sage_dense_fwd_tiled3_means, a kernel boundary ago), bit for
+    // bit what the z helpers would compute -- a neighbor-term helper then loads its 16 rows of `means` as a self-term helper
+    // loads its 16 rows of h0 (one float4 per pass instead of s) and does not write `means`.  Not with gcn.
+    int32_t means_ready;
 };
 
 // Source row of local row r of group g (and whether it exists); rows that do not exist map to a valid row, never stored.
@@ -188,6 +192,8 @@ __device__ __forceinline__ void tail_z_helper(const TailArgs& a, const int g, co
         f32x4 v;
         if (!term && !a.gcn) {
             v = *reinterpret_cast<const f32x4*>(a.h0 + i * ldh0 + c);
+        } else if (a.means_ready) {
+            v = *reinterpret_cast<const f32x4*>(a.means + i * (int)a.ldm + c);
         } else {
             const float* nb = a.h0 + (n + i * s) * ldh0 + c;
             f32x4 hv[TAIL_NB];
@@ -347,6 +353,8 @@ __device__ __forceinline__ void tail_z_term_helper(const TailArgs& a, const int 
         f32x4 v;
         if (!term) {
             v = *reinterpret_cast<const f32x4*>(a.h0 + i * ldh0 + c);
+        } else if (a.means_ready) {
+            v = *reinterpret_cast<const f32x4*>(a.means + i * (int)a.ldm + c);
         } else {
             const float* nb = a.h0 + (n + i * s) * ldh0 + c;
             f32x4 hv[TAIL_NB];

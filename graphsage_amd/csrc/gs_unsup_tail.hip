@@ -641,10 +641,12 @@ static int lp_args(const gs_lp_tail_desc* q, LpArgs* out, const char* who) {
     return GS_OK;
 }
 
-extern "C" int gs_linkpred_tail(const gs_lp_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+// means_ready: gs_linkpred_tail_means (`means` is an input, see TailArgs.means_ready)
+static int linkpred_tail_impl(const gs_lp_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, int means_ready, void* stream) {
     LpArgs L;
     int rc = lp_args(q, &L, "gs_linkpred_tail");
     if (rc != GS_OK) return rc;
+    L.t.means_ready = means_ready ? 1 : 0;
     CoGatherS J = {};
     int64_t gw = 0;
     rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
@@ -655,6 +657,14 @@ extern "C" int gs_linkpred_tail(const gs_lp_tail_desc* q, const gs_gather_desc* 
     if (D == 256 && O == 64) return launch_lp_tail<256, 64>(L, J, gw, st);
     if (D == 128 && O == 128) return launch_lp_tail<128, 128>(L, J, gw, st);
     return launch_lp_tail<128, 64>(L, J, gw, st);
+}
+
+extern "C" int gs_linkpred_tail(const gs_lp_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return linkpred_tail_impl(q, jobs_host, n_jobs, 0, stream);
+}
+
+extern "C" int gs_linkpred_tail_means(const gs_lp_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
+    return linkpred_tail_impl(q, jobs_host, n_jobs, 1, stream);
 }
 
 extern "C" int gs_linkpred_tail_neg(const gs_lp_tail_desc* q, float* loss_out, int accumulate, float* mrr_out, uint64_t* c0,

@@ -103,6 +103,15 @@ class Engine(object):
         # the layer-0 forward LDS-tiled on the bf16 matrix pipe (three-piece arithmetic, gs_sage_dense_fwd_tiled3) instead of the
         # register-streaming fp32-MFMA kernel
         self.tiled3_fwd = os.environ.get("GS_TILED3_FWD", "1") == "1"
+        # two-layer mean models on the fused tail: the tiled layer-0 forward also writes the layer-1 neighbor means from its finished
+        # tiles (gs_sage_dense_fwd_tiled3_means) and the tail's neighbor-term helpers load them instead of re-reading s rows of h0
+        # each (the *_means tail entries); bit-identical steps.  GS_FUSED_L1_MEANS=0: the tail forms the means itself (A/B).
+        # Supervised steps: on (same-call A/B against the previous library: headline 94.4 -> 92.9 us/step, RMAT 59.5 -> 58.2).
+        # Unsupervised steps: opt-in (GS_FUSED_L1_MEANS_UNSUP=1) -- measured 1.3 us SLOWER (156.8 -> 158.5): the hop tiles of 60 rows
+        # are 22 more forward workgroups on top of 360, and the term helpers of that tail fetched the neighbor rows once per term
+        # already (profiles/fused_l1_means_ab.txt).
+        self.fused_l1_means = os.environ.get("GS_FUSED_L1_MEANS", "1") != "0"
+        self.fused_l1_means_unsup = os.environ.get("GS_FUSED_L1_MEANS_UNSUP", "0") == "1"
         # the pooling MLP on the step's distinct ids as a split-MFMA contraction (gs_split16.hip / gs_split.hip); False = fp32 MFMA
         self.split_pool = True
         # split-K policy of the weight gradients (measured sweeps: DESIGN.md section 4 / profiles/r02..r05)

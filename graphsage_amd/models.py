@@ -140,7 +140,7 @@ class SampleAndAggregate(object):
         self._wgrad_sampler_seen = None
         self.tail_halves = os.environ.get("GS_TAIL_HALVES", "1") != "0"
         self.cogather_auto = ("GS_COGATHER_TAIL" not in os.environ and "GS_COGATHER_SPLIT3" not in os.environ)
-        self.tail_free_bytes = 64e6
+        self.tail_free_bytes = float(os.environ.get("GS_TAIL_FREE_MB", 64)) * 1e6     # (sweeps: profiles/r06_tail_halves_ab.txt, fused_l1_means_ab.txt)
         self.cogather_split = float(os.environ.get("GS_COGATHER_SPLIT", 0.5 if self.engine.stream_gemm else 0.7))
         tiled = self.engine.stream_gemm and self.engine.tiled3_fwd and self.engine.tiled3_wgrad
         self.cogather_split3 = float(os.environ.get("GS_COGATHER_SPLIT3", 0.25 if tiled else 0.15))
@@ -290,6 +290,11 @@ class SampleAndAggregate(object):
         samples1, support_sizes1, means0 = prefetched
         contiguous = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(samples1[:-1], samples1[1:]))
         self._lp_tail_used = bool(contiguous and self._lp_tail_ok() and n_roots == 2 * B + self.neg_sample_size)
+        agg0 = self.aggregators[0]
+        agg0.l1_means_out = None
+        if self._lp_tail_used and e.fused_l1_means and e.fused_l1_means_unsup:
+            # (as SupervisedGraphsage._forward: the tiled layer-0 launch writes the tail's neighbor means)
+            agg0.l1_means_out = e.ws_mat("tail_means", n_roots, 2 * self.dims[1])
         out, _ = self.aggregate(samples1, [self.features], self.dims, self.num_samples, support_sizes1, batch_size=n_roots,
                                 aggregators=self.aggregators, concat=self.concat, model_size=self.model_size,
                                 layer0_means=means0, layer0_side_jobs=side_jobs, last_layer_side_jobs=z_jobs,
@@ -381,7 +386,9 @@ class SampleAndAggregate(object):
                                       self.aff_all, self.link_pred_layer.neg_sample_weights, 1.0 / B, self._lp_sync,
                                       dz=self._d_agg_out if train else None, d_h0=self._tail_dh0 if train else None,
                                       neg_slabs=slabs if train else None)
-        ops.linkpred_tail(desc, jobs=tail_jobs, stream=e.stream)
+        means_ready = bool(getattr(self.aggregators[0], "l1_means_written", False))
+        self.last_tail_entry = "gs_linkpred_tail_means" if means_ready else "gs_linkpred_tail"
+        ops.linkpred_tail(desc, jobs=tail_jobs, stream=e.stream, means_ready=means_ready)
         # launch 2 always follows (it commits the hand-over state); the step epilogue rides in it unless dropout needs the
         # clock untouched until the backward pass has run (this path runs without dropout: always folded when given)
         fold = epilogue is not None
@@ -911,7 +918,7 @@ class SampleAndAggregate(object):
         return (getattr(self, "fuse_tail", True), getattr(self, "fuse_head", True), getattr(self, "fuse_sampler", True),
                 self.sampler_rides, self.cogather_split, self.cogather_split3, self.cogather_tail, self.tail_split,
                 self.cogather_auto, self.tail_halves, self.tail_free_bytes, self.sampler_in_wgrad, self.sampler_in_wgrad_max_bytes,
-                self.cogather_z, self.cogather_lp_fwd, self.cogather_lp_tail, self.cogather_lp_neg, e.stream_gemm, e.tiled3_fwd, e.tiled3_wgrad, e.split_pool, e.pool_f16, str(getattr(self, "pipeline", None)),
+                self.cogather_z, self.cogather_lp_fwd, self.cogather_lp_tail, self.cogather_lp_neg, e.stream_gemm, e.tiled3_fwd, e.fused_l1_means, e.fused_l1_means_unsup, e.tiled3_wgrad, e.split_pool, e.pool_f16, str(getattr(self, "pipeline", None)),
                 type(self.grad_hook).__name__,
                 id(self.grad_hook), law)
 

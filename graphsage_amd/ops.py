@@ -365,6 +365,19 @@ def sage_dense_fwd_tiled3(self_m, self_idx, agg, n, W_self, W_neigh, out_dim, ac
     return out
 
 
+def sage_dense_fwd_tiled3_means(self_m, self_idx, agg, n, W_self, W_neigh, out_dim, act, bias, out, n_roots, s, l1_means, jobs=(),
+                                stream=None):
+    """gs_sage_dense_fwd_tiled3_means: sage_dense_fwd_tiled3 (concat form) over the rows [roots | hop 1], n = n_roots (1 + s), that
+    also writes the NEXT layer's neighbor means l1_means [n_roots, 2 out_dim] from its finished tiles; `out` is bit-identical."""
+    import ctypes
+    jobs = list(jobs or ())
+    arr = (_lib.GatherDesc * max(len(jobs), 1))(*jobs)
+    call("gs_sage_dense_fwd_tiled3_means", self_m.ptr, self_m.ld, ptr(self_idx), self_m.d, agg.ptr, agg.ld, agg.d, n, W_self.ptr,
+         W_self.ld, W_neigh.ptr, W_neigh.ld, out_dim, act, ptr(bias), out.ptr, out.ld, ctypes.addressof(arr), len(jobs), n_roots, s,
+         l1_means.ptr, l1_means.ld, _s(stream))
+    return out
+
+
 def split_rows_words(K, N):
     """int32 words of gs_split_rows' output (gs_split_rows_bytes / 4): groups of 8 k up to an even count of 32-k stages."""
     import ctypes
@@ -572,7 +585,7 @@ def tail_sync_error(sync, n):
 
 def sage_tail_fwd_bwd(h0, n, s, W_self, W_neigh, out_dim, W_head, b_head, labels, C, sigmoid_loss, means, z, y, logits,
                       preds, dlogits, loss_rows, dz=None, d_h0=None, counters=(), jobs=(), stream=None, sync=None,
-                      split=False, jobs_z=(), gcn=False, ids_copy=None):
+                      split=False, jobs_z=(), gcn=False, ids_copy=None, means_ready=False):
     """gs_sage_tail_fwd_bwd: layer 1 + head (+ their input gradients when dz / d_h0 are given) in ONE launch.
     counters: up to three (device int64 tensor, delta) pairs advanced at the end of the launch.
     sync: int32 device tensor of tail_sync_words(n) words, zero-initialised once and owned by ONE caller / stream
@@ -580,7 +593,8 @@ def sage_tail_fwd_bwd(h0, n, s, W_self, W_neigh, out_dim, W_head, b_head, labels
     split: two launches instead -- gs_sage_tail_z (lean z-helper kernel carrying the gather jobs `jobs_z`) and then this
     entry with z_ready (no helpers, no hand-over state) carrying `jobs`; same results bit for bit.
     ids_copy: (src int32 tensor, dst int32 tensor, count) -- the launch's helper workgroups copy the step's node ids into the
-    private buffer the weight gradients gather through (gs_tail_desc.ids_copy_*)."""
+    private buffer the weight gradients gather through (gs_tail_desc.ids_copy_*).
+    means_ready: `means` is an input, written by sage_dense_fwd_tiled3_means earlier on the stream (the *_means entry points)."""
     if sync is None and not split:
         import torch
         sync = torch.zeros(tail_sync_words(n, out_dim), dtype=torch.int32, device=h0.buf.device)
@@ -611,16 +625,20 @@ def sage_tail_fwd_bwd(h0, n, s, W_self, W_neigh, out_dim, W_head, b_head, labels
     if split:
         jz = list(jobs_z or ())
         jzarr = (_lib.GatherDesc * max(len(jz), 1))(*jz)
-        call("gs_sage_tail_z", ctypes.addressof(q), ctypes.addressof(jzarr), len(jz), _s(stream))
+        call("gs_sage_tail_z_means" if means_ready else "gs_sage_tail_z", ctypes.addressof(q), ctypes.addressof(jzarr), len(jz),
+             _s(stream))
     jobs = list(jobs or ())
     jarr = (_lib.GatherDesc * max(len(jobs), 1))(*jobs)
-    call("gs_sage_tail_fwd_bwd", ctypes.addressof(q), ctypes.addressof(jarr), len(jobs), _s(stream))
+    call("gs_sage_tail_fwd_bwd_means" if means_ready else "gs_sage_tail_fwd_bwd", ctypes.addressof(q), ctypes.addressof(jarr),
+         len(jobs), _s(stream))
 
 
-def sage_tail_z(h0, n, s, W_self, W_neigh, out_dim, means, z, jobs=(), stream=None):
+def sage_tail_z(h0, n, s, W_self, W_neigh, out_dim, means, z, jobs=(), stream=None, means_ready=False, gcn=False):
     """gs_sage_tail_z: z = [h0[:n] . W_self | mean_j(h0[n + i s + j]) . W_neigh] and the neighbor means of a LAST
-    mean-aggregator layer (concat, identity act, no bias) in one lean launch (+ gather jobs riding at the full HBM rate)."""
+    mean-aggregator layer (concat, identity act, no bias) in one lean launch (+ gather jobs riding at the full HBM rate).
+    means_ready: gs_sage_tail_z_means (`means` is an input)."""
     q = _lib.TailDesc()
+    q.gcn = 1 if gcn else 0
     q.h0, q.ldh, q.n = h0.ptr, h0.ld, n
     q.W_self, q.ldws, q.W_neigh, q.ldwn = W_self.ptr, W_self.ld, W_neigh.ptr, W_neigh.ld
     q.means, q.ldm, q.z, q.ldz = means.ptr, means.ld, z.ptr, z.ld
@@ -628,7 +646,7 @@ def sage_tail_z(h0, n, s, W_self, W_neigh, out_dim, means, z, jobs=(), stream=No
     q.z_ready = 1
     jobs = list(jobs or ())
     jarr = (_lib.GatherDesc * max(len(jobs), 1))(*jobs)
-    call("gs_sage_tail_z", ctypes.addressof(q), ctypes.addressof(jarr), len(jobs), _s(stream))
+    call("gs_sage_tail_z_means" if means_ready else "gs_sage_tail_z", ctypes.addressof(q), ctypes.addressof(jarr), len(jobs), _s(stream))
     return z
 
 
@@ -680,11 +698,12 @@ def linkpred_tail_desc(h0, B, n_neg, s, W_self, W_neigh, out_dim, means, z, y, l
     return q
 
 
-def linkpred_tail(desc, jobs=(), stream=None):
-    """gs_linkpred_tail: launch 1 of the unsupervised fused tail (+ gather jobs riding)."""
+def linkpred_tail(desc, jobs=(), stream=None, means_ready=False):
+    """gs_linkpred_tail: launch 1 of the unsupervised fused tail (+ gather jobs riding).  means_ready: gs_linkpred_tail_means
+    (desc.means is an input, written by sage_dense_fwd_tiled3_means earlier on the stream)."""
     jobs = list(jobs or ())
     jarr = (_lib.GatherDesc * max(len(jobs), 1))(*jobs)
-    call("gs_linkpred_tail", ctypes.addressof(desc), ctypes.addressof(jarr), len(jobs), _s(stream))
+    call("gs_linkpred_tail_means" if means_ready else "gs_linkpred_tail", ctypes.addressof(desc), ctypes.addressof(jarr), len(jobs), _s(stream))
 
 
 def linkpred_tail_neg(desc, loss_out=None, accumulate=False, mrr_out=None, counters=(), jobs=(), stream=None):

@@ -102,6 +102,12 @@ class SupervisedGraphsage(SampleAndAggregate):
         # anything else takes the per-operator schedule
         contiguous = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(samples1[:-1], samples1[1:]))
         self._tail_used = bool(train and contiguous and self._tail_ok())
+        agg0 = self.aggregators[0]
+        agg0.l1_means_out = None
+        if self._tail_used and e.fused_l1_means and self.aggregator_type == "mean":
+            # `tail_means` exists before the layer-0 launch: where that is the tiled concat form it writes the layer-1 neighbor
+            # means from its finished tiles (agg0.l1_means_written) and the tail's helpers load them
+            agg0.l1_means_out = e.ws_mat("tail_means", n, 2 * self.dims[1])
         out, _ = self.aggregate(samples1, [self.features], self.dims, self.num_samples, support_sizes1, batch_size=n,
                                 aggregators=self.aggregators, concat=self.concat, model_size=self.model_size,
                                 layer0_means=means0, layer0_side_jobs=side_jobs,
@@ -119,6 +125,8 @@ class SupervisedGraphsage(SampleAndAggregate):
             Z = 2 * O1
             s = self.num_samples[len(self.num_samples) - 1]
             self._tail_means = e.ws_mat("tail_means", n, h0.d)
+            means_ready = bool(getattr(agg0, "l1_means_written", False))
+            self.last_tail_entry = "gs_sage_tail_fwd_bwd_means" if means_ready else "gs_sage_tail_fwd_bwd"
             self.agg_out = e.ws_mat("tail_z", n, Z)
             self.outputs1 = e.ws_mat("outputs1", n, Z)
             self.node_preds = e.ws_mat("node_preds", n, C)
@@ -146,7 +154,6 @@ class SupervisedGraphsage(SampleAndAggregate):
             if self.tail_split and tail_jobs:
                 jobs_z, jobs_m = ops.split_gather_jobs(tail_jobs, self.cogather_tail_z)
             ids_copy = None
-            agg0 = self.aggregators[0]
             agg0.wgrad_ids = None
             if getattr(e, "_sampler_to_wgrad", False) and self.aggregator_type == "mean" and agg0._saved \
                     and agg0._saved[-1].self_in is not None and agg0._saved[-1].self_in.ids is not None:
@@ -159,7 +166,7 @@ class SupervisedGraphsage(SampleAndAggregate):
                                   self.sigmoid_loss, self._tail_means, self.agg_out, self.outputs1, self.node_preds,
                                   self.preds, self._dlogits, self._loss_rows, dz=self._tail_dz, d_h0=self._tail_dh0,
                                   counters=counters, jobs=jobs_m, stream=e.stream, sync=self._tail_sync,
-                                  split=self.tail_split, jobs_z=jobs_z, gcn=gcn1, ids_copy=ids_copy)
+                                  split=self.tail_split, jobs_z=jobs_z, gcn=gcn1, ids_copy=ids_copy, means_ready=means_ready)
         else:
             self.agg_out = out
             self.outputs1 = e.ws_mat("outputs1", n, out.d)

@@ -267,6 +267,19 @@ int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, const int32_t* 
                              int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self, const float* W_neigh,
                              int64_t ldw_neigh, int32_t out_dim, int act, const float* bias, float* out, int64_t ldo,
                              const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream);
+/* gs_sage_dense_fwd_tiled3_means (added entry point): gs_sage_dense_fwd_tiled3 (concat form: self != NULL) over the rows
+ * [roots (n_roots) | hop 1 (n_roots * s; rows n_roots + i*s .. + s - 1 belong to root i)], n = n_roots * (1 + s), 1 <= s <= 64, that
+ * ALSO writes the next layer's neighbor means from the finished tiles (reduce_mean of aggregators.py:48 over the layer's own output):
+ *   l1_means[i, c] = (((0 + out[n_roots + i*s, c]) + out[n_roots + i*s + 1, c]) + ...) * (1.f / s),  i < n_roots, c < 2 * out_dim
+ * (fp32, this order: the bits the fused tail's helper workgroups form from `out`); l1_means is [n_roots, ld_means >= 2 * out_dim],
+ * 16-byte aligned, ld_means % 4 == 0; no other word of it is touched.  `out` is bit-identical to gs_sage_dense_fwd_tiled3's: hop
+ * rows are tiled (64 / s) * s to a workgroup so that no root's rows straddle two, and an element's K reduction does not depend
+ * on the tiling. */
+int gs_sage_dense_fwd_tiled3_means(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self, const float* agg,
+                                   int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self,
+                                   const float* W_neigh, int64_t ldw_neigh, int32_t out_dim, int act, const float* bias, float* out,
+                                   int64_t ldo, const gs_gather_desc* jobs_host, int32_t n_jobs, int64_t n_roots, int32_t s,
+                                   float* l1_means, int64_t ld_means, void* stream);
 /* Contractions on the bf16 matrix pipe WITHOUT giving up fp32: every fp32 operand x is cut into three bf16 pieces
  * x = h + m + l (top / middle / low 8 significant bits: nothing is lost), a product is the sum of piece products -- each formed
  * exactly by v_mfma_f32_32x32x16_bf16 and accumulated in fp32 -- and six of the nine are kept (hh, hm, mh, mm, hl, lh; the
@@ -644,7 +657,7 @@ typedef struct gs_tail_desc {
     const float* W_head; int64_t ldwh;
     const float* b_head;
     const float* labels; int64_t ldlab;
-    float* means; int64_t ldm;
+    float* means; int64_t ldm;      /* (an INPUT of the *_means entry points) */
     float* z; int64_t ldz;
     float* y; int64_t ldy;
     float* logits; int64_t ldlo;
@@ -729,6 +742,14 @@ int gs_sage_tail_dh0(const gs_tail_desc* desc_host, const gs_gather_desc* jobs_h
 /* jobs_host / n_jobs (0..6): gather+mean jobs of the NEXT step co-scheduled in the launch (as gs_sage_dense_fwd_cogather):
  * the tail keeps n/16 CUs busy, the rest of the chip streams the gather meanwhile. */
 int gs_sage_tail_fwd_bwd(const gs_tail_desc* desc_host, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream);
+/* The three tail launches with `means` of the descriptor as an INPUT (added entry points, same descriptors): the layer-0 forward
+ * that wrote h0 has written the layer-1 neighbor means as well (gs_sage_dense_fwd_tiled3_means, earlier on the same stream), so
+ * the neighbor-term helper workgroups load 16 rows of means instead of 16 * s rows of h0 and do not write means.  Every output is
+ * bit-identical to the plain entry's when means[i] = (((0 + h0[n + i*s]) + h0[n + i*s + 1]) + ...) * (1.f / s) in fp32, which is
+ * what that forward writes.  gcn != 0 returns GS_ENOTSUP (the GCN mean includes the self row). */
+int gs_sage_tail_fwd_bwd_means(const gs_tail_desc* desc_host, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream);
+int gs_sage_tail_z_means(const gs_tail_desc* desc_host, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream);
+int gs_linkpred_tail_means(const gs_lp_tail_desc* desc_host, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream);
 
 /* Inverted dropout tf.nn.dropout(x, keep_prob = 1 - rate) (aggregators.py:46-47,104-105; layers.py:107): kept
  * elements are scaled by 1/keep_prob.  The keep mask is a counter hash of (seed, *clock_dev, site, row0 + row,
