@@ -6,6 +6,7 @@ This replaces what the TF1 runtime provided to the reference: tf.Variable storag
 (supervised_models.py:60, aggregators.py:30-33), gradient accumulation of
 optimizer.compute_gradients (supervised_models.py:95) and apply_gradients (:99).
 """
+import contextlib
 import ctypes
 import os
 
@@ -393,6 +394,16 @@ class Engine(object):
         assert var.scatter
         ops.scatter_add_rows(d, n, s, var.cols, scale, ids, Mat(var.slabs.view(var.rows, var.ld), var.cols),
                              stream=self.stream)
+
+    @contextlib.contextmanager
+    def deferring_sampler(self):
+        """Inside: a fan-out sampler launch (neigh_samplers.fanout) is not issued but handed to the next optimizer launch (or,
+        under _sampler_to_wgrad, the next weight-gradient launch) as `_deferred_sampler`."""
+        self._defer_sampler = True
+        try:
+            yield
+        finally:
+            self._defer_sampler = False
 
     def launch_wgrads(self, side_jobs=None):
         """ONE grouped launch for every queued weight gradient; `side_jobs` (gather+mean descriptors of the next step)

@@ -70,6 +70,34 @@ def device_features(features, engine=None):
     return Mat.from_numpy(np.asarray(features, dtype=np.float32), e.device, ld_multiple=32)
 
 
+def _run_captured(graphs, warm, key, fn, stream, may_capture):
+    """fn() eagerly on the first use of `key`, captured into a hipGraph (kept in `graphs`) and launched on the second, the
+    graph replayed afterwards.  may_capture() is asked only when a capture is about to start; while it says no, fn() stays
+    eager.  True when this call captured the graph."""
+    g = graphs.get(key)
+    if g is not None:
+        g.launch()
+        return False
+    if key not in warm or not may_capture():
+        fn()
+        warm.add(key)
+        return False
+    g = ops.Graph(stream)
+    g.begin()
+    try:
+        fn()
+    except Exception:
+        try:                      # leave the stream out of capture mode, or every later launch on it fails too
+            g.end()
+        except Exception:
+            pass
+        raise
+    g.end()
+    graphs[key] = g
+    g.launch()
+    return True
+
+
 class SampleAndAggregate(object):
     """Base implementation of unsupervised GraphSAGE (graphsage/models.py:187-405): three sample+aggregate passes
     (batch1, batch2, 20 degree^0.75 negatives) sharing the aggregators, l2-normalise, skip-gram cross-entropy
@@ -280,55 +308,69 @@ class SampleAndAggregate(object):
         roots[2 * B: 2 * B + self.neg_sample_size].copy_(torch.from_numpy(neg))
         torch.cuda.current_stream().synchronize()
 
+    def _forward_layers(self, roots, n, prefetched, tail_ok, means_ok, side_jobs, z_jobs=None):
+        """The head of either model's forward pass: the data phase (unless prefetched) and the aggregator layers over the n
+        roots -- layer 0 alone when the model's fused tail launch takes the rest.  Returns (output of the layers run, tail used?).
+        tail_ok(): does the fused tail apply to this step?  It also needs the hops of layer 0 in ONE contiguous buffer
+        (model.sample on the model's id buffer); anything else takes the per-operator schedule.  means_ok: let the tiled
+        layer-0 launch write the tail's layer-1 neighbor means (Engine.fused_l1_means)."""
+        e = self.engine
+        self.reset_tapes()
+        if prefetched is None:
+            prefetched = self._data_phase(roots, n, getattr(self, "_parity", 0), stage=getattr(self, "_pending_stage", None))
+        samples1, support_sizes1, means0 = prefetched
+        contiguous = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(samples1[:-1], samples1[1:]))
+        tail_used = bool(contiguous and tail_ok())
+        agg0 = self.aggregators[0]
+        agg0.l1_means_out = None
+        if tail_used and e.fused_l1_means and means_ok:
+            # `tail_means` exists before the layer-0 launch: where that is the tiled concat form it writes the layer-1 neighbor
+            # means from its finished tiles (agg0.l1_means_written) and the tail's helpers load them
+            agg0.l1_means_out = e.ws_mat("tail_means", n, 2 * self.dims[1])
+        out, _ = self.aggregate(samples1, [self.features], self.dims, self.num_samples, support_sizes1, batch_size=n,
+                                aggregators=self.aggregators, concat=self.concat, model_size=self.model_size,
+                                layer0_means=means0, layer0_side_jobs=side_jobs, last_layer_side_jobs=z_jobs,
+                                _stop_after_layer=0 if tail_used else None)
+        self.samples1 = samples1
+        if tail_used and self._tape[0][0] != "batched":
+            raise ops._lib.GraphsageAmdError("fused tail needs the contiguous id buffer (model.sample on ids_buffer)")
+        return out, tail_used
+
     def _forward_unsup(self, roots, B, n_roots, train, prefetched=None, side_jobs=None, epilogue=None, z_jobs=None, tail_jobs=None):
         """_build (:347-370) + _loss (:385-391) + _accuracy (:393-405) and, when training, the gradient of the
         link-prediction head w.r.t. the normalised embeddings."""
         e = self.engine
-        self.reset_tapes()
-        if prefetched is None:
-            prefetched = self._data_phase(roots, n_roots, getattr(self, "_parity", 0))
-        samples1, support_sizes1, means0 = prefetched
-        contiguous = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(samples1[:-1], samples1[1:]))
-        self._lp_tail_used = bool(contiguous and self._lp_tail_ok() and n_roots == 2 * B + self.neg_sample_size)
-        agg0 = self.aggregators[0]
-        agg0.l1_means_out = None
-        if self._lp_tail_used and e.fused_l1_means and e.fused_l1_means_unsup:
-            # (as SupervisedGraphsage._forward: the tiled layer-0 launch writes the tail's neighbor means)
-            agg0.l1_means_out = e.ws_mat("tail_means", n_roots, 2 * self.dims[1])
-        out, _ = self.aggregate(samples1, [self.features], self.dims, self.num_samples, support_sizes1, batch_size=n_roots,
-                                aggregators=self.aggregators, concat=self.concat, model_size=self.model_size,
-                                layer0_means=means0, layer0_side_jobs=side_jobs, last_layer_side_jobs=z_jobs,
-                                _stop_after_layer=0 if self._lp_tail_used else None)
-        self.samples1 = samples1
+        out, self._lp_tail_used = self._forward_layers(
+            roots, n_roots, prefetched, lambda: self._lp_tail_ok() and n_roots == 2 * B + self.neg_sample_size,
+            e.fused_l1_means_unsup, side_jobs, z_jobs)
         self._loss_rows = e.ws_f32("loss_rows", B)
         self._rr_rows = e.ws_f32("rr_rows", B)
         self.aff_all = e.ws_mat("aff_all", B, self.neg_sample_size + 1)
         if self._lp_tail_used:
-            if self._tape[0][0] != "batched":
-                raise ops._lib.GraphsageAmdError("fused tail needs the contiguous id buffer (model.sample on ids_buffer)")
             tj, nj = tail_jobs, None
             if tail_jobs and self.cogather_lp_neg > 0 and self.cogather_lp_tail > 0:
                 # the second launch (nine workgroups) carries its own share of the gather
                 tj, nj = ops.split_gather_jobs(tail_jobs, self.cogather_lp_tail / (self.cogather_lp_tail + self.cogather_lp_neg))
             self._forward_lp_tail(B, n_roots, train, epilogue, tj, nj)
-            return
-        self.agg_out = out
-        d = out.d
-        self.outputs_all = e.ws_mat("outputs_all", n_roots, d)
-        self.outputs1 = self.outputs_all.rows_slice(0, B)
-        # l2_normalize (:368-370) + link-prediction loss / MRR ranks (:385-405) + their gradient carried back through the
-        # normalisation: ONE launch (+ a 20-workgroup one for the negatives' rows); d_agg_out = dLoss/d(aggregator output)
-        self._d_agg_out = e.ws_mat("d_agg_out", n_roots, d)
-        # `epilogue` (the step's device-counter increments): without dropout the loss / mrr means and the counters ride in
-        # the head's second launch (with dropout the clock must not move before the backward pass: separate launch later)
-        fold = epilogue is not None and self._dropout_rate() == 0.0
-        self._epilogue_folded = fold
-        epi = (self.loss_dev, False, self.mrr_dev, self._epilogue_counters(epilogue)) if fold else None
-        self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B, self._loss_rows,
-                                                  self._rr_rows, self.aff_all, self._d_agg_out, epilogue=epi)
+        else:
+            self.agg_out = out
+            d = out.d
+            self.outputs_all = e.ws_mat("outputs_all", n_roots, d)
+            self.outputs1 = self.outputs_all.rows_slice(0, B)
+            # l2_normalize (:368-370) + link-prediction loss / MRR ranks (:385-405) + their gradient carried back through the
+            # normalisation: ONE launch (+ a 20-workgroup one for the negatives' rows); d_agg_out = dLoss/d(aggregator output)
+            self._d_agg_out = e.ws_mat("d_agg_out", n_roots, d)
+            # `epilogue` (the step's device-counter increments): without dropout the loss / mrr means and the counters ride in
+            # the head's second launch (with dropout the clock must not move before the backward pass: separate launch later)
+            fold = epilogue is not None and self._dropout_rate() == 0.0
+            self._epilogue_folded = fold
+            epi = (self.loss_dev, False, self.mrr_dev, self._epilogue_counters(epilogue)) if fold else None
+            self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B, self._loss_rows,
+                                                      self._rr_rows, self.aff_all, self._d_agg_out, epilogue=epi)
         # loss = (sum_vars wd*l2_loss + xent) / batch_size  (:386-390, :378); the xent mean (and the mrr, :404) are formed
         # by the epilogue (folded: the weight-decay terms are added behind it; separate launch: it adds to them)
-        self._weight_decay_loss(B, fold)
+        self._weight_decay_loss([v for a in self.aggregators for v in a.vars.values()], 0.5 * self.weight_decay / B,
+                                self._epilogue_folded)
 
     def _epilogue_counters(self, epilogue):
         """The step epilogue's [(device counter, increment)] * 3: optimizer step, sampler clock, pair cursor."""
@@ -336,18 +378,18 @@ class SampleAndAggregate(object):
         return [(e.step_dev, epilogue.get("step", 0)), (e.sample_clock_dev, epilogue.get("clock", 0)),
                 (epilogue.get("cursor"), epilogue.get("cursor_delta", 0))]
 
-    def _weight_decay_loss(self, B, fold):
-        """loss_dev (+)= sum_vars wd * l2_loss / batch_size (:386-388, :378).  fold: the epilogue has written the head's mean
-        already and the terms are added behind it; otherwise they start the sum and the later epilogue adds to them."""
-        self._loss_accumulate = False
+    def _weight_decay_loss(self, variables, scale, fold=False):
+        """loss_dev (+)= scale * sum_variables sum(v^2): the weight-decay terms of the loss (unsupervised: the aggregators'
+        variables, / batch_size, :386-388, :378; supervised: every decayed variable, supervised_models.py:104-108).  fold: the
+        epilogue has written the head's mean already and the terms are added behind it; otherwise they start the sum and the
+        later epilogue adds to them (_loss_accumulate)."""
+        first = not fold
         if self.weight_decay != 0.0:
-            first = not fold
-            for a in self.aggregators:
-                for v in a.vars.values():
-                    ops.call("gs_sumsq_scaled", v.value.ptr, v.size, 0.5 * self.weight_decay / B, self.loss_dev.data_ptr(),
-                             0 if first else 1, self.engine.stream)
-                    first = False
-            self._loss_accumulate = not fold
+            for v in variables:
+                ops.call("gs_sumsq_scaled", v.value.ptr, v.size, scale, self.loss_dev.data_ptr(), 0 if first else 1,
+                         self.engine.stream)
+                first = False
+        self._loss_accumulate = not first and not fold
 
     def _lp_tail_ok(self):
         """The fused layer-1 + link-prediction launches (gs_linkpred_tail / gs_linkpred_tail_neg) apply to the two-layer mean
@@ -396,7 +438,6 @@ class SampleAndAggregate(object):
         counters = self._epilogue_counters(epilogue) if fold else []
         ops.linkpred_tail_neg(desc, loss_out=self.loss_dev if fold else None, accumulate=False,
                               mrr_out=self.mrr_dev if fold else None, counters=counters, jobs=neg_jobs, stream=e.stream)
-        self._weight_decay_loss(B, fold)
 
     def _backward_unsup(self, B, n_roots, fuse_adam, wgrad_jobs=None, epilogue=None):
         """Reverse schedule.  The epilogue (loss / mrr means + device counters) runs FIRST: the fan-out sampler of a later
@@ -412,14 +453,7 @@ class SampleAndAggregate(object):
         advanced = (early or folded) and bool(epilogue.get("step"))
         e.begin_backward()
         if getattr(self, "_lp_tail_used", False):
-            # the fused tail produced every input gradient; queue the weight gradients it feeds (as SupervisedGraphsage._backward)
-            a1 = self.aggregators[1]
-            o = self.dims[2]
-            h0 = self._tail_h0
-            e.wgrad(a1.vars['self_weights'], h0.rows_slice(0, n_roots), None, self._d_agg_out, 0, n_roots)
-            e.wgrad(a1.vars['neigh_weights'], self._tail_means, None, self._d_agg_out, o, n_roots)
-            mode, agg0, rows, offsets, outs = self._tape[0]
-            agg0.backward_hops(self._tail_dh0, True, embed_sink=None)
+            self._queue_tail_wgrads(n_roots, self._d_agg_out)
         else:
             self.link_pred_layer.bilinear_wgrad()          # dW of the bilinear affinity, queued with the other weight gradients
             self.aggregate_backward(self._d_agg_out)
@@ -433,10 +467,27 @@ class SampleAndAggregate(object):
         self.engine.advance(loss_rows=self._loss_rows, n=B, loss_out=self.loss_dev, accumulate=self._loss_accumulate,
                             aux_rows=self._rr_rows, aux_out=self.mrr_dev, **counters)
 
-    def _optimize(self):
+    def _queue_tail_wgrads(self, n, dz):
+        """The fused tail launch (either model's) already produced every input gradient; queue the weight gradients it feeds:
+        layer 1's from dz = dLoss/dz [n, 2 O] (mean: z = [h0 W_self | means W_neigh]; GCN: its one matrix against the means over
+        {neighbors} U {self}), then layer 0's from the tail's d_h0."""
         e = self.engine
-        e.adam(self.learning_rate, clip=5.0, grad_scale=1.0 / self.world_size)
-        e.advance(step=1)
+        a1 = self.aggregators[1]
+        if self.aggregator_type == "gcn":
+            e.wgrad(a1.vars['weights'], self._tail_means, None, dz, 0, n)
+        else:
+            e.wgrad(a1.vars['self_weights'], self._tail_h0.rows_slice(0, n), None, dz, 0, n)
+            e.wgrad(a1.vars['neigh_weights'], self._tail_means, None, dz, self.dims[2], n)
+        self._tape[0][1].backward_hops(self._tail_dh0, True, embed_sink=None)
+
+    def _optimize(self, advanced=False):
+        """Data-parallel path: clip_by_value(+-5) + Adam after the all-reduce.  The local gradient is that of the local batch
+        mean; the hook sums over ranks and grad_scale divides by world_size.  advanced: the step counter was already incremented
+        by an earlier launch of this step."""
+        e = self.engine
+        e.adam(self.learning_rate, clip=5.0, grad_scale=1.0 / self.world_size, step_offset=0 if advanced else 1)
+        if not advanced:
+            e.advance(step=1)
 
     def _stage_feed_unsup(self, feed_dict):
         e = self.engine
@@ -455,17 +506,29 @@ class SampleAndAggregate(object):
         torch.cuda.current_stream().synchronize()
         return roots, B, n_roots
 
-    def _fetch_unsup(self, B, with_outputs=True):
+    def _handover_error(self):
+        """(error word of the fused tail's hand-over buffer, the launch's name, its waiting workgroups' name)."""
+        err = ops.lp_tail_sync_error(self._lp_sync, *self._lp_sync_shape) if getattr(self, "_lp_sync", None) is not None else 0
+        return err, "fused link-prediction tail", "main"
+
+    def _sync_checked(self):
+        """What every fetch does first: wait for the stream, then raise if the fused tail's in-kernel hand-over or the
+        gradient exchange (peer-store exchange: a bounded device-side wait that tripped) reported an error."""
         self.engine.sync()
-        if getattr(self, "_lp_sync", None) is not None:
-            err = ops.lp_tail_sync_error(self._lp_sync, *self._lp_sync_shape)
-            if err:
-                raise ops._lib.GraphsageAmdError(
-                    "fused link-prediction tail: hand-over between its workgroups failed (flags %d: 1 = a main workgroup gave up "
-                    "waiting for its helpers, 2 = unexpected arrival count); results since the last fetch are invalid -- set "
-                    "model.fuse_tail = False to use the per-operator schedule" % err)
+        err, launch, waiting = self._handover_error()
+        if err:
+            raise ops._lib.GraphsageAmdError(
+                "%s: hand-over between its workgroups failed (flags %d: 1 = a %s workgroup gave up waiting for its helpers, "
+                "2 = unexpected arrival count); results since the last fetch are invalid -- set model.fuse_tail = False to use "
+                "the per-operator schedule" % (launch, err, waiting))
         if hasattr(self.grad_hook, "check"):
             self.grad_hook.check()
+
+    def _fetch(self, B):
+        return self._fetch_unsup(B)
+
+    def _fetch_unsup(self, B, with_outputs=True):
+        self._sync_checked()
         loss = float(self.loss_dev.item())
         mrr = float(self.mrr_dev.item())
         aff = self.aff_all.numpy()
@@ -475,27 +538,14 @@ class SampleAndAggregate(object):
 
     def train_step(self, feed_dict, fetch=True):
         """sess.run([merged, opt_op, loss, ranks, aff_all, mrr, outputs1], feed_dict)  (unsupervised_train.py:273-274)."""
-        e = self.engine
         roots, B, n_roots = self._stage_feed_unsup(feed_dict)
-        fused = self.grad_hook is None
-        in_graph = self._dp_in_graph()
 
-        def fwd_bwd():
+        def body(step, local_adam, tail):
             self._stage_negatives_or_injected(roots, B)
-            epilogue = dict(step=1 if fused else 0, clock=1)
-            self._forward_unsup(roots, B, n_roots, True, epilogue=epilogue)
-            self._backward_unsup(B, n_roots, fuse_adam=fused, epilogue=epilogue)
-            if in_graph:
-                # backward | all-reduce (recorded in the graph) | clip + Adam, as _pipelined_steps_unsup
-                self.grad_hook(self)
-                self._optimize()
+            self._step_fwd_bwd(B, (roots, n_roots), None, self._NO_SHARES, dict(step=step, clock=1), local_adam)
+            tail()                # (_dispatch: a body calls tail() behind every step it issues)
 
-        # With a capturable hook the whole data-parallel step is this one function (one hipGraph): the exchange and the
-        # optimizer run exactly once per step.
-        self._run(("utrain" if fused else ("utrain_dp" if in_graph else "utrain_fb"), B, self._adj_version()), fwd_bwd)
-        if not fused and not in_graph:
-            self.grad_hook(self)
-            self._run(("opt",), self._optimize)
+        self._dispatch("utrain", (B,), body)
         return self._fetch_unsup(B) if fetch else None
 
     def eval_step(self, feed_dict):
@@ -514,7 +564,7 @@ class SampleAndAggregate(object):
         return loss, ranks, mrr, outs
 
     # ---- device-resident epoch: edge pairs live in HBM; steady state is one hipGraph replay per step with the next
-    #      step's sampling + gather co-scheduled with this step's layer-0 contraction (see supervised_models.py)
+    #      step's sampling + gather co-scheduled with this step's launches ("the step schedule" below)
     def attach_device_pairs(self, pairs):
         e = self.engine
         if self.embeds is not None:
@@ -526,39 +576,7 @@ class SampleAndAggregate(object):
         torch.cuda.synchronize()
 
     def set_epoch_pairs(self, pairs):
-        self.engine.sync()
-        self._pairs.copy_(torch.from_numpy(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)))
-        self._cursor.zero_()
-        if self._primed is not None:
-            self.engine.sample_clock_dev -= 1
-        self._primed = None
-        torch.cuda.synchronize()
-
-    def train_step_device(self, B, fetch=False):
-        self._pipelined_steps_unsup(B, 1)
-        return self._fetch_unsup(B) if fetch else None
-
-    def train_steps_device(self, B, steps, steps_per_launch=8):
-        """`steps` steps on the device-resident pairs; on one GPU `steps_per_launch` consecutive steps are replayed per
-        hipGraph launch (keeps the GPU fed when the host is slow or shared)."""
-        k = steps_per_launch - (steps_per_launch % 2)
-        if not ((self.grad_hook is None or self._dp_in_graph()) and self.use_graphs and k >= 2):
-            for _ in range(steps):
-                self._pipelined_steps_unsup(B, 1)
-            return
-        done = 0
-        while done < steps:
-            # multi-step graphs always start at buffer parity 0 (one captured graph per length); single steps realign the
-            # parity; a shorter tail takes the largest even length that fits
-            rem = steps - done
-            kk = min(k, rem - (rem % 2))
-            if self._primed == B and self._pipe_parity == 0 and kk >= 2:
-                self._pipelined_steps_unsup(B, kk)
-                done += kk
-            else:
-                self._pipelined_steps_unsup(B, 1)
-                done += 1
-        self._check_exchange()
+        self._reset_epoch(self._pairs, np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2))
 
     def _check_exchange(self):
         """A gradient exchange with bounded device-side waits (PeerPushAllReduce) reports a tripped wait through an error
@@ -592,102 +610,218 @@ class SampleAndAggregate(object):
             log("data-parallel schedule: all-reduce %.1f us stand-alone, recorded in the step graph behind the backward pass" % ar_us)
         return {"allreduce_us_standalone": ar_us}
 
-    def _pipelined_steps_unsup(self, B, k):
+    # ------------------------------------------------------------------------------ the step schedule (both models)
+    # ONE schedule: which launch carries which share of the next step's gather, where the sampler rides, the form of the
+    # optimizer (fused | in the graph behind a capturable hook | eager hook between two graphs) and the lengths / buffer
+    # parities of the captured graphs.  What differs between the models is in these hooks, which SupervisedGraphsage overrides:
+    #   _pipe_key              graph-key prefix of the pipelined steps
+    #   _sample_roots          staging + sampling of the roots of one buffer parity
+    #   _gather_shares         the next step's gather jobs divided over (layer-0 forward | tail | weight gradients | z launch)
+    #   _step_fwd_bwd          the forward / backward pair of one step
+    #   _sampler_to_wgrad_ok   may the riding sampler leave with the weight-gradient launch?  (supervised only)
+    #   _multi_step_ok, _drop_prefetched, _dp_step_early     (see below)
+    # The models also DIFFER in these points.  They are behaviour, kept as they were; do not "unify" them in passing:
+    #   * Priming.  Both prime through _prime(), but the supervised model's _drop_prefetched() hands the staged ids back to the
+    #     epoch cursor and the tick back to the sampler clock when the batch size changes; the unsupervised model hands nothing
+    #     back (its _drop_prefetched is empty): after a change of B the pairs of the dropped batch are skipped.
+    #   * In-graph data parallel (_dp_step_early).  Supervised: the tail launch / early epilogue advances the step counter
+    #     (epilogue step = 1) and the optimizer behind the hook runs with advanced=True.  Unsupervised: the epilogue leaves the
+    #     step counter alone (step = 1 only with the local optimizer) and _optimize() advances it in a launch of its own.
+    #   * Eligibility.  The supervised model pipelines (and takes multi-step graphs) only with `pipeline` on and no dropout, and
+    #     has the non-pipelined "dtrain" form for the rest; the unsupervised model always pipelines and has no such form.
+    #   * Sampler segments.  _root_segments: three segments (batch1 | batch2 | negatives) here, None for the supervised model.
+    _pipe_key = "updtrain"
+    _dp_step_early = False
+    _NO_SHARES = (None, None, None, None)
+
+    def _sample_roots(self, B, parity):
+        """Stage and sample the roots of buffer `parity`: (what _step_fwd_bwd needs of them, root rows, samples, support)."""
+        roots, n_roots = self._roots(B, parity=parity)
+        stage = None
+        if self._fanout_fusable():
+            # the edge-pair batch and the negatives are staged by the fan-out sampler launch itself (one launch, and
+            # one that can ride in the optimizer launch)
+            stage = ("unsup", self._pairs, self._cursor, B, self._neg_cdf, self._neg_guide, self._guide_bits,
+                     self.neg_sample_size, self.neg_seed)
+        else:
+            self._stage_negatives(roots, B, pairs=self._pairs, cursor=self._cursor)
+        samples, support = self._sample_phase(roots, n_roots, parity, stage=stage)
+        return (roots, n_roots), n_roots, samples, support
+
+    def _gather_shares(self, jobs):
+        tail_jobs = []
+        if self._lp_tail_ok() and self.cogather_lp_tail > 0:
+            # three-launch form (layer-0 forward | fused link-prediction tail | weight gradients): the tail is long and
+            # thin (66 main workgroups), the rest of the chip streams its share of the gather at the full rate
+            f_fwd, f_tail = self.cogather_lp_fwd, self.cogather_lp_tail + self.cogather_lp_neg
+            fwd_jobs, rest = ops.split_gather_jobs(jobs, f_fwd)
+            tail_jobs, wgrad_jobs = ops.split_gather_jobs(rest, min(1.0, f_tail / max(1e-6, 1.0 - f_fwd)))
+        else:
+            fwd_jobs, wgrad_jobs = ops.split_gather_jobs(jobs, self.cogather_split)
+        z_jobs = []
+        if not tail_jobs and self.cogather_z > 0 and len(self.num_samples) > 1 and not self._lp_tail_ok():
+            # the last layer's lean launch (gs_sage_tail_z) leaves most of the chip idle: a share rides there at
+            # the full HBM rate
+            wgrad_jobs, z_jobs = ops.split_gather_jobs(wgrad_jobs, max(0.0, 1.0 - self.cogather_z / max(1e-6, 1.0 - self.cogather_split)))
+        return fwd_jobs, tail_jobs, wgrad_jobs, z_jobs
+
+    def _step_fwd_bwd(self, B, roots, prefetched, shares, epilogue, local_adam):
+        roots, n_roots = roots
+        fwd_jobs, tail_jobs, wgrad_jobs, z_jobs = shares
+        self._forward_unsup(roots, B, n_roots, True, prefetched=prefetched, side_jobs=fwd_jobs, epilogue=epilogue, z_jobs=z_jobs,
+                            tail_jobs=tail_jobs)
+        self._backward_unsup(B, n_roots, fuse_adam=local_adam, wgrad_jobs=wgrad_jobs, epilogue=epilogue)
+
+    def _sampler_to_wgrad_ok(self, jobs):
+        return False
+
+    def _multi_step_ok(self):
+        """May train_steps_device replay several steps per graph launch?  (One GPU, or the exchange recorded in the graph.)"""
+        return self.grad_hook is None or self._dp_in_graph()
+
+    def _drop_prefetched(self):
+        """The batch size changes under a primed pipeline: nothing is handed back here (see the list above)."""
+
+    def _reset_epoch(self, table, values):
+        """New epoch: `values` into the device-resident order / pair list, the cursor back to 0."""
+        self.engine.sync()  # steps still queued on the engine stream read the old order / cursor
+        table.copy_(torch.from_numpy(values))
+        self._cursor.zero_()
+        if self._primed is not None:
+            # a prefetched-but-unused batch of the old order is dropped: give its sampler-clock tick back so the
+            # pipelined schedule draws exactly the samples of the sequential one
+            self.engine.sample_clock_dev -= 1
+        self._primed = None
+        torch.cuda.synchronize()
+
+    def _dispatch(self, prefix, key, body):
+        """One launch unit -- a single step, or k pipelined ones -- in the form the gradient exchange allows: the whole unit one
+        hipGraph (no hook: key `prefix`) | data parallel with a capturable hook: exchange and optimizer inside the graph too, once
+        per step (`prefix`_dp) | forward + backward graph (`prefix`_fb), eager hook, ("opt",) graph.
+        body(step, local_adam, tail) issues the steps: `step` is the epilogue's increment of the optimizer step counter,
+        local_adam says whether the backward pass applies clip + Adam itself, and tail() is called behind every step."""
+        local_adam, in_graph = self.grad_hook is None, self._dp_in_graph()
+        step = 1 if local_adam or (in_graph and self._dp_step_early) else 0
+
+        def tail():
+            if in_graph:
+                self.grad_hook(self)          # ncclAllReduce on the engine stream, recorded in the graph
+                self._optimize(advanced=bool(step))
+
+        self._run((prefix + ("" if local_adam else "_dp" if in_graph else "_fb"),) + key + (self._adj_version(),),
+                  lambda: body(step, local_adam, tail))
+        if not (local_adam or in_graph):
+            self.grad_hook(self)              # all-reduce of engine.grads (ordered by stream events)
+            self._run(("opt",), self._optimize)
+
+    def _prime(self, n):
+        """Fill the pipeline: the data chain (staging, sampling, layer-0 gather + mean) of the first step, into parity 0."""
+        if self._primed == n:
+            return
         e = self.engine
-        local_adam = self.grad_hook is None
-        in_graph = self._dp_in_graph()
-        fused = local_adam or in_graph
+        self._drop_prefetched()
+        self._pipe_parity = 0
+        roots, rows, samples, support = self._sample_roots(n, 0)
+        self_all, neighs = self._layer0_inputs(samples, support, rows)
+        means0 = self.aggregators[0].prefetch(self_all, neighs, tag=0) if self_all is not None else None
+        e.advance(clock=1, cursor=self._cursor, cursor_delta=n)
+        self._prefetched[(n, 0)] = (roots, (samples, support, means0))   # static views of persistent buffers
+        e.sync()
+        self._primed = n
 
-        fusable = self._fanout_fusable()
+    def _pipelined_steps(self, n, k):
+        """k consecutive pipelined steps as ONE hipGraph launch (k even, or 1); the pipeline is primed.
 
-        def sample_next(parity):
-            roots, n_roots = self._roots(B, parity=parity)
-            self._parity = parity
-            if fusable:
-                # the edge-pair batch and the negatives are staged by the fan-out sampler launch itself (one launch, and
-                # one that can ride in the optimizer launch)
-                stage = ("unsup", self._pairs, self._cursor, B, self._neg_cdf, self._neg_guide, self._guide_bits,
-                         self.neg_sample_size, self.neg_seed)
-                samples, support = self._sample_phase(roots, n_roots, parity, stage=stage)
-            else:
-                self._stage_negatives(roots, B, pairs=self._pairs, cursor=self._cursor)
-                samples, support = self._sample_phase(roots, n_roots, parity)
-            return roots, n_roots, samples, support
-
-        if self._primed != B:
-            self._pipe_parity = 0
-            roots, n_roots, samples, support = sample_next(0)
-            self_all, neighs = self._layer0_inputs(samples, support, n_roots)
-            means0 = self.aggregators[0].prefetch(self_all, neighs, tag=0) if self_all is not None else None
-            e.advance(clock=1, cursor=self._cursor, cursor_delta=B)
-            self._prefetched[(B, 0)] = (roots, n_roots, (samples, support, means0))
-            e.sync()
-            self._primed = B
+        Single stream: step t first samples step t+1 (one small launch, or riding in an optimizer launch), then its
+        launches carry step t+1's gather+mean waves along (horizontal fusion): no cross-stream dependency.  Buffers alternate by
+        parity; the batches, samples and updates are exactly those of the sequential schedule.  (A second-stream fork/join
+        pipeline and a forked gather branch beside the all-reduce were built and measured in rounds 2-3 -- 152-162 us against
+        118, 149.9 against 147.9 -- and removed in round 4: benchmarks/variants/README.md.)"""
+        e = self.engine
         p0 = self._pipe_parity
+        fused = self.grad_hook is None or self._dp_in_graph()
+        assert fused or k == 1
         per_root = 1
         for f in self.num_samples[:0:-1]:
             per_root *= f
-        # inside a multi-step graph the sampler of the step after next rides in this step's optimizer launch
-        ride = self.sampler_rides and fused and k > 1 and fusable and per_root <= 512
+        # sampler-in-optimizer-launch: inside a multi-step graph the sampler of the step after next rides in this step's
+        # optimizer launch.  The device counters are advanced BEFORE that launch -- by the fused tail launch, the folded
+        # epilogue or the early epilogue of the backward pass
+        ride = self.sampler_rides and fused and k > 1 and self._fanout_fusable() and per_root <= 512
 
-        def body():
-            p = p0
-            staged = None
+        def body(step, local_adam, tail):
+            p, staged = p0, None
             for j in range(k):
                 q = 1 - p
                 if staged is None:
-                    staged = sample_next(q)                    # standalone sampler launch (first step of a graph)
-                roots_q, n_roots_q, samples, support = staged
-                self_all, neighs = self._layer0_inputs(samples, support, n_roots_q)
+                    staged = self._sample_roots(n, q)               # standalone sampler launch (first step of a graph)
+                roots_q, rows_q, samples, support = staged
+                self_all, neighs = self._layer0_inputs(samples, support, rows_q)
                 means_q, jobs = self.aggregators[0].prefetch_jobs(self_all, neighs, tag=q)
                 staged = None
                 if ride and j + 1 < k:
-                    # by the time the optimizer launch runs, this step's own id buffers (parity p) are free and the epilogue
-                    # has advanced the sampler clock and the pair cursor: the draws are those of the standalone launch
-                    e._defer_sampler = True
-                    try:
-                        staged = sample_next(p)
-                    finally:
-                        e._defer_sampler = False
+                    # by the time the optimizer launch runs, this step's own id / label buffers (parity p) are free and the
+                    # sampler clock and the epoch cursor have been advanced: the draws are those of the standalone launch
+                    with e.deferring_sampler():
+                        staged = self._sample_roots(n, p)
                     if e._deferred_sampler is None:
                         raise ops._lib.GraphsageAmdError("sampler did not take the one-launch fan-out path")
-                self._prefetched[(B, q)] = (roots_q, n_roots_q, (samples, support, means_q))
-                roots, n_roots, pre = self._prefetched[(B, p)]
+                self._prefetched[(n, q)] = (roots_q, (samples, support, means_q))
+                roots, pre = self._prefetched[(n, p)]
                 self._parity = p
-                tail_jobs = []
-                if self._lp_tail_ok() and self.cogather_lp_tail > 0:
-                    # three-launch form (layer-0 forward | fused link-prediction tail | weight gradients): the tail is long and
-                    # thin (66 main workgroups), the rest of the chip streams its share of the gather at the full rate
-                    f_fwd, f_tail = self.cogather_lp_fwd, self.cogather_lp_tail + self.cogather_lp_neg
-                    fwd_jobs, rest = ops.split_gather_jobs(jobs, f_fwd)
-                    tail_jobs, wgrad_jobs = ops.split_gather_jobs(rest, min(1.0, f_tail / max(1e-6, 1.0 - f_fwd)))
-                else:
-                    fwd_jobs, wgrad_jobs = ops.split_gather_jobs(jobs, self.cogather_split)
-                z_jobs = []
-                if not tail_jobs and self.cogather_z > 0 and len(self.num_samples) > 1 and not self._lp_tail_ok():
-                    # the last layer's lean launch (gs_sage_tail_z) leaves most of the chip idle: a share rides there at
-                    # the full HBM rate
-                    wgrad_jobs, z_jobs = ops.split_gather_jobs(wgrad_jobs, max(0.0, 1.0 - self.cogather_z / max(1e-6, 1.0 - self.cogather_split)))
-                epilogue = dict(step=1 if local_adam else 0, clock=1, cursor=self._cursor, cursor_delta=B)
-                self._forward_unsup(roots, B, n_roots, True, prefetched=pre, side_jobs=fwd_jobs, epilogue=epilogue, z_jobs=z_jobs,
-                                    tail_jobs=tail_jobs)
-                self._backward_unsup(B, n_roots, fuse_adam=local_adam, wgrad_jobs=wgrad_jobs, epilogue=epilogue)
+                # the next step's gather is split between this step's big launches: they are latency-bound, so the HBM-bound
+                # gather waves back-fill their idle slots
+                shares = self._gather_shares(jobs)
+                # (fused-tail supervised models, opt-in: the riding sampler leaves with the weight-gradient launch instead --
+                #  Engine.launch_wgrads -- and the tail launch copies this step's ids for the weight gradients, whose id buffer
+                #  the sampler refills)
+                e._sampler_to_wgrad = self._sampler_to_wgrad_ok(jobs)
+                try:
+                    self._step_fwd_bwd(n, roots, pre, shares, dict(step=step, clock=1, cursor=self._cursor, cursor_delta=n),
+                                       local_adam)
+                finally:
+                    if e._sampler_to_wgrad:
+                        self._wgrad_sampler_seen = bool(e.last_wgrad_sampler)   # (tests: did the sampler leave with that launch?)
+                    e._sampler_to_wgrad = False
                 if e._deferred_sampler is not None:
                     raise ops._lib.GraphsageAmdError("deferred sampler was not consumed by the optimizer launch")
-                if in_graph:
-                    # backward | ncclAllReduce (recorded in the graph) | clip + Adam
-                    self.grad_hook(self)
-                    self._optimize()
+                tail()
                 p = q
 
-        self._run(("updtrain" if local_adam else ("updtrain_dp" if in_graph else "updtrain_fb"), B, k, p0,
-                   self._adj_version()), body)
-        if not fused:
-            assert k == 1
-            self.grad_hook(self)
-            self._run(("opt",), self._optimize)
+        self._dispatch(self._pipe_key, (n, k, p0), body)
         if k % 2 == 1:
             self._pipe_parity = 1 - p0
+
+    def train_step_device(self, n, fetch=False):
+        """One training step on the next n ids / pairs of the device-resident epoch: the step's launches carry the data chain
+        of the step after it (batch staging + fan-out sampling + layer-0 gather-means; HBM-bound, needs no weights)."""
+        self._prime(n)
+        self._pipelined_steps(n, 1)
+        return self._fetch(n) if fetch else None
+
+    def train_steps_device(self, n, steps, steps_per_launch=8):
+        """`steps` training steps on the device-resident epoch; on a single GPU (or with the exchange in the graph)
+        `steps_per_launch` consecutive steps are replayed per hipGraph launch (amortises the launch gap and keeps the GPU fed
+        when the host is slow or shared; the schedule and results are unchanged)."""
+        k = steps_per_launch - (steps_per_launch % 2)
+        if not (self._multi_step_ok() and self.use_graphs and k >= 2):
+            for _ in range(steps):
+                self.train_step_device(n)
+            return
+        done = 0
+        while done < steps:
+            # multi-step graphs always start at buffer parity 0 (one captured graph per length); single steps realign the
+            # parity.  A shorter tail (the drivers replay print_every - 1 steps between two printed iterations) takes the
+            # largest even length that fits, so it still is one launch with the sampler riding in the optimizer launches.
+            rem = steps - done
+            kk = min(k, rem - (rem % 2))
+            if self._primed == n and self._pipe_parity == 0 and kk >= 2:
+                self._pipelined_steps(n, kk)
+                done += kk
+            else:
+                self.train_step_device(n)
+                done += 1
+        self._check_exchange()
 
     # ------------------------------------------------------------------------------ sample (S2)
     def ids_buffer(self, batch_size, layer_infos=None, parity=None):
@@ -929,30 +1063,12 @@ class SampleAndAggregate(object):
         e = self.engine
         # the dropout rate and the schedule choices are baked into the captured launches
         key = tuple(key) + (self._dropout_rate(), self._schedule_signature())
-        g = self._graphs.get(key)
-        if g is not None:
-            for name, val in self._graph_outputs[key].items():
+        outs = self._graph_outputs.get(key)
+        if outs is not None:
+            for name, val in outs.items():
                 setattr(self, name, val)
-            g.launch()
-            return
-        if not self.use_graphs or key not in self._warm or self._needs_host_rng():
-            fn()
-            self._warm.add(key)
-            return
-        g = ops.Graph(e.stream)
-        g.begin()
-        try:
-            fn()
-        except Exception:
-            try:                      # leave the stream out of capture mode, or every later launch on it fails too
-                g.end()
-            except Exception:
-                pass
-            raise
-        g.end()
-        self._graphs[key] = g
-        self._graph_outputs[key] = {name: getattr(self, name) for name in self._OUT_ATTRS if hasattr(self, name)}
-        g.launch()
+        if _run_captured(self._graphs, self._warm, key, fn, e.stream, lambda: self.use_graphs and not self._needs_host_rng()):
+            self._graph_outputs[key] = {name: getattr(self, name) for name in self._OUT_ATTRS if hasattr(self, name)}
 
     def _feed_dropout(self, feed_dict):
         """feed_dict[placeholders['dropout']] (supervised_train.py:117; validation feeds omit it = 0): every layer
@@ -1197,32 +1313,12 @@ class Node2VecModel(object):
         """`steps` steps on the attached pairs, `steps_per_launch` per graph launch (eager on first use of a length,
         captured on the second, replayed afterwards)."""
         assert self._pairs is not None, "attach_device_pairs first"
-        e = self.engine
         b = self._buffers(B, "d")
         done = 0
         while done < steps:
             k = max(1, min(int(steps_per_launch), steps - done))
-            key = (int(B), k)
-            g = self._graphs.get(key)
-            if g is not None:
-                g.launch()
-            elif not self.use_graphs or key not in self._warm:
-                self._device_steps(b, k)
-                self._warm.add(key)
-            else:
-                g = ops.Graph(e.stream)
-                g.begin()
-                try:
-                    self._device_steps(b, k)
-                except Exception:
-                    try:                      # leave the stream out of capture mode, or every later launch on it fails too
-                        g.end()
-                    except Exception:
-                        pass
-                    raise
-                g.end()
-                self._graphs[key] = g
-                g.launch()
+            _run_captured(self._graphs, self._warm, (int(B), k), lambda: self._device_steps(b, k), self.engine.stream,
+                          lambda: self.use_graphs)
             done += k
         return self._fetch(b) if fetch else None
 

@@ -92,29 +92,11 @@ class SupervisedGraphsage(SampleAndAggregate):
         `epilogue`: the step's device-counter increments; when the fused tail launch runs it advances them itself
         (and `_backward` then skips the separate epilogue launch)."""
         e = self.engine
-        self.reset_tapes()
         del self.node_pred._saved[:]
-        if prefetched is None:
-            prefetched = self._data_phase(batch, n, getattr(self, "_parity", 0), stage=getattr(self, "_pending_stage", None))
-        samples1, support_sizes1, means0 = prefetched
         C = self.num_classes
-        # the fused tail needs the hops of layer 0 in ONE contiguous buffer (model.sample on the model's id buffer);
-        # anything else takes the per-operator schedule
-        contiguous = all(b.data_ptr() == a.data_ptr() + 4 * a.numel() for a, b in zip(samples1[:-1], samples1[1:]))
-        self._tail_used = bool(train and contiguous and self._tail_ok())
         agg0 = self.aggregators[0]
-        agg0.l1_means_out = None
-        if self._tail_used and e.fused_l1_means and self.aggregator_type == "mean":
-            # `tail_means` exists before the layer-0 launch: where that is the tiled concat form it writes the layer-1 neighbor
-            # means from its finished tiles (agg0.l1_means_written) and the tail's helpers load them
-            agg0.l1_means_out = e.ws_mat("tail_means", n, 2 * self.dims[1])
-        out, _ = self.aggregate(samples1, [self.features], self.dims, self.num_samples, support_sizes1, batch_size=n,
-                                aggregators=self.aggregators, concat=self.concat, model_size=self.model_size,
-                                layer0_means=means0, layer0_side_jobs=side_jobs,
-                                _stop_after_layer=0 if self._tail_used else None)
-        self.samples1 = samples1
-        if self._tail_used and self._tape[0][0] != "batched":
-            raise ops._lib.GraphsageAmdError("fused tail needs the contiguous id buffer (model.sample on ids_buffer)")
+        out, self._tail_used = self._forward_layers(batch, n, prefetched, lambda: train and self._tail_ok(),
+                                                    self.aggregator_type == "mean", side_jobs)
         self._loss_rows = e.ws_f32("loss_rows", n)
         self.preds = e.ws_mat("preds", n, C)
         self._dlogits = e.ws_mat("dlogits", n, C)
@@ -134,20 +116,12 @@ class SupervisedGraphsage(SampleAndAggregate):
             self._tail_dh0 = e.ws_mat((self.name, "d_hidden", 0), h0.rows, h0.d)
             self._tail_h0 = h0
             self._head_fused = True
-            counters = []
-            self._tail_step_advanced = False
+            counters = self._epilogue_counters(epilogue) if epilogue else []
+            self._tail_step_advanced = bool(epilogue and epilogue.get("step"))
             # hand-over state of the launch's helper workgroups: private to this model (its engine stream)
             # (one buffer per batch size: its layout depends on n, and stale granules of another layout must never be met)
             self._tail_sync = e.ws_i32(("tail_sync", self.name, n, O1), ops.tail_sync_words(n, O1))
             self._tail_sync_n = n
-            if epilogue:
-                if epilogue.get("step"):
-                    counters.append((e.step_dev, epilogue["step"]))
-                    self._tail_step_advanced = True
-                if epilogue.get("clock"):
-                    counters.append((e.sample_clock_dev, epilogue["clock"]))
-                if epilogue.get("cursor") is not None and epilogue.get("cursor_delta"):
-                    counters.append((epilogue["cursor"], epilogue["cursor_delta"]))
             # split form: the z helpers as their own lean launch (its riders stream at the full HBM rate), then the
             # row-group workgroups; the tail's gather share is divided between the two launches
             jobs_z, jobs_m = [], tail_jobs
@@ -185,15 +159,7 @@ class SupervisedGraphsage(SampleAndAggregate):
                 ops.class_loss(self.node_preds, labels, n, C, self.sigmoid_loss, self._loss_rows, self.preds,
                                self._dlogits, stream=e.stream)                                               # :111-126
         # loss = weight decay terms (:104-108) + mean classification loss (the mean is added by the step epilogue)
-        self._loss_accumulate = False
-        if self.weight_decay != 0.0:
-            first = True
-            for v in e.variables:
-                if v.decay:
-                    ops.call("gs_sumsq_scaled", v.value.ptr, v.size, 0.5 * self.weight_decay,
-                             self.loss_dev.data_ptr(), 0 if first else 1, e.stream)
-                    first = False
-            self._loss_accumulate = not first
+        self._weight_decay_loss([v for v in e.variables if v.decay], 0.5 * self.weight_decay)
 
     def _backward(self, n, fuse_adam, wgrad_jobs=None, epilogue=None):
         """Reverse of _forward.  Every weight gradient of the pass is ONE grouped launch; the slab reduction
@@ -202,18 +168,9 @@ class SupervisedGraphsage(SampleAndAggregate):
         e.begin_backward()
         if getattr(self, "_tail_used", False):
             # the fused tail launch already produced every input gradient; queue the weight gradients it feeds
-            a1 = self.aggregators[1]
-            o = self.dims[2]
-            h0 = self._tail_h0
             e.wgrad(self.node_pred.vars['weights'], self.outputs1, None, self._dlogits, 0, n)
             e.bgrad(self.node_pred.vars['bias'], self._dlogits, n, self.num_classes)
-            if self.aggregator_type == "gcn":
-                e.wgrad(a1.vars['weights'], self._tail_means, None, self._tail_dz, 0, n)   # means = (sum neigh + self) / (s + 1)
-            else:
-                e.wgrad(a1.vars['self_weights'], h0.rows_slice(0, n), None, self._tail_dz, 0, n)
-                e.wgrad(a1.vars['neigh_weights'], self._tail_means, None, self._tail_dz, o, n)
-            mode, agg0, rows, offsets, outs = self._tape[0]
-            agg0.backward_hops(self._tail_dh0, True, embed_sink=None)
+            self._queue_tail_wgrads(n, self._tail_dz)
             e.finish_backward(self.weight_decay, fuse_adam=fuse_adam, lr=self.learning_rate, clip=5.0, side_jobs=wgrad_jobs,
                               loss=(self._loss_rows, n, 1.0 / n, self.loss_dev, self._loss_accumulate) if epilogue is not None else None,
                               step_offset=0 if self._tail_step_advanced else 1)
@@ -244,15 +201,6 @@ class SupervisedGraphsage(SampleAndAggregate):
     def _epilogue(self, n, **counters):
         self.engine.advance(loss_rows=self._loss_rows, n=n, loss_out=self.loss_dev, accumulate=self._loss_accumulate,
                             **counters)
-
-    def _optimize(self, advanced=False):
-        """Data-parallel path: clip_by_value(+-5) + Adam (:96-99) after the RCCL all-reduce.  The local gradient
-        is that of the local batch mean; the hook sums over ranks and grad_scale divides by world_size.
-        advanced: the step counter was already incremented by an earlier launch of this step."""
-        e = self.engine
-        e.adam(self.learning_rate, clip=5.0, grad_scale=1.0 / self.world_size, step_offset=0 if advanced else 1)
-        if not advanced:
-            e.advance(step=1)
 
     # ------------------------------------------------------------------------------ feeds
     def _stage_feed(self, feed_dict):
@@ -289,39 +237,23 @@ class SupervisedGraphsage(SampleAndAggregate):
         return self._fetch(n) if fetch else None
 
     def _train_on_device(self, batch_dev, labels_dev, n, fetch=True, prologue=None, cursor=None, key="train"):
-        e = self.engine
-        fused = self.grad_hook is None
-        in_graph = self._dp_in_graph()
-
-        def fwd_bwd():
+        """One non-pipelined step on a staged batch; `cursor`: the epoch cursor the step epilogue advances by n."""
+        def body(step, local_adam, tail):
             if prologue is not None:
                 prologue()
-            ep = dict(step=1 if (fused or in_graph) else 0, clock=1, cursor=cursor, cursor_delta=n if cursor is not None else 0)
-            self._forward(batch_dev, labels_dev, n, train=True, epilogue=ep)
-            self._backward(n, fuse_adam=fused, epilogue=ep)
-            if in_graph:
-                self.grad_hook(self)          # ncclAllReduce on the engine stream, recorded in the graph
-                self._optimize(advanced=True)
+            ep = dict(step=step, clock=1, cursor=cursor, cursor_delta=n if cursor is not None else 0)
+            self._step_fwd_bwd(n, (batch_dev, labels_dev), None, self._NO_SHARES, ep, local_adam)
+            tail()                # (_dispatch: a body calls tail() behind every step it issues)
 
-        if fused or in_graph:
-            self._run((key if fused else key + "_dp", n, self._adj_version()), fwd_bwd)     # the whole step: one hipGraph
-        else:
-            self._run((key + "_fb", n, self._adj_version()), fwd_bwd)
-            self.grad_hook(self)              # RCCL all-reduce of engine.grads (ordered by stream events)
-            self._run(("opt",), self._optimize)
+        self._dispatch(key, (n,), body)
         return self._fetch(n) if fetch else None
 
+    def _handover_error(self):
+        err = ops.tail_sync_error(self._tail_sync, self._tail_sync_n) if getattr(self, "_tail_sync", None) is not None else 0
+        return err, "fused tail launch", "row-group"
+
     def _fetch(self, n):
-        self.engine.sync()
-        if getattr(self, "_tail_sync", None) is not None:
-            err = ops.tail_sync_error(self._tail_sync, self._tail_sync_n)
-            if err:
-                raise ops._lib.GraphsageAmdError(
-                    "fused tail launch: hand-over between its workgroups failed (flags %d: 1 = a row-group workgroup "
-                    "gave up waiting for its helpers, 2 = unexpected arrival count); results since the last fetch are "
-                    "invalid -- set model.fuse_tail = False to use the per-operator schedule" % err)
-        if hasattr(self.grad_hook, "check"):
-            self.grad_hook.check()            # peer-store exchange: a bounded device-side wait that tripped
+        self._sync_checked()
         loss = float(self.loss_dev.item())
         preds = self.preds.view()[:n].detach().cpu().numpy()
         return loss, preds
@@ -340,15 +272,7 @@ class SupervisedGraphsage(SampleAndAggregate):
         torch.cuda.synchronize()
 
     def set_epoch_order(self, order):
-        self.engine.sync()  # steps still queued on the engine stream read the old order / cursor
-        self._order.copy_(torch.from_numpy(np.ascontiguousarray(order, dtype=np.int32)))
-        self._cursor.zero_()
-        if self._primed is not None:
-            # a prefetched-but-unused batch of the old order is dropped: give its sampler-clock tick back so the
-            # pipelined schedule draws exactly the samples of the sequential one
-            self.engine.sample_clock_dev -= 1
-        self._primed = None
-        torch.cuda.synchronize()
+        self._reset_epoch(self._order, np.ascontiguousarray(order, dtype=np.int32))
 
     def _drop_prefetched(self):
         """Forget the batch the pipeline has already staged (a different batch size follows, e.g. the short last batch
@@ -361,165 +285,59 @@ class SupervisedGraphsage(SampleAndAggregate):
             self._primed = None
             torch.cuda.synchronize()
 
+    # ---- the hooks of the step schedule (SampleAndAggregate, "the step schedule": the differences are listed there)
+    _pipe_key = "ptrain"
+    _dp_step_early = True
+
+    def _pipelined(self):
+        return getattr(self, "pipeline", True) and self._dropout_rate() == 0
+
+    def _multi_step_ok(self):
+        return self._pipelined() and super(SupervisedGraphsage, self)._multi_step_ok()
+
     def train_step_device(self, n, fetch=False):
-        """One training step on the next n ids of the device-resident epoch order.
-
-        Pipelined (default): the data chain of step t+1 (batch/label staging + fan-out sampling + layer-0
-        gather-means; HBM-bound, needs no weights) runs on a second HIP stream concurrently with the compute chain
-        of step t (MFMA-bound), as the two branches of ONE fork/join hipGraph.  Buffers alternate by parity; the
-        batches, samples and updates are exactly those of the sequential schedule."""
+        """One training step on the next n ids of the device-resident epoch order: pipelined (the shared schedule), or -- with
+        `pipeline` off or dropout on -- the sequential form below (graph key "dtrain")."""
+        if self._pipelined():
+            return super(SupervisedGraphsage, self).train_step_device(n, fetch)
+        # sequential form: batch selection + label gather ride along with the step's own fused sampler launch
         e = self.engine
-        if not getattr(self, "pipeline", True) or self._dropout_rate() > 0:
-            self._parity = 0
-            batch_dev = self.ids_buffer(n)[0][:n]
-            labels_dev = e.ws_mat(("labels", 0), n, self.num_classes)
+        self._parity = 0
+        batch_dev = self.ids_buffer(n)[0][:n]
+        labels_dev = e.ws_mat(("labels", 0), n, self.num_classes)
 
-            def stage():   # batch selection + label gather ride along with the fused sampler launch
-                self._pending_stage = (self._order, self._cursor, self.label_table, labels_dev)
+        def stage():
+            self._pending_stage = (self._order, self._cursor, self.label_table, labels_dev)
 
-            return self._train_on_device(batch_dev, labels_dev, n, fetch, prologue=stage, cursor=self._cursor,
-                                         key="dtrain")
-        fused = self.grad_hook is None or self._dp_in_graph()
-        data = self._data_fn(n)
-        if self._primed != n:                       # fill the pipeline: data chain of the first step
-            self._drop_prefetched()
-            self._pipe_parity = 0
-            data(0)
-            e.sync()
-            self._primed = n
-        self._pipelined_steps(n, 1, data, fused)
-        return self._fetch(n) if fetch else None
+        return self._train_on_device(batch_dev, labels_dev, n, fetch, prologue=stage, cursor=self._cursor, key="dtrain")
 
-    def _data_fn(self, n):
+    def _sample_roots(self, n, parity):
+        batch = self.ids_buffer(n, parity=parity)[0][:n]
+        labels = self.engine.ws_mat(("labels", parity), n, self.num_classes)
+        samples, support = self._sample_phase(batch, n, parity, stage=(self._order, self._cursor, self.label_table, labels))
+        return (batch, labels), n, samples, support
+
+    def _gather_shares(self, jobs):
+        if jobs and self.cogather_tail > 0 and self._tail_ok():
+            # the fused tail launch keeps only n/16 CUs busy: the rest of the chip streams a share of the gather
+            f_fwd, f_tail = self.rider_shares(jobs, self.dims[1] if self.aggregator_type == "gcn" else 2 * self.dims[1])
+            fwd_jobs, rest = ops.split_gather_jobs(jobs, f_fwd)
+            tail_jobs, wgrad_jobs = ops.split_gather_jobs(rest, min(1.0, f_tail / max(1e-6, 1.0 - f_fwd)))
+            return fwd_jobs, tail_jobs, wgrad_jobs, []
+        fwd_jobs, wgrad_jobs = ops.split_gather_jobs(jobs, self.cogather_split)
+        return fwd_jobs, [], wgrad_jobs, []
+
+    def _step_fwd_bwd(self, n, roots, prefetched, shares, epilogue, local_adam):
+        batch, labels = roots
+        fwd_jobs, tail_jobs, wgrad_jobs, _ = shares
+        self._forward(batch, labels, n, train=True, prefetched=prefetched, side_jobs=fwd_jobs, epilogue=epilogue,
+                      tail_jobs=tail_jobs)
+        self._backward(n, fuse_adam=local_adam, wgrad_jobs=wgrad_jobs, epilogue=epilogue)
+
+    def _sampler_to_wgrad_ok(self, jobs):
         e = self.engine
-
-        def data(parity):
-            batch_dev = self.ids_buffer(n, parity=parity)[0][:n]
-            labels_dev = e.ws_mat(("labels", parity), n, self.num_classes)
-            pre = self._data_phase(batch_dev, n, parity, stage=(self._order, self._cursor, self.label_table, labels_dev))
-            e.advance(clock=1, cursor=self._cursor, cursor_delta=n)
-            self._prefetched[(n, parity)] = (batch_dev, labels_dev, pre)   # static views of persistent buffers
-        return data
-
-    def _pipelined_steps(self, n, k, data, fused):
-        """k consecutive pipelined steps as ONE hipGraph launch (k even, or 1).
-
-        Single stream: step t first samples step t+1 (one small launch, or riding in an optimizer launch), then its
-        launches carry step t+1's gather+mean waves along (horizontal fusion): no cross-stream dependency.  (A second-stream
-        fork/join pipeline and a forked gather branch beside the all-reduce were built and measured in rounds 2-3 -- 152-162 us
-        against 118, 149.9 against 147.9 -- and removed in round 4: benchmarks/variants/README.md.)"""
-        e = self.engine
-        p0 = self._pipe_parity
-        mode = "fused"
-        in_graph = self._dp_in_graph()          # `fused` is then True as well: the whole DP step is one graph
-        local_adam = self.grad_hook is None
-
-        def compute(p, side_jobs=None, epilogue=None):
-            batch_dev, labels_dev, pre = self._prefetched[(n, p)]
-            self._parity = p
-            # the next step's gather is split between this step's two big GEMM launches (layer-0 forward, grouped
-            # weight gradient): both are latency-bound, so the HBM-bound gather waves back-fill their idle slots
-            if side_jobs and self.cogather_tail > 0 and self._tail_ok():
-                # the fused tail launch keeps only n/16 CUs busy: the rest of the chip streams a share of the gather
-                f_fwd, f_tail = self.rider_shares(side_jobs, self.dims[1] if self.aggregator_type == "gcn" else 2 * self.dims[1])
-                fwd_jobs, rest = ops.split_gather_jobs(side_jobs, f_fwd)
-                tail_jobs, wgrad_jobs = ops.split_gather_jobs(rest, min(1.0, f_tail / max(1e-6, 1.0 - f_fwd)))
-            else:
-                fwd_jobs, wgrad_jobs = ops.split_gather_jobs(side_jobs, self.cogather_split)
-                tail_jobs = []
-            self._forward(batch_dev, labels_dev, n, train=True, prefetched=pre, side_jobs=fwd_jobs, epilogue=epilogue,
-                          tail_jobs=tail_jobs)
-            self._backward(n, fuse_adam=local_adam, wgrad_jobs=wgrad_jobs, epilogue=epilogue)
-            if in_graph:
-                self.grad_hook(self)          # ncclAllReduce on the engine stream, recorded in the graph
-                self._optimize(advanced=True)
-
-        def sample_into(parity):
-            batch = self.ids_buffer(n, parity=parity)[0][:n]
-            labels = e.ws_mat(("labels", parity), n, self.num_classes)
-            samples, support = self._sample_phase(batch, n, parity, stage=(self._order, self._cursor, self.label_table, labels))
-            return batch, labels, samples, support
-
-        # sampler-in-optimizer-launch: the device counters are advanced BEFORE the optimizer launch -- by the fused tail
-        # launch, or by the early epilogue of _backward (this pipeline only runs without dropout)
-        per_root = 1
-        for f in self.num_samples[:0:-1]:
-            per_root *= f
-        ride = (self.sampler_rides and mode == "fused" and (local_adam or in_graph) and fused and k > 1
-                and (self._tail_ok() or self._dropout_rate() == 0) and self._fanout_fusable() and per_root <= 512)
-
-        def body():
-            p = p0
-            staged = None
-            for j in range(k):
-                if True:
-                    q = 1 - p
-                    if staged is None:
-                        staged = sample_into(q)                    # standalone sampler launch (first step of a graph)
-                    batch_q, labels_q, samples, support = staged
-                    self_all, neighs = self._layer0_inputs(samples, support, n)
-                    means_q, jobs = self.aggregators[0].prefetch_jobs(self_all, neighs, tag=q)
-                    staged = None
-                    if ride and j + 1 < k:
-                        # the sampler of the step AFTER the next one rides in this step's optimizer launch: by then
-                        # this step's own id / label buffers (parity p) are free, and the tail launch has already
-                        # advanced the sampler clock and the epoch cursor -- the draws are those of the standalone launch
-                        e._defer_sampler = True
-                        try:
-                            staged = sample_into(p)
-                        finally:
-                            e._defer_sampler = False
-                        if e._deferred_sampler is None:
-                            raise ops._lib.GraphsageAmdError("sampler did not take the one-launch fan-out path")
-                    self._prefetched[(n, q)] = (batch_q, labels_q, (samples, support, means_q))
-                    # (fused-tail models: that sampler leaves with the weight-gradient launch -- Engine.launch_wgrads -- and
-                    #  the tail launch copies this step's ids for the weight gradients, whose id buffer the sampler refills)
-                    e._sampler_to_wgrad = bool(self.sampler_in_wgrad and e._deferred_sampler is not None and self._tail_ok()
-                                               and sum(jb.n * jb.s * jb.d * 4 for jb in jobs) <= self.sampler_in_wgrad_max_bytes)
-                    try:
-                        compute(p, side_jobs=jobs, epilogue=dict(step=1 if fused else 0, clock=1, cursor=self._cursor,
-                                                                 cursor_delta=n))
-                    finally:
-                        if e._sampler_to_wgrad:
-                            self._wgrad_sampler_seen = bool(e.last_wgrad_sampler)   # (tests: did the sampler leave with that launch?)
-                        e._sampler_to_wgrad = False
-                    if e._deferred_sampler is not None:
-                        raise ops._lib.GraphsageAmdError("deferred sampler was not consumed by the optimizer launch")
-                p = 1 - p
-
-        key = ("ptrain" if local_adam else ("ptrain_dp" if in_graph else "ptrain_fb"), mode, n, k, p0, self._adj_version())
-        self._run(key, body)
-        if not fused:
-            assert k == 1
-            self.grad_hook(self)              # RCCL all-reduce of engine.grads (ordered by stream events)
-            self._run(("opt",), self._optimize)
-        if k % 2 == 1:
-            self._pipe_parity = 1 - p0
-
-    def train_steps_device(self, n, steps, steps_per_launch=8):
-        """`steps` training steps on the device-resident epoch; on a single GPU `steps_per_launch` consecutive steps
-        are replayed per hipGraph launch (amortises the launch gap; the schedule and results are unchanged)."""
-        fused = self.grad_hook is None or self._dp_in_graph()
-        k = steps_per_launch - (steps_per_launch % 2)
-        if not (getattr(self, "pipeline", True) and self._dropout_rate() == 0 and fused and self.use_graphs and k >= 2):
-            for _ in range(steps):
-                self.train_step_device(n)
-            return
-        done = 0
-        data = self._data_fn(n)
-        while done < steps:
-            # multi-step graphs always start at buffer parity 0 (one captured graph per length); single steps realign the
-            # parity.  A shorter tail (the drivers replay print_every - 1 steps between two printed iterations) takes the
-            # largest even length that fits, so it still is one launch with the sampler riding in the optimizer launches.
-            rem = steps - done
-            kk = min(k, rem - (rem % 2))
-            if self._primed == n and self._pipe_parity == 0 and kk >= 2:
-                self._pipelined_steps(n, kk, data, fused)
-                done += kk
-            else:
-                self.train_step_device(n)
-                done += 1
-        self._check_exchange()
+        return bool(self.sampler_in_wgrad and e._deferred_sampler is not None and self._tail_ok()
+                    and sum(jb.n * jb.s * jb.d * 4 for jb in jobs) <= self.sampler_in_wgrad_max_bytes)
 
     def predict(self):
         """sigmoid / softmax of the logits (supervised_models.py:122-126); filled by the last step."""

@@ -1,7 +1,7 @@
 """-m gpu: oracle parity of every TIMED BASELINE configuration at its own shapes, through the path bench.py times.
 
   * configs[3] (`aux.unsupervised`): unsupervised graphsage_mean at B = 512, fan-out 25x10, F = 602, dims 128/128,
-    20 negatives through SampleAndAggregate.train_step(s)_device -> _pipelined_steps_unsup (device-resident pairs,
+    20 negatives through SampleAndAggregate.train_step(s)_device -> _pipelined_steps (device-resident pairs,
     hipGraph capture/replay, next step's gather riding in this step's launches): pairs, negatives and every sampled id
     bit-exact vs oracle/sampler_hash.py, then orc.unsupervised_fwd_bwd (models.py:332-405, prediction.py:68-110
     restated) on exactly those ids: loss, MRR, affinities, every gradient, parameters after clip + Adam at 1e-4.

@@ -120,7 +120,7 @@ def test_native_rccl_hook_in_graph_single_rank(dev):
         loss, preds = model._fetch(32)
         outs.append((loss, preds.copy(), eng.get_engine().params.cpu().numpy().copy()))
         if dp:
-            assert any(k[0] == "ptrain_dp" and k[3] == 2 for k in model._graphs), list(model._graphs)   # 2-step DP graphs
+            assert any(k[0] == "ptrain_dp" and k[2] == 2 for k in model._graphs), list(model._graphs)   # 2-step DP graphs
             hook.close()
     np.testing.assert_allclose(outs[0][0], outs[1][0], rtol=1e-5)
     np.testing.assert_allclose(outs[0][2], outs[1][2], rtol=1e-5, atol=1e-7)
@@ -169,7 +169,7 @@ def test_dp_in_graph_schedule_single_rank_matches_and_unsup_in_graph(dev):
         loss, preds = model._fetch(32)
         gouts.append((loss, eng.get_engine().params.cpu().numpy().copy()))
         if dp:
-            assert any(k[0] == "ptrain_dp" and k[3] == 2 for k in model._graphs), list(model._graphs)
+            assert any(k[0] == "ptrain_dp" and k[2] == 2 for k in model._graphs), list(model._graphs)
             hook.close()
     np.testing.assert_allclose(gouts[0][0], gouts[1][0], rtol=1e-5)
     np.testing.assert_allclose(gouts[0][1], gouts[1][1], rtol=1e-5, atol=1e-7)
