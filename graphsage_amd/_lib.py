@@ -16,6 +16,7 @@ LAW_IID, LAW_REFERENCE, LAW_DISTINCT = 0, 1, 2      # GS_LAW_* (sampling law of 
 SAMPLER_LAWS = {"iid": LAW_IID, "reference": LAW_REFERENCE, "distinct": LAW_DISTINCT}
 GS_PEER_HANDLE_BYTES = 64
 GS_ABI_VERSION = 12     # must equal GS_ABI_VERSION of include/graphsage_amd.h (struct layouts below mirror that header)
+WGRAD_TILED3_FORM_DEFAULT = 1    # initial value of g_wgrad_tiled3_form (csrc/gs_split.hip; gs_set_wgrad_tiled3_form)
 
 
 class GraphsageAmdError(RuntimeError):
@@ -92,6 +93,7 @@ _PROTOS = {
     "gs_dense_wgrad_grouped_stream": [_P, c_int32, _P, c_int32, _P],
     "gs_dense_wgrad_grouped_tiled3": [_P, c_int32, _P, c_int32, _P],
     "gs_dense_wgrad_grouped_tiled3_sample": [_P, c_int32, _P, c_int32, _P, _P],
+    "gs_set_wgrad_tiled3_form": [c_int],
     "gs_sage_dense_fwd_tiled3": [_P, c_int64, _P, c_int32, _P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int, _P,
                                  _P, c_int64, _P, c_int32, _P],
     "gs_sage_dense_fwd_tiled3_means": [_P, c_int64, _P, c_int32, _P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, c_int32,
@@ -356,6 +358,12 @@ def call(name, *args):
     check(rc, name)
     if _DEBUG_SYNC and not name.startswith(("gs_capture", "gs_graph", "gs_stream", "gs_event")):
         torch.cuda.synchronize()
+
+
+def set_wgrad_tiled3_form(form):
+    """gs_set_wgrad_tiled3_form: which kernel the next gs_dense_wgrad_grouped_tiled3[_sample] launches take (0 | 1).  A host-side
+    switch that launches nothing, so it does not go through call() (the per-launch debug sync / log)."""
+    check(load().gs_set_wgrad_tiled3_form(int(form)), "gs_set_wgrad_tiled3_form")
 
 
 def ptr(t):

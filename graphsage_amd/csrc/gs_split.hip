@@ -1346,6 +1346,281 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
 #undef W3_INFLIGHT
 }
 
+// The second form of the launch above (gs_set_wgrad_tiled3_form(1)): same items, riders, slabs and MFMA sequence -- the slabs are
+// bit-identical -- but A travels like the forward's A.  In wgrad_tiled3_kernel every wave reads and cuts the whole [16 k][64 m] A
+// tile for itself (8 of its 12 two-element cuts per stage, 132 cut-VALU beside 12 MFMAs); here A is cut ONCE per workgroup:
+//   A: thread (wave w, lane) owns column m0 + lane and the k rows 4 w .. 4 w + 3 of a stage: four global_load_dword per stage
+//     (each a 256-byte row segment per wave instruction; the row base is a wave-uniform 64-bit SGPR pair, the lane adds its
+//     column), register ring of W3A_NR stages, two cuts ((k0,k1), (k2,k3): the pairs of the first form, so the pieces are the
+//     same bits), three ds_write_b64 into a [piece][m][16 k] bf16 buffer (48-byte rows, two buffers); a wave's fragments of a
+//     stage are six ds_read_b128 (2 row blocks x 3 pieces) shared by the four waves;
+//   dZ: as in the first form (raw fp32 by LDS-DMA, ring of four 8 KB slots, eight ds_read_b32 and four cuts per wave, row mask);
+//   the slice's row ids: no LDS list -- lane L of wave w holds the ids of ITS four rows of stage L (a slice has <= 64 stages), a
+//     stage's loader takes them with v_readlane (stages beyond the slice: lane 63's, valid rows whose dZ is masked).
+// Per stage and wave beside the 12 MFMAs: 6 cuts (4 dZ + 2 A) = 66 VALU, 3 piece writes, 6 + 8 fragment reads, 4 A requests,
+// 2 DMAs.  Dynamic LDS: 2 buffers x 3 pieces x 64 rows x 48 bytes = 18,432 + 4 x 8,192 = 51,200 bytes (<= 53,248: a host still
+// shares its CU with two rider workgroups).
+// Banks (tests/test_wgrad_acut_layout.py): a 16-lane group of the fragment read covers 16 distinct 16-byte units of the 64 banks;
+// the 16 lanes of a piece-write phase (rows m .. m + 15 at 48-byte pitch, one 8-byte unit each) take 32 distinct banks of 64.
+#define W3A_LDA 24         // bf16 per LDS row of an A piece plane: 16 k + 8 pad
+#define W3A_NA 2           // A piece buffers (stage s + 1 being read, stage s + 2 being written)
+#define W3A_NB 4           // raw dZ stages in flight
+#define W3A_NR 4           // A stages in flight in registers
+#define W3A_LDS_BYTES (W3A_NA * 3 * 64 * W3A_LDA * 2 + W3A_NB * W3_KS * 128 * 4)
+static_assert(W3A_LDS_BYTES <= 53248, "a host workgroup must leave room for two rider workgroups on its CU");
+static_assert(W3_MAXROWS <= 64 * W3_KS, "one lane per stage holds the slice's row ids");
+
+__global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G, const FanoutArgs F, const CoGatherS J) {
+    typedef __attribute__((address_space(3))) void* lds_ptr_t;
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int A_PLANE = 64 * W3A_LDA * 2, A_BYTES = 3 * A_PLANE, B_BYTES = W3_KS * 128 * 4, B_BASE = W3A_NA * A_BYTES;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if ((int)blockIdx.x >= G.n_items) {                             // riders: as in wgrad_tiled3_kernel
+        const int64_t r = (int64_t)blockIdx.x - G.n_items;
+        const int64_t sblocks = (F.B + 3) >> 2;
+        if (r < sblocks) {
+            const int64_t root = 4 * r + wave;
+            if (root < F.B) {
+                int32_t* ints = reinterpret_cast<int32_t*>(smem) + wave * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL);
+                sample_fanout_root<GS_FANOUT_LDS_SMALL, true>(F, root, reinterpret_cast<int32_t (*)[GS_FANOUT_LDS_SMALL]>(ints),
+                                                              reinterpret_cast<int32_t (*)[GS_LAW_COLS]>(ints + 2 * GS_FANOUT_LDS_SMALL));
+            }
+            return;
+        }
+        run_gather_item<T3_RIDER_U>(J, (r - sblocks) * 4 + wave, lane);
+        return;
+    }
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int nwg = G.n_items;                                      // XCD-aware item order: as in wgrad_tiled3_kernel
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, lcl = blockIdx.x >> 3;
+    const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lcl;
+    int pi = 0;
+    while (pi + 1 < G.n && item >= G.p[pi + 1].item_start) ++pi;
+    const Wg3Prob& q = G.p[pi];
+    const int local = item - q.item_start;
+    const int tiles = q.tiles_m * q.tiles_n;
+    const int z = local / tiles;
+    const int tt = local - z * tiles;
+    const int tile_m = tt / q.tiles_n, tile_n = tt - tile_m * q.tiles_n;
+    const int m0 = tile_m * 64, n0 = tile_n * 128;
+    const int rb = z * q.kchunk, re = min(rb + q.kchunk, q.n);
+    const int len = max(re - rb, 0);                           // (an empty slice still writes its slab: zeros)
+    const int rlast = max(re, 1) - 1;                          // every row read is clamped to a valid one
+    const int stages = (len + W3_KS - 1) / W3_KS;
+    const int stages4 = (stages + 3) & ~3;
+    // ---- the source rows of this wave's A requests: lane L holds those of stage L (ids of a gathered problem, else the rows)
+    int32_t rid[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int rr = min(rb + W3_KS * lane + 4 * wave + j, rlast);
+        rid[j] = q.a_idx ? q.a_idx[rr] : rr;
+    }
+    // ---- requests.  dZ: wave w moves chunks 2 w, 2 w + 1 of a stage (chunk = 2 k rows x 128 n = 1 KB, lane-linear in LDS)
+    const float* __restrict__ zcol = q.dZ + min(n0 + 4 * l31, q.zcols - 4);            // (columns beyond the row: a valid chunk again,
+    const int lda = q.lda, ldz = q.ldz;                                                //  computed and never stored)
+    auto dma_b = [&](const int s, const int slot) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int c = 2 * wave + i;
+            const int r = min(rb + W3_KS * s + 2 * c + lh, rlast);
+            __builtin_amdgcn_global_load_lds(zcol + (int64_t)r * ldz, (lds_ptr_t)(smem + B_BASE + slot * B_BYTES + c * 1024), 16, 0, 0);
+        }
+    };
+    // A: row base in SGPRs (64-bit: tables beyond 4 GB), the lane's column as a 32-bit byte offset from the tile's first column.
+    // Hand-written requests as in sage_tiled3_fwd_kernel: the compiler adds no wait of its own; W3A_BARRIER's counted vmcnt
+    // guarantees them and names the registers it releases ("+v"), so nothing may touch them between request and wait.
+    const float* __restrict__ abase = q.A + m0;
+    const uint32_t acol = (uint32_t)(min(m0 + lane, lda - 1) - m0) * 4u;
+    float ra[W3A_NR][4];
+    auto gload_row = [&](float& dst, const int j, const int s) {
+        const int64_t row = (int64_t)__builtin_amdgcn_readlane(rid[j], min(s, 63));
+        const float* p = abase + row * lda;
+        asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(acol), "s"(p));
+    };
+    auto gload_a = [&](const int set, const int s) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gload_row(ra[set][j], j, s);
+    };
+    const int wn = wave;                                       // 32-column group
+    f32x16 acc[2], sml[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { acc[i][e] = 0.f; sml[i][e] = 0.f; }
+    u32x4 fa[2][2][3], fb[2][3];
+    const int kfrag = 8 * lh;                                  // first of this lane's 8 k inside a stage
+    const int a_rd = (l31 * W3A_LDA + kfrag) * 2;              // + 32 i rows, + piece plane
+    const int b_rd = B_BASE + (kfrag * 128 + 32 * wn + l31) * 4;       // + slot, + i k rows (512 bytes each)
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;
+    const uint32_t a_wr = lds0 + (uint32_t)((lane * W3A_LDA + 4 * wave) * 2);          // + buffer
+    // the three ds_write_b64 of a thread's 4 k x 3 pieces (hand-written, no "memory": see sage_tiled3_fwd_kernel's cut_store_a)
+    auto store_a = [&](const int buf_off, const u32x2 vh, const u32x2 vm, const u32x2 vl) {
+        asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %0, %3 offset:%5"
+                     :: "v"(a_wr + (uint32_t)buf_off), "v"(vh), "v"(vm), "v"(vl), "n"(A_PLANE), "n"(2 * A_PLANE));
+    };
+    auto cut_store_a = [&](const float x0, const float x1, const float x2, const float x3, const int buf_off) {
+        uint32_t h0, m0_, l0, h1, m1_, l1;
+        gs_split2(x0, x1, h0, m0_, l0);
+        gs_split2(x2, x3, h1, m1_, l1);
+        store_a(buf_off, u32x2{h0, h1}, u32x2{m0_, m1_}, u32x2{l0, l1});
+    };
+    // Stage barrier by hand (see F3_BARRIER).  What the NEXT stage consumes has landed: the raw dZ of stage ss + 2 (requested
+    // during stage ss - 1) and the A registers it cuts (stage ss + 3, requested during stage ss - 3).  A thread's requests retire
+    // IN ORDER and a stage issues its two DMAs and THEN its four A requests: behind dZ(ss + 2) lie the four A requests of that
+    // stage and this stage's six -- vmcnt(10); A(ss + 3) is older than all of them.
+#define W3A_BARRIER(cnt, r0, r1, r2, r3) do { asm volatile("s_waitcnt vmcnt(" #cnt ") lgkmcnt(0)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) \
+                                                           :: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
+    // ---- prologue: ONE round trip -- dZ of stages 0..2 and A of stages 0..5 requested together; the pieces of stages 0, 1 stored,
+    //      stage 0's fragments read and cut
+    dma_b(0, 0);
+    dma_b(1, 1);
+    dma_b(2, 2);
+    {
+        float t0[4], t1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gload_row(t0[j], j, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gload_row(t1[j], j, 1);
+        gload_a(2, 2); gload_a(3, 3); gload_a(0, 4); gload_a(1, 5);
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(t0[0]), "+v"(t0[1]), "+v"(t0[2]), "+v"(t0[3]), "+v"(t1[0]), "+v"(t1[1]), "+v"(t1[2]), "+v"(t1[3]),
+                       "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]), "+v"(ra[1][0]), "+v"(ra[1][1]), "+v"(ra[1][2]),
+                       "+v"(ra[1][3]), "+v"(ra[2][0]), "+v"(ra[2][1]), "+v"(ra[2][2]), "+v"(ra[2][3]), "+v"(ra[3][0]), "+v"(ra[3][1]),
+                       "+v"(ra[3][2]), "+v"(ra[3][3]) :: "memory");
+        cut_store_a(t0[0], t0[1], t0[2], t0[3], 0);
+        cut_store_a(t1[0], t1[1], t1[2], t1[3], A_BYTES);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) fa[0][i][p] = *reinterpret_cast<const u32x4*>(smem + a_rd + i * (32 * W3A_LDA * 2) + p * A_PLANE);
+        float bw[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bw[i] = *reinterpret_cast<const float*>(smem + b_rd + i * 512);
+        const int lim = len - kfrag;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
+        gs_split8(f32x4{bw[0], bw[1], bw[2], bw[3]}, f32x4{bw[4], bw[5], bw[6], bw[7]}, fb[0][0], fb[0][1], fb[0][2]);
+    }
+    // byte offsets of the piece buffers of stage ss + 1 | ss + 2 (the latter = the one stage ss was read from, during stage
+    // ss - 1: every wave has passed a barrier since); dZ slots are (stage) % 4
+    int oa_nxt = A_BYTES, oa_nn = 0;
+    // As in the first form: the stages whose look-ahead reads lie wholly inside the slice run WITHOUT the row mask, the last ones
+    // (and the zero padding of the ring) the masked copy.
+    auto run = [&](auto masked, const int s_begin, const int s_end) {
+    for (int s = s_begin; s < s_end; s += 4) {
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int ss = s + q4;
+            const int r = q4 & 1;                              // fragment set of this stage
+            const int as = (q4 + 2) & 3, an = (q4 + 3) & 3;    // A register sets that hold stages ss + 2 | ss + 3
+            const unsigned char* na = smem + oa_nxt + a_rd;
+            const unsigned char* nb = smem + ((q4 + 1) & 3) * B_BYTES + b_rd;
+#define W3A_SB __builtin_amdgcn_sched_barrier(0);
+#define W3A_MM(dst, i, pa, pb) dst[i] = gs_mfma_bf16(fa[r][i][pa], fb[r][pb], dst[i]); W3A_SB
+#define W3A_RA(i, p) fa[r ^ 1][i][p] = *reinterpret_cast<const u32x4*>(na + (i) * (32 * W3A_LDA * 2) + (p) * A_PLANE); W3A_SB
+#define W3A_RB(i) bw[i] = *reinterpret_cast<const float*>(nb + (i) * 512);
+            float bw[8];
+            uint32_t ph[4], pm[4], pl[4];
+            uint32_t ah[2], am[2], al[2];
+            // One stage of a wave in a PINNED issue order: the 12 MFMAs of stage ss (the sequence of wgrad_tiled3_kernel) on one
+            // fragment set, each followed by a slice of the other work: the fragments of stage ss + 1 (6 + 8 reads, 4 cuts), the
+            // pieces of stage ss + 2 (2 cuts, 3 writes), the requests of stages ss + 3 (dZ) and ss + 6 (A).
+            W3A_MM(sml, 0, 0, 2)
+            W3A_RB(0) W3A_RB(1) W3A_RB(2) W3A_RB(3) W3A_RB(4) W3A_RB(5) W3A_RB(6) W3A_RB(7)
+            W3A_SB
+            W3A_MM(sml, 1, 0, 2) W3A_RA(0, 0)
+            W3A_MM(acc, 0, 0, 0) W3A_RA(0, 1)
+            W3A_MM(acc, 1, 0, 0) W3A_RA(0, 2)
+            W3A_MM(sml, 0, 2, 0) W3A_RA(1, 0)
+            if constexpr (decltype(masked)::value) {           // the slice ends inside stage ss + 1, or before it
+                const int lim = len - W3_KS * (ss + 1) - kfrag;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
+            }
+            gs_split2(bw[0], bw[1], ph[0], pm[0], pl[0]);
+            W3A_SB
+            W3A_MM(sml, 1, 2, 0) W3A_RA(1, 1)
+            gs_split2(bw[2], bw[3], ph[1], pm[1], pl[1]);
+            W3A_SB
+            W3A_MM(sml, 0, 1, 1) W3A_RA(1, 2)
+            gs_split2(bw[4], bw[5], ph[2], pm[2], pl[2]);
+            W3A_SB
+            W3A_MM(sml, 1, 1, 1)
+            gs_split2(bw[6], bw[7], ph[3], pm[3], pl[3]);
+            fb[r ^ 1][0] = u32x4{ph[0], ph[1], ph[2], ph[3]};
+            fb[r ^ 1][1] = u32x4{pm[0], pm[1], pm[2], pm[3]};
+            fb[r ^ 1][2] = u32x4{pl[0], pl[1], pl[2], pl[3]};
+            W3A_SB
+            W3A_MM(sml, 0, 0, 1)
+            gs_split2(ra[as][0], ra[as][1], ah[0], am[0], al[0]);
+            W3A_SB
+            W3A_MM(sml, 1, 0, 1)
+            gs_split2(ra[as][2], ra[as][3], ah[1], am[1], al[1]);
+            store_a(oa_nn, u32x2{ah[0], ah[1]}, u32x2{am[0], am[1]}, u32x2{al[0], al[1]});
+            W3A_SB
+            W3A_MM(sml, 0, 1, 0)
+            dma_b(ss + 3, (q4 + 3) & 3);                       // into the slot stage ss - 1 was read from (during stage ss - 2)
+            gload_a(as, ss + 6);
+            W3A_SB
+            W3A_MM(sml, 1, 1, 0)
+            W3A_BARRIER(10, ra[an][0], ra[an][1], ra[an][2], ra[an][3]);
+            W3A_SB
+#undef W3A_MM
+#undef W3A_RA
+#undef W3A_RB
+#undef W3A_SB
+            const int t = oa_nxt; oa_nxt = oa_nn; oa_nn = t;
+        }
+    }
+    };
+    const int s_plain = max(len / W3_KS - 1, 0) & ~3;          // stages ss < s_plain read a full stage ss + 1
+    run(std::false_type{}, 0, s_plain);
+    run(std::true_type{}, s_plain, stages4);
+    asm volatile("s_waitcnt vmcnt(0)"                          // the look-ahead requests of the last stages
+                 : "+v"(ra[0][0]), "+v"(ra[0][1]), "+v"(ra[0][2]), "+v"(ra[0][3]), "+v"(ra[1][0]), "+v"(ra[1][1]), "+v"(ra[1][2]),
+                   "+v"(ra[1][3]), "+v"(ra[2][0]), "+v"(ra[2][1]), "+v"(ra[2][2]), "+v"(ra[2][3]), "+v"(ra[3][0]), "+v"(ra[3][1]),
+                   "+v"(ra[3][2]), "+v"(ra[3][3]) :: "memory");
+    __syncthreads();
+#undef W3A_BARRIER
+    // ---- the wave's 64 x 32 tile -> its slab, through a wave-private LDS staging tile: as in wgrad_tiled3_kernel
+    float* otile = reinterpret_cast<float*>(smem) + wave * (64 * 36);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+            otile[(32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh) * 36 + l31] = acc[i][e] + sml[i][e];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (wave-private region: the wave's own writes before its reads)
+    float* __restrict__ S = q.slabs + (int64_t)z * q.d * q.ld_slab;
+    const bool vec = (q.ld_slab & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
+    const int c4 = (lane & 7) * 4, r0 = lane >> 3;
+    const int colg = n0 + 32 * wn + c4;
+    const int N = q.out_dim;
+#pragma unroll
+    for (int itr = 0; itr < 8; ++itr) {
+        const int rr = 8 * itr + r0;
+        const int row = m0 + rr;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(otile + rr * 36 + c4);
+        if (row < q.d) {
+            float* dst = S + (int64_t)row * q.ld_slab + colg;
+            if (vec && colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
+            else {
+                if (colg < N) dst[0] = v.x;
+                if (colg + 1 < N) dst[1] = v.y;
+                if (colg + 2 < N) dst[2] = v.z;
+                if (colg + 3 < N) dst[3] = v.w;
+            }
+        }
+    }
+}
+
+static int g_wgrad_tiled3_form = 1;      // gs_set_wgrad_tiled3_form
+
 static int wgrad_grouped_tiled3_impl(const gs_wgrad_desc* descs_host, int32_t n_desc, const gs_gather_desc* jobs_host,
                                      int32_t n_jobs, const FanoutArgs* sampler, void* stream) {
     GS_REQUIRE(descs_host && n_desc > 0 && n_desc <= W3_MAXP, "gs_dense_wgrad_grouped_tiled3: 1..%d problems", W3_MAXP);
@@ -1385,11 +1660,28 @@ static int wgrad_grouped_tiled3_impl(const gs_wgrad_desc* descs_host, int32_t n_
     if (sampler) F = *sampler;
     const int64_t blocks = items + gs_ceil_div(F.B, 4) + gs_ceil_div(waves, 4);
     GS_REQUIRE(blocks < (1ll << 31), "gs_dense_wgrad_grouped_tiled3: grid too large");
-    const size_t lds = W3_NS * (W3_KS * 64 * 4 + W3_KS * 128 * 4) + W3_MAXROWS * 4;
     static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= W3_NS * (W3_KS * 64 * 4 + W3_KS * 128 * 4), "sampler rider LDS");
+    static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= W3A_LDS_BYTES, "sampler rider LDS");
+    if (g_wgrad_tiled3_form == 1) {
+        const size_t lds = W3A_LDS_BYTES;
+        GS_LDS_ATTR(lds, wgrad_tiled3_acut_kernel);
+        hipLaunchKernelGGL(wgrad_tiled3_acut_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, G, F, J);
+        GS_LAUNCH_CHECK("wgrad_tiled3_acut_kernel");
+        return GS_OK;
+    }
+    const size_t lds = W3_NS * (W3_KS * 64 * 4 + W3_KS * 128 * 4) + W3_MAXROWS * 4;
     GS_LDS_ATTR(lds, wgrad_tiled3_kernel);
     hipLaunchKernelGGL(wgrad_tiled3_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, G, F, J);
     GS_LAUNCH_CHECK("wgrad_tiled3_kernel");
+    return GS_OK;
+}
+
+// Which kernel the two entries below launch: 0 = wgrad_tiled3_kernel (every wave cuts the A tile for itself), 1 =
+// wgrad_tiled3_acut_kernel (A cut once per workgroup).  Same results bit for bit; process-wide, read at launch (a captured graph
+// keeps what it was captured with).
+extern "C" int gs_set_wgrad_tiled3_form(int form) {
+    GS_REQUIRE(form == 0 || form == 1, "gs_set_wgrad_tiled3_form: form is 0 or 1 (got %d)", form);
+    g_wgrad_tiled3_form = form;
     return GS_OK;
 }
 

@@ -126,8 +126,11 @@ class Engine(object):
                                    if self.device.type == "cuda" else 1024)
         self._stream_slice_rows = 256.0   # stream kernel: ~one wave per SIMD with >= 256 reduction rows per slice
         # the grouped weight gradients LDS-tiled on the bf16 matrix pipe (three-piece arithmetic, gs_dense_wgrad_grouped_tiled3): one
-        # 8-wave workgroup per (64 x 128 tile, slice), cut so that the launch is ONE round of workgroups (one per CU)
+        # four-wave workgroup per (64 x 128 tile, slice), cut so that the launch is ONE round of workgroups (one per CU)
         self.tiled3_wgrad = os.environ.get("GS_TILED3_WGRAD", "1") == "1"
+        # ... with the A rows through registers and cut ONCE per workgroup into bf16 piece buffers shared by the four waves
+        # (gs_set_wgrad_tiled3_form(1)); False = every wave reads and cuts the raw A tile for itself.  Bit-identical slabs.
+        self.tiled3_wgrad_acut = os.environ.get("GS_WGRAD_ACUT", str(ops._lib.WGRAD_TILED3_FORM_DEFAULT)) == "1"
         self.last_wgrad_kernel = None     # "tiled3" | "stream/tiled": what the last grouped weight-gradient launch took (tests)
         self._tiled3_wg_slots = (torch.cuda.get_device_properties(self.device).multi_processor_count
                                  if self.device.type == "cuda" else 256)
@@ -424,6 +427,7 @@ class Engine(object):
                 arr = (ops._lib.WgradDesc * len(pending))(*pending)
                 jarr = (ops._lib.GatherDesc * max(len(jobs), 1))(*jobs)
                 rider = self._deferred_sampler if getattr(self, "_sampler_to_wgrad", False) else None
+                ops._lib.set_wgrad_tiled3_form(1 if self.tiled3_wgrad_acut else 0)
                 if rider is not None:
                     # a later mini-batch's fan-out sampler rides in THIS launch (the caller has made sure that no problem gathers
                     # through the id buffer it fills; the library checks)

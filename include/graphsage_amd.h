@@ -249,19 +249,25 @@ int gs_dense_wgrad_grouped_stream(const gs_wgrad_desc* descs_host, int32_t n_des
                                   int32_t n_jobs, void* stream);
 /* gs_dense_wgrad_grouped_tiled3 (ABI 9, round 6): gs_dense_wgrad_grouped_stream -- same descriptors, same split-K slabs, same
  * co-scheduled gather jobs -- in the three-piece bf16 arithmetic of gs_sage_dense_fwd_tiled3 (fp32 in and out, the accuracy of an
- * fp32 FMA chain), LDS-tiled: one 8-wave workgroup per (64 x 128 tile of dW, reduction slice), both operands moved HBM -> LDS raw
- * by LDS-DMA and cut by the waves that read them.  <= 12 problems; a slice is round_up(ceil(n / n_slabs), 32) rows and must not
+ * fp32 FMA chain), LDS-tiled: one four-wave workgroup per (64 x 128 tile of dW, reduction slice), stage = 16 k, both operands moved
+ * HBM -> LDS raw by LDS-DMA and cut by the waves that read them (form 0; gs_set_wgrad_tiled3_form).  <= 12 problems; a slice is round_up(ceil(n / n_slabs), 32) rows and must not
  * exceed 1024 (any problem, gathered or dense); row addresses are 64-bit (tables beyond 4 GB are fine: a_rows is not needed).  A slab whose slice is empty is
  * written as zeros.  Replaces the TF-op group of aggregators.py:51-58's gradient (tf.gradients of the two matmuls). */
 int gs_dense_wgrad_grouped_tiled3(const gs_wgrad_desc* descs_host, int32_t n_desc, const gs_gather_desc* jobs_host,
                                   int32_t n_jobs, void* stream);
+/* Which kernel gs_dense_wgrad_grouped_tiled3 / _sample launch (process-wide, read at launch; no ABI change: same descriptors, same
+ * slabs bit for bit): 0 = every wave reads and cuts the raw A tile for itself (both operands by LDS-DMA, an LDS list of the
+ * slice's rows); 1 = A travels through registers and is cut once per workgroup into bf16 piece buffers that the four waves share
+ * (the A path of gs_sage_dense_fwd_tiled3, transposed; dZ as in form 0; the slice's row ids live in registers).  GS_EINVAL
+ * for any other value. */
+int gs_set_wgrad_tiled3_form(int form);
 /* gs_sage_dense_fwd_tiled3 (ABI 9, round 6): the contraction of gs_sage_dense_fwd_stream2 -- same arguments, fp32 operands in and
  * out -- on the bf16 matrix pipe in the three-piece arithmetic described below (every fp32 operand = three bf16 pieces, six exact
- * piece products per element pair, fp32 accumulation: the accuracy of an fp32 FMA chain), LDS-tiled: one 8-wave workgroup per
- * 64 x 128 output tile of a term, stage = 32 k; the A rows ((gathered) fp32) are cut once per workgroup in registers, the weights
+ * piece products per element pair, fp32 accumulation: the accuracy of an fp32 FMA chain), LDS-tiled: one four-wave workgroup per
+ * 64 x 128 output tile of a term, stage = 16 k; the A rows ((gathered) fp32) are cut once per workgroup in registers, the weights
  * go global -> LDS by DMA as fp32 and are cut by the wave that contracts them (no pre-cut copy, nothing to refresh after an
- * optimizer step); the two 16-k halves of a stage are contracted by different waves and summed once in the epilogue (fixed order:
- * deterministic).  Pad columns [d, round_up(d, 4)) of self / agg must be readable (any value: masked); out_dim and ldo multiples
+ * optimizer step); a wave contracts every stage of its 64 x 32 tile, so an element's K reduction has one fixed order
+ * (deterministic).  Pad columns [d, round_up(d, 4)) of self / agg must be readable (any value: masked); out_dim and ldo multiples
  * of 4.  self == NULL: one term (GCN).  Gather jobs ride as in gs_sage_dense_fwd_stream. */
 int gs_sage_dense_fwd_tiled3(const float* self, int64_t ld_self, const int32_t* self_idx, int32_t d_self, const float* agg,
                              int64_t ld_agg, int32_t d_agg, int64_t n, const float* W_self, int64_t ldw_self, const float* W_neigh,
