@@ -792,19 +792,28 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
                              asm volatile("" ::: "memory"); } while (0)
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;                      // LDS byte address of the dynamic segment
-    auto cut_store_a = [&](const int set, const int s, unsigned char* buf) {
-        const int k = F3_KS * s + 4 * aq;
-        const float x0 = k < K ? ra[set].x : 0.f, x1 = k + 1 < K ? ra[set].y : 0.f;       // selects: zero beyond K (NaN pads must not leak)
-        const float x2 = k + 2 < K ? ra[set].z : 0.f, x3 = k + 3 < K ? ra[set].w : 0.f;
+    const uint32_t a_wr0 = lds0 + (uint32_t)a_wr;                                    // the thread's piece slot in buffer 0
+    // whole: the stage lies wholly inside K (a steady stage, below) -- no select
+    auto cut_store_a = [&](auto whole, auto second_buf, const int set, const int s) {
+        float x0 = ra[set].x, x1 = ra[set].y, x2 = ra[set].z, x3 = ra[set].w;
+        if constexpr (!decltype(whole)::value) {
+            const int k = F3_KS * s + 4 * aq;
+            x0 = k < K ? x0 : 0.f; x1 = k + 1 < K ? x1 : 0.f;                      // selects: zero beyond K (NaN pads must not leak)
+            x2 = k + 2 < K ? x2 : 0.f; x3 = k + 3 < K ? x3 : 0.f;
+        }
         uint32_t h0, m0_, l0, h1, m1_, l1;
         gs_split2(x0, x1, h0, m0_, l0);
         gs_split2(x2, x3, h1, m1_, l1);
         // (hand-written stores: behind a C++ store to LDS the compiler waits for EVERY outstanding LDS-DMA -- it cannot tell that
         //  the B ring and the A-piece buffers never overlap -- i.e. vmcnt(0) once per stage; F3_BARRIER waits for lgkmcnt(0))
-        const uint32_t ad = lds0 + (uint32_t)(buf - smem) + (uint32_t)a_wr;
         const u32x2 vh = u32x2{h0, h1}, vm = u32x2{m0_, m1_}, vl = u32x2{l0, l1};
-        asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %0, %3 offset:%5"
-                     :: "v"(ad), "v"(vh), "v"(vm), "v"(vl), "n"(A_PLANE), "n"(2 * A_PLANE));      // (no "memory": see above)
+        const uint32_t ad = a_wr0;
+        if constexpr (!decltype(second_buf)::value)
+            asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %0, %3 offset:%5"
+                         :: "v"(ad), "v"(vh), "v"(vm), "v"(vl), "n"(A_PLANE), "n"(2 * A_PLANE));  // (no "memory": see above)
+        else
+            asm volatile("ds_write_b64 %0, %1 offset:%4\n\tds_write_b64 %0, %2 offset:%5\n\tds_write_b64 %0, %3 offset:%6"
+                         :: "v"(ad), "v"(vh), "v"(vm), "v"(vl), "n"(A_BYTES), "n"(A_BYTES + A_PLANE), "n"(A_BYTES + 2 * A_PLANE));
     };
     auto read_cut_frags = [&](const int set, const unsigned char* abuf, const unsigned char* bslot) {
 #pragma unroll
@@ -834,27 +843,40 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
         F3_STAMP(1);
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(t0), "+v"(t1), "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
         const f32x4 s0 = ra[0], s1 = ra[1];
-        ra[0] = t0; cut_store_a(0, 0, smem);
-        ra[1] = t1; cut_store_a(1, 1, smem + A_BYTES);
+        ra[0] = t0; cut_store_a(std::false_type{}, std::false_type{}, 0, 0);
+        ra[1] = t1; cut_store_a(std::false_type{}, std::true_type{}, 1, 1);
         ra[0] = s0; ra[1] = s1;                                // (sets 0, 1 hold stages 4, 5; sets 2, 3 stages 2, 3)
     }
     F3_BARRIER(0);
     F3_STAMP(2);
     read_cut_frags(0, smem, smem + B_BASE);
-    // byte offsets of the A-piece buffers of stage s + 1 | s + 2 (= the one stage s was read from, during stage s - 1: every wave
-    // has passed a barrier since); B slots are (stage) % 4
-    int oa_nxt = A_BYTES, oa_nn = 0;
-    const int stages4 = (stages + 3) & ~3;                     // whole rings: padded with all-zero stages (A is masked beyond K)
-    for (int s = 0; s < stages4; s += 4) {
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {                       // the register sets are indexed statically
-            const int ss = s + q4;
-            constexpr int dummy_ = 0; (void)dummy_;
-            const int r = q4 & 1;                              // fragment set of this stage
-            const int as = (q4 + 2) & 3;                       // A staging set that holds stage ss + 2
-            const unsigned char* na = smem + oa_nxt;
-            const unsigned char* nb = smem + B_BASE + ((ss + 1) & 3) * B_BYTES + (b_rd - B_BASE);
-            unsigned char* wa = smem + oa_nn;
+    // The K loop runs in rings of four stages (the register sets are indexed statically: stage ss takes the sets of ss % 4), first
+    // STEADY rings, then CAREFUL stages, one stage body for both:
+    //   steady  while every request a ring issues lies wholly inside K -- A of stage ss + 6, B of stage ss + 3, the cut of stage
+    //           ss + 2, for its last stage ss = s + 3: 16 (s + 10) <= K.  No select, no clamp, no address arithmetic in the vector
+    //           stream: the lane's A pointer moves once per ring (the four requests take 0 / 64 / 128 / 192 bytes as the
+    //           instruction's offset), a B request is a wave-uniform 64-bit base, advanced by 16 rows per stage on the scalar pipe,
+    //           plus the lane's constant 32-bit byte offset; nothing beyond column K - 1 is requested;
+    //   careful the remaining stages, selects and clamped addresses as in the prologue; the last ring is left behind its
+    //           stages % 4 -th stage (no stage of zeros is computed).
+    // Both kinds issue B, B, A in this order, once per stage: F3_BARRIER(4)'s accounting holds across the seam.
+    // A-piece buffers: stage ss + 1 is read from buffer (ss + 1) & 1, stage ss + 2 written to buffer ss & 1 (= the one stage ss was
+    // read from, during stage ss - 1: every wave has passed a barrier since); B slots are (stage) % 4.
+    const int whole_stages = K / F3_KS;
+    // (a lane's B offset (lh * ldw + bcol) * 4 must fit 32 bits: leading dimensions beyond 2^29 take the careful stages throughout)
+    const int s_steady = (whole_stages >= 10 && ldw < (1 << 29)) ? ((whole_stages - 10) & ~3) + 4 : 0;
+    const float* pa = xrow + 4 * aq + 6 * F3_KS;                                     // A of stage s + 6
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(T.W) + (int64_t)(3 * F3_KS + 4 * wave) * ldw * 4;   // B of stage s + 3: the
+    const int64_t wb_pair = (int64_t)ldw * 8, wb_stage = (int64_t)ldw * (F3_KS * 4);                                      // wave's first chunk
+    const uint32_t wb_lane = (uint32_t)(lh * ldw + bcol) * 4u;
+    const uint32_t wb_lds = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(B_BASE + 2 * wave * 1024));   // the wave's first chunk of slot 0
+    auto stage = [&](auto q4_, auto steady_, const int ss) __attribute__((always_inline)) {
+            constexpr int q4 = decltype(q4_)::value;
+            constexpr bool steady = decltype(steady_)::value;
+            constexpr int r = q4 & 1;                          // fragment set of this stage
+            constexpr int as = (q4 + 2) & 3;                   // A staging set that holds stage ss + 2
+            const unsigned char* na = smem + (r ? 0 : A_BYTES);
+            const unsigned char* nb = smem + ((q4 + 1) & 3) * B_BYTES + b_rd;
 #define F3_SB __builtin_amdgcn_sched_barrier(0);
 #ifdef F3_DIAG_NOMFMA
 #define F3_MM(dst, i, pa, pb) asm volatile("" :: "v"(fa[r][i][pa]), "v"(fb[r][pb])); F3_SB
@@ -897,14 +919,30 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
             F3_SB
             F3_MM(sml, 1, 0, 1)
 #ifndef F3_DIAG_NOLDSW
-            cut_store_a(as, ss + 2, wa);
+            cut_store_a(steady_, std::integral_constant<bool, r != 0>{}, as, ss + 2);
 #else
             asm volatile("" :: "v"(ra[as]));
 #endif
             F3_SB
             F3_MM(sml, 0, 1, 0)
-            dma_b(ss + 3, (ss + 3) & 3);
-            gload_a(as, ss + 6);
+            if constexpr (steady) {
+#ifndef F3_DIAG_NOGB
+                // (by hand: the builtin forms base + lane offset as a 64-bit vector add per request; M0 = the chunk's LDS address)
+                asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
+                             "s_add_i32 m0, %3, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
+                             :: "v"(wb_lane), "s"(wb), "s"(wb + wb_pair), "s"(wb_lds), "n"(((q4 + 3) & 3) * B_BYTES),
+                                "n"(((q4 + 3) & 3) * B_BYTES + 1024) : "scc");      // (M0: the compiler sets it in front of every request of its own)
+#endif
+                wb += wb_stage;
+#ifdef F3_DIAG_NOGA
+                ra[as] = f32x4{(float)ss, 1.f, 2.f, (float)tid};
+#else
+                asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(ra[as]) : "v"(pa), "n"(q4 * F3_KS * 4));
+#endif
+            } else {
+                dma_b(ss + 3, (q4 + 3) & 3);
+                gload_a(as, ss + 6);
+            }
             F3_SB
             F3_MM(sml, 1, 1, 0)
             F3_STAMP(8 + 3 * ss);
@@ -925,11 +963,33 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
 #undef F3_RA
 #undef F3_RW
 #undef F3_SB
-            const int t = oa_nxt; oa_nxt = oa_nn; oa_nn = t;
-        }
+    };
+    constexpr std::integral_constant<int, 0> q0{};
+    constexpr std::integral_constant<int, 1> q1{};
+    constexpr std::integral_constant<int, 2> q2{};
+    constexpr std::integral_constant<int, 3> q3{};
+    int s = 0;
+    for (; s < s_steady; s += 4) {
+        stage(q0, std::true_type{}, s);
+        stage(q1, std::true_type{}, s + 1);
+        stage(q2, std::true_type{}, s + 2);
+        stage(q3, std::true_type{}, s + 3);
+        pa += 4 * F3_KS;
+    }
+    for (; s < stages; s += 4) {                                // (the last ring ends behind stage stages - 1: no stage of zeros)
+        stage(q0, std::false_type{}, s);
+        if (s + 1 >= stages) break;
+        stage(q1, std::false_type{}, s + 1);
+        if (s + 2 >= stages) break;
+        stage(q2, std::false_type{}, s + 2);
+        if (s + 3 >= stages) break;
+        stage(q3, std::false_type{}, s + 3);
     }
     F3_STAMP(3);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // the look-ahead requests of the last stages
+    // The look-ahead requests of the last stages are still in flight INTO the four staging sets, and the compiler does not know: the
+    // wait names the sets ("+v"), as in wgrad_tiled3_acut_kernel, so that they stay reserved up to here whatever the scheduler
+    // moves in front of it (the sets are dead behind the last cut otherwise).
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
     __syncthreads();
     F3_STAMP(4);
     // ---- the wave's 64 x 32 tile: bias + activation, then through a wave-private LDS staging tile to 16-byte row segments
@@ -1512,6 +1572,14 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
     int oa_nxt = A_BYTES, oa_nn = 0;
     // As in the first form: the stages whose look-ahead reads lie wholly inside the slice run WITHOUT the row mask, the last ones
     // (and the zero padding of the ring) the masked copy.
+    // The copy without the mask is also the one without clamps in the vector stream: it runs while every dZ request of a ring lies
+    // wholly inside the slice (stage ss + 3 for its last stage ss = s + 3: 16 (s + 7) <= len).  Its dZ requests are a wave-uniform
+    // 64-bit base, advanced by 16 rows per stage on the scalar pipe, plus the lane's constant 32-bit byte offset (by hand, as in
+    // sage_tiled3_fwd_kernel's steady stages); the A requests were scalar arithmetic behind their four v_readlane already.
+    const unsigned char* zb = reinterpret_cast<const unsigned char*>(q.dZ) + (int64_t)(rb + 3 * W3_KS + 4 * wave) * ldz * 4;
+    const int64_t zb_pair = (int64_t)ldz * 8, zb_stage = (int64_t)ldz * (W3_KS * 4);
+    const uint32_t zb_lane = (uint32_t)(lh * ldz + min(n0 + 4 * l31, q.zcols - 4)) * 4u;
+    const uint32_t zb_lds = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(B_BASE + 2 * wave * 1024));
     auto run = [&](auto masked, const int s_begin, const int s_end) {
     for (int s = s_begin; s < s_end; s += 4) {
 #pragma unroll
@@ -1565,8 +1633,17 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
             store_a(oa_nn, u32x2{ah[0], ah[1]}, u32x2{am[0], am[1]}, u32x2{al[0], al[1]});
             W3A_SB
             W3A_MM(sml, 0, 1, 0)
-            dma_b(ss + 3, (q4 + 3) & 3);                       // into the slot stage ss - 1 was read from (during stage ss - 2)
-            gload_a(as, ss + 6);
+            if constexpr (decltype(masked)::value) {
+                dma_b(ss + 3, (q4 + 3) & 3);                   // into the slot stage ss - 1 was read from (during stage ss - 2)
+                gload_a(as, ss + 6);
+            } else {
+                asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
+                             "s_add_i32 m0, %3, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
+                             :: "v"(zb_lane), "s"(zb), "s"(zb + zb_pair), "s"(zb_lds), "n"(((q4 + 3) & 3) * B_BYTES),
+                                "n"(((q4 + 3) & 3) * B_BYTES + 1024) : "scc");
+                zb += zb_stage;
+                gload_a(as, ss + 6);
+            }
             W3A_SB
             W3A_MM(sml, 1, 1, 0)
             W3A_BARRIER(10, ra[an][0], ra[an][1], ra[an][2], ra[an][3]);
@@ -1579,7 +1656,8 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
         }
     }
     };
-    const int s_plain = max(len / W3_KS - 1, 0) & ~3;          // stages ss < s_plain read a full stage ss + 1
+    const int whole = len / W3_KS;
+    const int s_plain = (whole >= 7 && ldz < (1 << 29)) ? ((whole - 7) & ~3) + 4 : 0;   // (<= (whole - 1) & ~3: stages ss < s_plain read a full stage ss + 1)
     run(std::false_type{}, 0, s_plain);
     run(std::true_type{}, s_plain, stages4);
     asm volatile("s_waitcnt vmcnt(0)"                          // the look-ahead requests of the last stages
