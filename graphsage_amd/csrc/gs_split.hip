@@ -17,6 +17,9 @@
 //                             and cut in registers (11 VALU per 2 elements, in the shadow of the MFMAs), B operands come
 //                             pre-cut from W3.  One WAVE per 32 x 64 output tile over the whole K: no LDS, no barrier, no
 //                             split-K epilogue; gather jobs of the next step ride as extra workgroups like before.
+//   gs_sage_dense_fwd_tiled3, gs_dense_wgrad_grouped_tiled3   the LDS-tiled forms of the step (sage_tiled3_fwd_kernel,
+//                             wgrad_tiled3_kernel, wgrad_tiled3_acut_kernel): one design, one set of device helpers and layout
+//                             constants ("shared by the tiled3 kernels"); only the pinned stage bodies are per kernel.
 #include "gs_common.h"
 #include "gs_gather_dev.h"
 #include "gs_sample_dev.h"
@@ -25,6 +28,8 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 __device__ __forceinline__ uint32_t gs_hi16_pair(const float x, const float y) {   // bf16 bits of x (low half) and y (high half)
     return __builtin_amdgcn_perm(__float_as_uint(y), __float_as_uint(x), 0x07060302u);
@@ -62,6 +67,13 @@ __device__ __forceinline__ void gs_split8(const f32x4 a0, const f32x4 a1, u32x4&
 
 __device__ __forceinline__ f32x16 gs_mfma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// XCD-aware block order of the tiled launches: physical block b runs on XCD b % 8, so the nwg working blocks are dealt to the
+// XCDs in eight contiguous runs -- consecutive LOGICAL blocks (tiles that read the same operand rows) share an XCD's L2.
+__device__ __forceinline__ int t3_logical_block(const int nwg) {
+    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
 }
 
 // ------------------------------------------------------------------------------------------------ W -> W3
@@ -152,9 +164,7 @@ __global__ __launch_bounds__(512) void split_tiled_fwd_kernel(const SplitTiledAr
     const int tiles_n = (g.N + 127) >> 7, tiles_m = (count + 127) >> 7;
     const int nwg = tiles_m * tiles_n;
     if ((int)blockIdx.x >= nwg) return;
-    // XCD-aware: block b runs on XCD b % 8; consecutive LOGICAL tiles (the column tiles of one row tile) share an XCD's L2
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
+    const int tile = t3_logical_block(nwg);                   // (consecutive tiles: the column tiles of one row tile)
     const int tile_m = tile / tiles_n, tile_n = tile - tile_m * tiles_n;
     const int m0 = tile_m * 128, n0 = tile_n * 128;
     const int K = g.K, N = g.N;
@@ -346,8 +356,7 @@ __global__ __launch_bounds__(512) void split_tiled_fwd_wide_kernel(const SplitTi
     if ((int)blockIdx.x >= sch.full + sch.rem * sch.S) return;
     int tile, part = -1;                                       // part >= 0: a K part of a tail-round tile (partial tile -> g.ws)
     if ((int)blockIdx.x < sch.full) {
-        const int q8 = sch.full >> 3, r8 = sch.full & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-        tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
+        tile = t3_logical_block(sch.full);
     } else {
         const int r = (int)blockIdx.x - sch.full;              // the S parts of a tile sit on S consecutive block ids
         tile = sch.full + r / sch.S;
@@ -684,10 +693,130 @@ struct Fwd3Args {
 #define T3_RIDER_U 8
 #endif
 #define F3_BM 64
-#define F3_NA 2            // A-piece buffers (stage s + 1 being read, stage s + 2 being written)
-#define F3_NB 4            // raw B stages in flight
-#define F3_KS 16           // k per stage
-#define F3_LDA 24          // bf16 per LDS row of an A plane: 16 + 8 pad (48 bytes: 16 lanes of a 16-byte fragment read cover all banks)
+
+// ------------------------------------------------------------------------------------------------ shared by the tiled3 kernels
+// sage_tiled3_fwd_kernel, wgrad_tiled3_kernel and wgrad_tiled3_acut_kernel are one design (four waves, 16-k stages, a wave's
+// 64 x 32 tile as acc[2] + sml[2], hand-written requests behind a counted wait) and share everything below.  What they do NOT
+// share is the stage body -- the pinned sequence of MFMAs and slices between two stage barriers, with its sched_barriers: that is
+// per kernel, on purpose, and it is where the time is.  (t3_logical_block is further up; the weight gradients' item decode, riders
+// and epilogue follow Wg3Args.)
+// LDS layout of the forward and of the acut form: T3_NA buffers of A pieces ([piece][64 rows][16 k] bf16), then a ring of T3_NB
+// raw fp32 B / dZ stages ([16 k][128 columns]).
+// Each number is written ONCE, under the name tests/test_wgrad_acut_layout.py reads it by (that test models the piece buffer's
+// banks from this file's text and predates the forward sharing the layout); the kernels use the T3_ names.
+#define W3_KS 16           // k per stage
+#define W3A_LDA 24         // bf16 per LDS row of an A piece plane: 16 k + 8 pad (48 bytes: 16 lanes of a 16-byte fragment read cover all banks)
+#define W3A_NA 2           // A-piece buffers (stage s + 1 being read, stage s + 2 being written)
+#define W3A_NB 4           // raw B stages in flight
+#define W3A_LDS_BYTES (W3A_NA * 3 * 64 * W3A_LDA * 2 + W3A_NB * W3_KS * 128 * 4)
+#define T3_KS W3_KS
+#define T3_LDA W3A_LDA
+#define T3_NA W3A_NA
+#define T3_NB W3A_NB
+#define T3_A_PLANE (64 * T3_LDA * 2)           // bytes of one piece plane
+#define T3_A_BYTES (3 * T3_A_PLANE)            // ... of one A-piece buffer
+#define T3_B_BYTES (T3_KS * 128 * 4)           // ... of one raw B slot
+#define T3_B_BASE (T3_NA * T3_A_BYTES)         // the B ring's offset
+#define T3_LDS_BYTES (T3_B_BASE + T3_NB * T3_B_BYTES)      // 2 * 9,216 + 4 * 8,192 = 51,200
+static_assert(T3_LDS_BYTES <= 53248, "a host workgroup must leave room for two rider workgroups on its CU");
+static_assert(T3_LDS_BYTES == W3A_LDS_BYTES, "the layout test's formula is the launches' LDS size");
+
+__device__ __forceinline__ void t3_zero(f32x16 (&acc)[2], f32x16 (&sml)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { acc[i][e] = 0.f; sml[i][e] = 0.f; }
+}
+
+// The stage barrier by hand: "my LDS writes and reads of this stage are done" (lgkmcnt(0)) + "what the next stage consumes has
+// landed" (a COUNTED vmcnt: the younger requests stay in flight across the barrier; the count is each kernel's accounting, written
+// at its call) + s_barrier + a compiler fence.  __syncthreads, and also a release fence on the local address space (the compiler
+// orders the LDS-DMA writes behind it), would wait for vmcnt(0): every request of the stages ahead would have to land before any
+// wave may go on -- a stage would cost a memory round trip.
+// The requests are hand-written asm the compiler does not track, so the wait NAMES the registers that requests in flight write
+// ("+v"(reg), ... behind the count): nothing may be moved into or out of them between request and wait.  The list is empty where
+// every request goes to LDS (wgrad_tiled3_kernel).
+#define T3_STR2(x) #x
+#define T3_STR(x) T3_STR2(x)
+#define T3_BARRIER(cnt, ...) do { asm volatile("s_waitcnt vmcnt(" T3_STR(cnt) ") lgkmcnt(0)" : __VA_ARGS__ :: "memory"); \
+                                  __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
+
+// The three ds_write_b64 of a thread's 4 k x 3 pieces, at lds_addr + OFF (OFF: an immediate -- the second buffer costs no add).
+// Hand-written and WITHOUT a "memory" clobber: behind a C++ store to LDS the compiler waits for EVERY outstanding LDS-DMA -- it
+// cannot tell that the B ring and the A-piece buffers never overlap -- i.e. vmcnt(0) once per stage; the stage barrier's
+// lgkmcnt(0) and fence are what order these writes.
+template <int OFF>
+__device__ __forceinline__ void t3_store_pieces(const uint32_t lds_addr, const u32x2 vh, const u32x2 vm, const u32x2 vl) {
+    asm volatile("ds_write_b64 %0, %1 offset:%4\n\tds_write_b64 %0, %2 offset:%5\n\tds_write_b64 %0, %3 offset:%6"
+                 :: "v"(lds_addr), "v"(vh), "v"(vm), "v"(vl), "n"(OFF), "n"(OFF + T3_A_PLANE), "n"(OFF + 2 * T3_A_PLANE));
+}
+
+// A steady stage's two B / dZ requests (chunks 2 w, 2 w + 1 of the stage: two k rows x 128 columns each) into the slot at byte
+// offset `slot`: base = the wave-uniform 64-bit address of the first chunk's rows (the caller advances it by 16 rows per stage on
+// the scalar pipe), pair = two rows in bytes, lane_off = the lane's constant 32-bit byte offset ((lane >> 5) * ld + column) * 4 --
+// which is why leading dimensions from 2^29 on take the clamped stages throughout -- and lds = the LDS address of the wave's first
+// chunk in slot 0.  By hand: the builtin forms base + lane offset as a 64-bit vector add per request; M0 = the chunk's LDS
+// address is set here because the compiler sets it only in front of requests of its own.  (slot: an immediate once the call is
+// inlined into an unrolled ring -- a constant expression or the unrolled loop's counter.)
+__device__ __forceinline__ void t3_dma_pair(const uint32_t lane_off, const unsigned char* base, const int64_t pair, const uint32_t lds,
+                                            const int slot) {
+    asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
+                 "s_add_i32 m0, %3, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
+                 :: "v"(lane_off), "s"(base), "s"(base + pair), "s"(lds), "n"(slot), "n"(slot + 1024) : "scc");
+}
+
+// Prologue only (the stage bodies slice these reads between their MFMAs): a wave's A fragments of one stage, six ds_read_b128
+// from p = buffer + the lane's (row, k half) offset ...
+__device__ __forceinline__ void t3_read_a_frags(u32x4 (&fa)[2][3], const unsigned char* p) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int pc = 0; pc < 3; ++pc) fa[i][pc] = *reinterpret_cast<const u32x4*>(p + i * (32 * T3_LDA * 2) + pc * T3_A_PLANE);
+}
+// ... and its B fragment: the lane's 8 k of its column as eight ds_read_b32 from p = slot + the lane's offset, cut here; MASK:
+// the values of the k rows from lim on are zeroed (rows beyond a slice: the clamped row was read)
+template <bool MASK>
+__device__ __forceinline__ void t3_read_cut_b(u32x4 (&fb)[3], const unsigned char* p, const int lim) {
+    float bw[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) bw[i] = *reinterpret_cast<const float*>(p + i * 512);
+    if constexpr (MASK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
+    }
+    gs_split8(f32x4{bw[0], bw[1], bw[2], bw[3]}, f32x4{bw[4], bw[5], bw[6], bw[7]}, fb[0], fb[1], fb[2]);
+}
+
+// The epilogue's staging tile: a wave's 64 x 32 accumulators (C/D layout: row = (e & 3) + 8 (e >> 2) + 4 (lane >> 5) of its
+// 32-row block, column = lane & 31) -> its private [64 rows][32 + 4 pad] floats of LDS as f(acc + sml), then lgkmcnt(0): the
+// region is wave-private, so the wave's own writes before its reads need no barrier.  Rows are read back as 16-byte segments:
+// lane -> row 8 itr + (lane >> 3), columns 4 (lane & 7) ..
+template <class F>
+__device__ __forceinline__ float* t3_stage_tile(unsigned char* smem, const int wave, const int lane, const f32x16 (&acc)[2],
+                                                const f32x16 (&sml)[2], const F f) {
+    float* otile = reinterpret_cast<float*>(smem) + wave * (64 * 36);
+    float* mine = otile + 4 * (lane >> 5) * 36 + (lane & 31);          // (the lane's part once: every store is base + immediate)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mine[(32 * i + (e & 3) + 8 * (e >> 2)) * 36] = f(acc[i][e] + sml[i][e]);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    return otile;
+}
+__device__ __forceinline__ f32x4 t3_tile_seg(const float* otile, const int lane, const int itr) {
+    return *reinterpret_cast<const f32x4*>(otile + ((lane >> 3) * 36 + (lane & 7) * 4) + itr * (8 * 36));   // (lane part + immediate)
+}
+// .. and stored with the row's column guard: one 16-byte store where the segment lies inside N (vec: dst is 16-byte aligned)
+__device__ __forceinline__ void t3_store_row4(float* dst, const f32x4 v, const int colg, const int N, const bool vec) {
+    if (vec && colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
+    else {
+        if (colg < N) dst[0] = v.x;
+        if (colg + 1 < N) dst[1] = v.y;
+        if (colg + 2 < N) dst[2] = v.z;
+        if (colg + 3 < N) dst[3] = v.w;
+    }
+}
+
 #ifdef F3_TIMELINE
 // Diagnostics build only (-DF3_TIMELINE, benchmarks/timeline_tiled3.py): shader-clock and wall-clock stamps of waves 0 and 4 of the
 // first 256 workgroups.  [wg][wave 0 | 4][0] entry [1] operands requested [2] prologue barrier passed [3] K loop left [4] K halves
@@ -705,11 +834,8 @@ extern "C" int gs_debug_f3_timeline(unsigned long long* out_host, int n) {
 #endif
 
 __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, const CoGatherS J) {
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int A_PLANE = F3_BM * F3_LDA * 2;                // bytes
-    constexpr int A_BYTES = 3 * A_PLANE, B_BYTES = F3_KS * 128 * 4;
-    constexpr int B_BASE = F3_NA * A_BYTES;
+    constexpr int A_PLANE = T3_A_PLANE, A_BYTES = T3_A_BYTES, B_BYTES = T3_B_BYTES, B_BASE = T3_B_BASE;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= g.n_tiles) {
         run_gather_item<T3_RIDER_U>(J, ((int64_t)blockIdx.x - g.n_tiles) * 4 + wave, lane);
@@ -718,10 +844,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     const int l31 = lane & 31, lh = lane >> 5;
     F3_STAMP(0);
     F3_STAMPV(6, wall_clock64());
-    // XCD-aware: block b runs on XCD b % 8; consecutive LOGICAL tiles share an XCD's L2 (a term's W stays resident there)
-    const int nwg = g.n_tiles;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
+    const int tile = t3_logical_block(g.n_tiles);             // (consecutive tiles: a term's W stays resident in the XCD's L2)
     const int per_term = g.tiles_m * g.tiles_n;
     const int term = tile / per_term;
     const int it = tile - term * per_term;
@@ -738,14 +861,14 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     }
     const Fwd3Term& T = g.t[term];
     const int K = T.K, N = g.N;
-    const int stages = (K + F3_KS - 1) / F3_KS;
+    const int stages = (K + T3_KS - 1) / T3_KS;
     const int K4 = ((K + 3) >> 2) << 2;                        // readable columns of a row
     // ---- A: (row tid >> 2, float4 tid & 3) of the 64 x 16 stage tile, through registers
     const int arow = tid >> 2, aq = tid & 3;
     const int grow = min(m0 + arow, mend - 1);
     const int64_t srow = T.a_idx ? (int64_t)T.a_idx[grow] : (int64_t)grow;
     const float* __restrict__ xrow = T.A + srow * T.lda;
-    const int a_wr = (arow * F3_LDA + 4 * aq) * 2;
+    const int a_wr = (arow * T3_LDA + 4 * aq) * 2;
     // ---- B: wave w moves chunks 2 w, 2 w + 1 of a stage's 8 (chunk = two k rows x 128 columns = 1 KB, lane-linear in LDS)
     const int bcol = min(n0 + 4 * l31, N - 4);                 // (columns beyond N: a valid column again, computed and never stored)
     const float* __restrict__ wcol = T.W + bcol;
@@ -753,11 +876,11 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     // A ring of FOUR staging sets: the set stage s + 2 is cut from is re-requested for stage s + 6 at once -- four stages (~2 us)
     // of cover for a gathered row's trip to HBM.  Requests are hand-written (asm): the compiler does not track them, so it adds no
     // wait of its own (it answered every use with vmcnt(0) once LDS-DMA requests shared the queue); the counted wait in front of
-    // every stage barrier (F3_BARRIER) is what guarantees them -- see the accounting there.
+    // every stage barrier (T3_BARRIER) is what guarantees them -- see the accounting at the end of the stage body.
     f32x4 ra[4];
     // (F3_DIAG_*: diagnostics builds only, benchmarks/probes/build_variant.sh -- wrong values, the kernel's time without one component)
     auto gload_a = [&](const int set, const int s) {           // straight-line request with a clamped (always valid) address
-        const int k = min(F3_KS * s + 4 * aq, K4 - 4);
+        const int k = min(T3_KS * s + 4 * aq, K4 - 4);
 #ifdef F3_DIAG_NOGA
         ra[set] = f32x4{(float)k, 1.f, 2.f, (float)tid};
 #else
@@ -769,61 +892,32 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c = 2 * wave + i;
-            const int k = min(F3_KS * s + 2 * c + lh, K - 1);
+            const int k = min(T3_KS * s + 2 * c + lh, K - 1);
             __builtin_amdgcn_global_load_lds(wcol + (int64_t)k * ldw, (lds_ptr_t)(smem + B_BASE + slot * B_BYTES + c * 1024), 16, 0, 0);
         }
 #endif
     };
     const int wn = wave;                                       // 32-column group
     f32x16 acc[2], sml[2];                                     // [row tile of 32]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[i][e] = 0.f; sml[i][e] = 0.f; }
+    t3_zero(acc, sml);
     // fragments of a stage: TWO register sets -- the MFMAs of stage s run on one while the other receives stage s + 1's
     u32x4 fa[2][2][3], fb[2][3];
-    const int a_rd = (l31 * F3_LDA + 8 * lh) * 2;                                    // + 32 i rows, + piece plane
+    const int a_rd = (l31 * T3_LDA + 8 * lh) * 2;                                    // + 32 i rows, + piece plane
     const int b_rd = B_BASE + ((8 * lh) * 128 + 32 * wn + l31) * 4;                  // + i k rows (512 bytes each)
-    // The stage barrier by hand: "my LDS writes and reads of this stage are done" (lgkmcnt(0)) + "the B stage the next stage reads
-    // has landed" (a COUNTED vmcnt: the younger requests stay in flight across the barrier) + s_barrier.  __syncthreads, and also a
-    // release fence on the local address space (the compiler orders the LDS-DMA writes behind it), would wait for vmcnt(0): every
-    // request of the stages ahead would have to land before any wave may go on -- a stage would cost a memory round trip.
-#define F3_BARRIER(cnt) do { asm volatile("s_waitcnt vmcnt(" #cnt ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                             asm volatile("" ::: "memory"); } while (0)
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;                      // LDS byte address of the dynamic segment
     const uint32_t a_wr0 = lds0 + (uint32_t)a_wr;                                    // the thread's piece slot in buffer 0
     // whole: the stage lies wholly inside K (a steady stage, below) -- no select
     auto cut_store_a = [&](auto whole, auto second_buf, const int set, const int s) {
         float x0 = ra[set].x, x1 = ra[set].y, x2 = ra[set].z, x3 = ra[set].w;
         if constexpr (!decltype(whole)::value) {
-            const int k = F3_KS * s + 4 * aq;
+            const int k = T3_KS * s + 4 * aq;
             x0 = k < K ? x0 : 0.f; x1 = k + 1 < K ? x1 : 0.f;                      // selects: zero beyond K (NaN pads must not leak)
             x2 = k + 2 < K ? x2 : 0.f; x3 = k + 3 < K ? x3 : 0.f;
         }
         uint32_t h0, m0_, l0, h1, m1_, l1;
         gs_split2(x0, x1, h0, m0_, l0);
         gs_split2(x2, x3, h1, m1_, l1);
-        // (hand-written stores: behind a C++ store to LDS the compiler waits for EVERY outstanding LDS-DMA -- it cannot tell that
-        //  the B ring and the A-piece buffers never overlap -- i.e. vmcnt(0) once per stage; F3_BARRIER waits for lgkmcnt(0))
-        const u32x2 vh = u32x2{h0, h1}, vm = u32x2{m0_, m1_}, vl = u32x2{l0, l1};
-        const uint32_t ad = a_wr0;
-        if constexpr (!decltype(second_buf)::value)
-            asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %0, %3 offset:%5"
-                         :: "v"(ad), "v"(vh), "v"(vm), "v"(vl), "n"(A_PLANE), "n"(2 * A_PLANE));  // (no "memory": see above)
-        else
-            asm volatile("ds_write_b64 %0, %1 offset:%4\n\tds_write_b64 %0, %2 offset:%5\n\tds_write_b64 %0, %3 offset:%6"
-                         :: "v"(ad), "v"(vh), "v"(vm), "v"(vl), "n"(A_BYTES), "n"(A_BYTES + A_PLANE), "n"(A_BYTES + 2 * A_PLANE));
-    };
-    auto read_cut_frags = [&](const int set, const unsigned char* abuf, const unsigned char* bslot) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fa[set][i][p] = *reinterpret_cast<const u32x4*>(abuf + a_rd + i * (32 * F3_LDA * 2) + p * A_PLANE);
-        float bw[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bw[i] = *reinterpret_cast<const float*>(bslot + (b_rd - B_BASE) + i * 512);
-        gs_split8(f32x4{bw[0], bw[1], bw[2], bw[3]}, f32x4{bw[4], bw[5], bw[6], bw[7]}, fb[set][0], fb[set][1], fb[set][2]);
+        t3_store_pieces<decltype(second_buf)::value ? A_BYTES : 0>(a_wr0, u32x2{h0, h1}, u32x2{m0_, m1_}, u32x2{l0, l1});
     };
     // ---- prologue: ONE round trip -- A of stages 0..5 and B of stages 0..2 requested together; stages 0, 1 cut and stored
     //      (their sets re-requested for stages 6, 7), the fragments of stage 0 read and cut
@@ -832,7 +926,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     dma_b(2, 2);
     {
         f32x4 t0, t1;
-        const int k0 = min(4 * aq, K4 - 4), k1 = min(F3_KS + 4 * aq, K4 - 4);
+        const int k0 = min(4 * aq, K4 - 4), k1 = min(T3_KS + 4 * aq, K4 - 4);
 #ifdef F3_DIAG_NOGA
         t0 = t1 = f32x4{(float)k0, 1.f, 2.f, (float)k1};
 #else
@@ -847,9 +941,10 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
         ra[1] = t1; cut_store_a(std::false_type{}, std::true_type{}, 1, 1);
         ra[0] = s0; ra[1] = s1;                                // (sets 0, 1 hold stages 4, 5; sets 2, 3 stages 2, 3)
     }
-    F3_BARRIER(0);
+    T3_BARRIER(0);                                             // (nothing in flight: the wait above was for everything)
     F3_STAMP(2);
-    read_cut_frags(0, smem, smem + B_BASE);
+    t3_read_a_frags(fa[0], smem + a_rd);
+    t3_read_cut_b<false>(fb[0], smem + b_rd, 0);
     // The K loop runs in rings of four stages (the register sets are indexed statically: stage ss takes the sets of ss % 4), first
     // STEADY rings, then CAREFUL stages, one stage body for both:
     //   steady  while every request a ring issues lies wholly inside K -- A of stage ss + 6, B of stage ss + 3, the cut of stage
@@ -859,15 +954,15 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     //           plus the lane's constant 32-bit byte offset; nothing beyond column K - 1 is requested;
     //   careful the remaining stages, selects and clamped addresses as in the prologue; the last ring is left behind its
     //           stages % 4 -th stage (no stage of zeros is computed).
-    // Both kinds issue B, B, A in this order, once per stage: F3_BARRIER(4)'s accounting holds across the seam.
+    // Both kinds issue B, B, A in this order, once per stage: T3_BARRIER(4)'s accounting holds across the seam.
     // A-piece buffers: stage ss + 1 is read from buffer (ss + 1) & 1, stage ss + 2 written to buffer ss & 1 (= the one stage ss was
     // read from, during stage ss - 1: every wave has passed a barrier since); B slots are (stage) % 4.
-    const int whole_stages = K / F3_KS;
-    // (a lane's B offset (lh * ldw + bcol) * 4 must fit 32 bits: leading dimensions beyond 2^29 take the careful stages throughout)
+    const int whole_stages = K / T3_KS;
+    // (t3_dma_pair's 32-bit lane offset: leading dimensions from 2^29 on take the careful stages throughout)
     const int s_steady = (whole_stages >= 10 && ldw < (1 << 29)) ? ((whole_stages - 10) & ~3) + 4 : 0;
-    const float* pa = xrow + 4 * aq + 6 * F3_KS;                                     // A of stage s + 6
-    const unsigned char* wb = reinterpret_cast<const unsigned char*>(T.W) + (int64_t)(3 * F3_KS + 4 * wave) * ldw * 4;   // B of stage s + 3: the
-    const int64_t wb_pair = (int64_t)ldw * 8, wb_stage = (int64_t)ldw * (F3_KS * 4);                                      // wave's first chunk
+    const float* pa = xrow + 4 * aq + 6 * T3_KS;                                     // A of stage s + 6
+    const unsigned char* wb = reinterpret_cast<const unsigned char*>(T.W) + (int64_t)(3 * T3_KS + 4 * wave) * ldw * 4;   // B of stage s + 3: the
+    const int64_t wb_pair = (int64_t)ldw * 8, wb_stage = (int64_t)ldw * (T3_KS * 4);                                      // wave's first chunk
     const uint32_t wb_lane = (uint32_t)(lh * ldw + bcol) * 4u;
     const uint32_t wb_lds = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(B_BASE + 2 * wave * 1024));   // the wave's first chunk of slot 0
     auto stage = [&](auto q4_, auto steady_, const int ss) __attribute__((always_inline)) {
@@ -887,7 +982,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
 #define F3_RA(i, p) fa[r ^ 1][i][p] = u32x4{(unsigned)(p), (unsigned)(uintptr_t)na, 2u, (unsigned)tid}; F3_SB
 #define F3_RW(i) bw[i] = __uint_as_float((unsigned)(uintptr_t)nb + i);
 #else
-#define F3_RA(i, p) fa[r ^ 1][i][p] = *reinterpret_cast<const u32x4*>(na + a_rd + (i) * (32 * F3_LDA * 2) + (p) * A_PLANE); F3_SB
+#define F3_RA(i, p) fa[r ^ 1][i][p] = *reinterpret_cast<const u32x4*>(na + a_rd + (i) * (32 * T3_LDA * 2) + (p) * A_PLANE); F3_SB
 #define F3_RW(i) bw[i] = *reinterpret_cast<const float*>(nb + (i) * 512);
 #endif
             float bw[8];
@@ -927,17 +1022,13 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
             F3_MM(sml, 0, 1, 0)
             if constexpr (steady) {
 #ifndef F3_DIAG_NOGB
-                // (by hand: the builtin forms base + lane offset as a 64-bit vector add per request; M0 = the chunk's LDS address)
-                asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
-                             "s_add_i32 m0, %3, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
-                             :: "v"(wb_lane), "s"(wb), "s"(wb + wb_pair), "s"(wb_lds), "n"(((q4 + 3) & 3) * B_BYTES),
-                                "n"(((q4 + 3) & 3) * B_BYTES + 1024) : "scc");      // (M0: the compiler sets it in front of every request of its own)
+                t3_dma_pair(wb_lane, wb, wb_pair, wb_lds, ((q4 + 3) & 3) * B_BYTES);
 #endif
                 wb += wb_stage;
 #ifdef F3_DIAG_NOGA
                 ra[as] = f32x4{(float)ss, 1.f, 2.f, (float)tid};
 #else
-                asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(ra[as]) : "v"(pa), "n"(q4 * F3_KS * 4));
+                asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(ra[as]) : "v"(pa), "n"(q4 * T3_KS * 4));
 #endif
             } else {
                 dma_b(ss + 3, (q4 + 3) & 3);
@@ -956,7 +1047,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
             asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
             F3_STAMP(9 + 3 * ss);
 #endif
-            F3_BARRIER(4);
+            T3_BARRIER(4, "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]));
             F3_STAMP(10 + 3 * ss);
             F3_SB
 #undef F3_MM
@@ -974,7 +1065,7 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
         stage(q1, std::true_type{}, s + 1);
         stage(q2, std::true_type{}, s + 2);
         stage(q3, std::true_type{}, s + 3);
-        pa += 4 * F3_KS;
+        pa += 4 * T3_KS;
     }
     for (; s < stages; s += 4) {                                // (the last ring ends behind stage stages - 1: no stage of zeros)
         stage(q0, std::false_type{}, s);
@@ -987,43 +1078,28 @@ __global__ __launch_bounds__(256) void sage_tiled3_fwd_kernel(const Fwd3Args g, 
     }
     F3_STAMP(3);
     // The look-ahead requests of the last stages are still in flight INTO the four staging sets, and the compiler does not know: the
-    // wait names the sets ("+v"), as in wgrad_tiled3_acut_kernel, so that they stay reserved up to here whatever the scheduler
-    // moves in front of it (the sets are dead behind the last cut otherwise).
+    // wait names the sets ("+v"), as T3_BARRIER does, so that they stay reserved up to here whatever the scheduler moves in front
+    // of it (the sets are dead behind the last cut otherwise).
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(ra[0]), "+v"(ra[1]), "+v"(ra[2]), "+v"(ra[3]) :: "memory");
     __syncthreads();
     F3_STAMP(4);
     // ---- the wave's 64 x 32 tile: bias + activation, then through a wave-private LDS staging tile to 16-byte row segments
-    float* otile = reinterpret_cast<float*>(smem) + wave * (64 * 36);     // [64 rows][32 + 4 pad] per wave
     const int col_off = term * N;
-    {
-        const int col = n0 + 32 * wn + l31;
-        const float bv = (g.bias && col < N) ? g.bias[col_off + col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float v = (acc[i][e] + sml[i][e]) + bv;
-                if (g.act == GS_ACT_RELU) v = fmaxf(v, 0.f);
-                otile[(32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh) * 36 + l31] = v;     // C/D layout: row = (e&3) + 8 (e>>2) + 4 (lane>>5)
-            }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (wave-private region: the wave's own LDS writes before its reads)
+    const int col = n0 + 32 * wn + l31;
+    const float bv = (g.bias && col < N) ? g.bias[col_off + col] : 0.f;
+    const bool relu = g.act == GS_ACT_RELU;
+    float* otile = t3_stage_tile(smem, wave, lane, acc, sml, [=](float v) {
+        v += bv;
+        return relu ? fmaxf(v, 0.f) : v;
+    });
     const int c4 = (lane & 7) * 4, r0 = lane >> 3;
     const int colg = n0 + 32 * wn + c4;
 #pragma unroll
     for (int itr = 0; itr < 8; ++itr) {
         const int r = 8 * itr + r0;
         const int row = m0 + r;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(otile + r * 36 + c4);
-        if (row < mend) {
-            float* dst = g.C + (int64_t)row * g.ldc + col_off + colg;
-            if (colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
-            else {
-                if (colg < N) dst[0] = v.x;
-                if (colg + 1 < N) dst[1] = v.y;
-                if (colg + 2 < N) dst[2] = v.z;
-            }
-        }
+        const f32x4 v = t3_tile_seg(otile, lane, itr);
+        if (row < mend) t3_store_row4(g.C + (int64_t)row * g.ldc + col_off + colg, v, colg, N, true);
     }
     // ---- the layer-1 neighbor means of a hop tile's whole groups, from the staging tile (wave-private: no barrier): 8 lanes x
     //      float4 = the wave's 32 columns, lane >> 3 = the group; zero start, j = 0..s-1, ONE multiply by 1/s -- the expression
@@ -1099,7 +1175,7 @@ static int fwd_tiled3_impl(const float* self, int64_t ld_self, const int32_t* se
     if (rc != GS_OK) return rc;
     const int64_t blocks = g.n_tiles + gs_ceil_div(waves, 4);
     GS_REQUIRE(blocks > 0 && blocks < (1ll << 31), "gs_sage_dense_fwd_tiled3: grid too large");
-    const size_t lds = F3_NA * (3 * F3_BM * F3_LDA * 2) + F3_NB * (F3_KS * 128 * 4);
+    const size_t lds = T3_LDS_BYTES;
     GS_LDS_ATTR(lds, sage_tiled3_fwd_kernel);
     hipLaunchKernelGGL(sage_tiled3_fwd_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, g, J);
     GS_LAUNCH_CHECK("sage_tiled3_fwd_kernel");
@@ -1144,7 +1220,6 @@ extern "C" int gs_sage_dense_fwd_tiled3_means(const float* self, int64_t ld_self
 #ifndef W3_NS
 #define W3_NS 4
 #endif
-#define W3_KS 16           // k per stage
 #define W3_MAXROWS 1024
 #define W3_MAXP 12
 struct Wg3Prob {
@@ -1162,55 +1237,90 @@ struct Wg3Args {
     int32_t n, n_items;
 };
 
+// ---- shared by the two weight-gradient kernels (the rest: "shared by the tiled3 kernels", above the forward)
+// Riders behind the contraction workgroups, r = the rider workgroup's number: first the fan-out SAMPLER of a later mini-batch, one
+// root per WAVE, four per rider slot (five dependent round trips of almost no work: as a rider of the optimizer launch it was what
+// that launch waited for -- 8 us against the optimizer's own 5.5 -- here it ends long before the contraction does); then
+// gather+mean waves.
+__device__ __forceinline__ void t3_wgrad_riders(const FanoutArgs& F, const CoGatherS& J, const int64_t r, unsigned char* smem,
+                                                const int wave, const int lane) {
+#ifdef W3_NO_SAMPLER              // diagnostics switch (both forms)
+    const int64_t sblocks = 0;
+#else
+    const int64_t sblocks = (F.B + 3) >> 2;
+    if (r < sblocks) {
+        const int64_t root = 4 * r + wave;
+        if (root < F.B) {
+            int32_t* ints = reinterpret_cast<int32_t*>(smem) + wave * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL);   // (the wave's
+            sample_fanout_root<GS_FANOUT_LDS_SMALL, true>(F, root,                                              //  share of the launch's LDS)
+                                                          reinterpret_cast<int32_t (*)[GS_FANOUT_LDS_SMALL]>(ints),
+                                                          reinterpret_cast<int32_t (*)[GS_LAW_COLS]>(ints + 2 * GS_FANOUT_LDS_SMALL));
+        }
+        return;
+    }
+#endif
+    run_gather_item<T3_RIDER_U>(J, (r - sblocks) * 4 + wave, lane);
+}
+
+// A contraction workgroup's work item: (64 m x 128 n tile, reduction slice z) of problem pi.  Consecutive LOGICAL items are the m
+// tiles of one slice (the same dZ rows): they share an XCD's L2 (t3_logical_block).
+struct Wg3Item {
+    int pi, z, tile_m, tile_n, m0, n0;
+    int rb, re, len;       // the slice's rows [rb, re); len = 0: an empty slice still writes its slab (zeros)
+    int rlast;             // every row read is clamped to a valid one
+    int stages, stages4;   // 16-k stages of the slice | rounded up to whole rings of four
+};
+__device__ __forceinline__ Wg3Item t3_wgrad_item(const Wg3Args& G) {
+    const int item = t3_logical_block(G.n_items);
+    Wg3Item it;
+    it.pi = 0;
+    while (it.pi + 1 < G.n && item >= G.p[it.pi + 1].item_start) ++it.pi;
+    const Wg3Prob& q = G.p[it.pi];
+    const int local = item - q.item_start;
+    const int tiles = q.tiles_m * q.tiles_n;
+    it.z = local / tiles;
+    const int tt = local - it.z * tiles;
+    it.tile_m = tt / q.tiles_n; it.tile_n = tt - it.tile_m * q.tiles_n;
+    it.m0 = it.tile_m * 64; it.n0 = it.tile_n * 128;
+    it.rb = it.z * q.kchunk; it.re = min(it.rb + q.kchunk, q.n);
+    it.len = max(it.re - it.rb, 0);
+    it.rlast = max(it.re, 1) - 1;
+    it.stages = (it.len + T3_KS - 1) / T3_KS;
+    it.stages4 = (it.stages + 3) & ~3;
+    return it;
+}
+
+// The wave's 64 x 32 tile -> its slab, through the staging tile (16-byte row segments where the slab's rows are 16-byte aligned)
+__device__ __forceinline__ void t3_wgrad_store(const Wg3Prob& q, const Wg3Item& it, unsigned char* smem, const int wave, const int lane,
+                                               const f32x16 (&acc)[2], const f32x16 (&sml)[2]) {
+    const float* otile = t3_stage_tile(smem, wave, lane, acc, sml, [](const float v) { return v; });
+    float* __restrict__ S = q.slabs + (int64_t)it.z * q.d * q.ld_slab;
+    const bool vec = (q.ld_slab & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
+    const int c4 = (lane & 7) * 4, r0 = lane >> 3;
+    const int colg = it.n0 + 32 * wave + c4;
+    const int N = q.out_dim;                                   // (read once: behind a store the compiler reads it again)
+#pragma unroll
+    for (int itr = 0; itr < 8; ++itr) {
+        const int rr = 8 * itr + r0;
+        const int row = it.m0 + rr;
+        const f32x4 v = t3_tile_seg(otile, lane, itr);
+        if (row < q.d) t3_store_row4(S + (int64_t)row * q.ld_slab + colg, v, colg, N, vec);
+    }
+}
+
 __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, const FanoutArgs F, const CoGatherS J) {
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int A_BYTES = W3_KS * 64 * 4, B_BYTES = W3_KS * 128 * 4, S_BYTES = A_BYTES + B_BYTES;
+    constexpr int A_BYTES = T3_KS * 64 * 4, B_BYTES = T3_KS * 128 * 4, S_BYTES = A_BYTES + B_BYTES;
     constexpr int IDX_BASE = W3_NS * S_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= G.n_items) {
-        // Riders behind the contraction workgroups: first the fan-out SAMPLER of a later mini-batch, one root per workgroup (five
-        // dependent round trips of almost no work: as a rider of the optimizer launch it was what that launch waited for -- 8 us
-        // against the optimizer's own 5.5 -- here it ends long before the contraction does); then gather+mean waves.
-        const int64_t r = (int64_t)blockIdx.x - G.n_items;
-#ifdef W3_NO_SAMPLER              // diagnostics switch
-        const int64_t sblocks = 0;
-        if (false) {
-#else
-        const int64_t sblocks = (F.B + 3) >> 2;                     // one root per WAVE: four per rider slot
-        if (r < sblocks) {
-#endif
-            const int64_t root = 4 * r + wave;
-            if (root < F.B) {
-                int32_t* ints = reinterpret_cast<int32_t*>(smem) + wave * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL);   // (the wave's
-                sample_fanout_root<GS_FANOUT_LDS_SMALL, true>(F, root,                                              //  share of the launch's LDS)
-                                                              reinterpret_cast<int32_t (*)[GS_FANOUT_LDS_SMALL]>(ints),
-                                                              reinterpret_cast<int32_t (*)[GS_LAW_COLS]>(ints + 2 * GS_FANOUT_LDS_SMALL));
-            }
-            return;
-        }
-        run_gather_item<T3_RIDER_U>(J, (r - sblocks) * 4 + wave, lane);
+        t3_wgrad_riders(F, J, (int64_t)blockIdx.x - G.n_items, smem, wave, lane);
         return;
     }
     const int l31 = lane & 31, lh = lane >> 5;
-    // XCD-aware: block b runs on XCD b % 8; consecutive LOGICAL items (the m tiles of one slice: the same dZ rows) share an L2
-    const int nwg = G.n_items;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, lcl = blockIdx.x >> 3;
-    const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lcl;
-    int pi = 0;
-    while (pi + 1 < G.n && item >= G.p[pi + 1].item_start) ++pi;
-    const Wg3Prob& q = G.p[pi];
-    const int local = item - q.item_start;
-    const int tiles = q.tiles_m * q.tiles_n;
-    const int z = local / tiles;
-    const int tt = local - z * tiles;
-    const int tile_m = tt / q.tiles_n, tile_n = tt - tile_m * q.tiles_n;
-    const int m0 = tile_m * 64, n0 = tile_n * 128;
-    const int rb = z * q.kchunk, re = min(rb + q.kchunk, q.n);
-    const int len = max(re - rb, 0);                           // (an empty slice still writes its slab: zeros)
-    const int rlast = max(re, 1) - 1;                          // every row read is clamped to a valid one
-    const int stages = (len + W3_KS - 1) / W3_KS;
-    const int stages4 = (stages + 3) & ~3;
+    const Wg3Item it = t3_wgrad_item(G);
+    const Wg3Prob& q = G.p[it.pi];
+    const int m0 = it.m0, n0 = it.n0, rb = it.rb, len = it.len, rlast = it.rlast, stages4 = it.stages4;
     // the slice's source rows (<= W3_MAXROWS), once: the row ids of a gathered problem, else the rows themselves -- one code path
     int32_t* idxs = reinterpret_cast<int32_t*>(smem + IDX_BASE);
 #pragma unroll
@@ -1225,29 +1335,26 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
     const float* __restrict__ zcol = q.dZ + min(n0 + 4 * l31, q.zcols - 4);            //  computed and never stored)
     const int lda = q.lda, ldz = q.ldz;
     auto a_row = [&](const int s) -> int64_t {                 // source row of this lane's A request of stage s
-        return (int64_t)idxs[min(W3_KS * s + akk, W3_MAXROWS - 1)];
+        return (int64_t)idxs[min(T3_KS * s + akk, W3_MAXROWS - 1)];
     };
     auto dma = [&](const int s, const int slot, const int64_t arow) {
         unsigned char* base = smem + slot * S_BYTES;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c = 2 * wave + i;
-            const int r = min(rb + W3_KS * s + 2 * c + lh, rlast);
+            const int r = min(rb + T3_KS * s + 2 * c + lh, rlast);
             __builtin_amdgcn_global_load_lds(zcol + (int64_t)r * ldz, (lds_ptr_t)(base + A_BYTES + c * 1024), 16, 0, 0);
         }
         __builtin_amdgcn_global_load_lds(acol + arow * lda, (lds_ptr_t)(base + wave * 1024), 16, 0, 0);
     };
     const int wn = wave;                                       // 32-column group
     f32x16 acc[2], sml[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[i][e] = 0.f; sml[i][e] = 0.f; }
+    t3_zero(acc, sml);
     u32x4 fa[2][2][3], fb[2][3];
     const int kfrag = 8 * lh;                                  // first of this lane's 8 k inside a stage
     const int a_rd = (kfrag * 64 + l31) * 4;                   // + i k rows (256 bytes each), + 128 for the second m block
     const int b_rd = A_BYTES + (kfrag * 128 + 32 * wn + l31) * 4;      // + i k rows (512 bytes each)
-    // stage barrier by hand, see sage_tiled3_fwd_kernel: counted vmcnt (younger requests stay in flight) + lgkmcnt(0) + s_barrier
+    // T3_BARRIER's count: the W3_NS - 3 younger stages' requests, 3 each (every request goes to LDS: no register list)
 #if W3_NS == 4
 #define W3_INFLIGHT 3
 #elif W3_NS == 5
@@ -1257,22 +1364,13 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
 #else
 #define W3_INFLIGHT 15
 #endif
-#define W3_WAIT_STR2(x) #x
-#define W3_WAIT_STR(x) W3_WAIT_STR2(x)
-#define W3_BARRIER() do { asm volatile("s_waitcnt vmcnt(" W3_WAIT_STR(W3_INFLIGHT) ") lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); \
-                          asm volatile("" ::: "memory"); } while (0)
     auto read_cut_frags = [&](const int set, const unsigned char* slot, const int s) {
-        float bw[8], aw[2][8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bw[i] = *reinterpret_cast<const float*>(slot + b_rd + i * 512);
+        float aw[2][8];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int i = 0; i < 8; ++i) aw[j][i] = *reinterpret_cast<const float*>(slot + a_rd + j * 128 + i * 256);
-        const int lim = len - W3_KS * s - kfrag;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
-        gs_split8(f32x4{bw[0], bw[1], bw[2], bw[3]}, f32x4{bw[4], bw[5], bw[6], bw[7]}, fb[set][0], fb[set][1], fb[set][2]);
+        t3_read_cut_b<true>(fb[set], slot + b_rd, len - T3_KS * s - kfrag);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
             gs_split8(f32x4{aw[j][0], aw[j][1], aw[j][2], aw[j][3]}, f32x4{aw[j][4], aw[j][5], aw[j][6], aw[j][7]},
@@ -1282,7 +1380,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
 #pragma unroll
     for (int s = 0; s < W3_NS - 1; ++s) dma(s, s, a_row(s));
     int64_t arow_nxt = a_row(W3_NS - 1);
-    W3_BARRIER();                                              // stages 0 and 1 have landed (everyone's share of them)
+    T3_BARRIER(W3_INFLIGHT);                                              // stages 0 and 1 have landed (everyone's share of them)
     read_cut_frags(0, smem, 0);
     int slot_rd = 1, slot_wr = W3_NS - 1;                      // slot of stage ss + 1 | of stage ss + W3_NS - 1
     // The stages whose look-ahead reads lie wholly inside the slice run WITHOUT the row mask (a branch inside a stage would break the
@@ -1311,7 +1409,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
             W3_SB
             W3_MM(acc, 0, 0, 0)
             if constexpr (decltype(masked)::value) {           // the slice ends inside stage ss + 1, or before it
-                const int lim = len - W3_KS * (ss + 1) - kfrag;
+                const int lim = len - T3_KS * (ss + 1) - kfrag;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
             }
@@ -1357,7 +1455,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
             W3_MM(sml, 1, 1, 0)
             arow_nxt = a_row(ss + W3_NS);
             // stage ss + 2 (what the next stage reads) has landed: behind it only the W3_NS - 3 younger stages' requests, 3 each
-            W3_BARRIER();
+            T3_BARRIER(W3_INFLIGHT);
             W3_SB
 #undef W3_MM
 #undef W3_RB
@@ -1368,41 +1466,12 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
         }
     }
     };
-    const int s_plain = max(len / W3_KS - 1, 0) & ~3;          // stages ss < s_plain read a full stage ss + 1
+    const int s_plain = max(len / T3_KS - 1, 0) & ~3;          // stages ss < s_plain read a full stage ss + 1
     run(std::false_type{}, 0, s_plain);
     run(std::true_type{}, s_plain, stages4);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the look-ahead requests of the last stages
     __syncthreads();
-    // ---- the wave's 64 x 32 tile -> its slab, through a wave-private LDS staging tile (16-byte row segments)
-    float* otile = reinterpret_cast<float*>(smem) + wave * (64 * 36);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-            otile[(32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh) * 36 + l31] = acc[i][e] + sml[i][e];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (wave-private region: the wave's own writes before its reads)
-    float* __restrict__ S = q.slabs + (int64_t)z * q.d * q.ld_slab;
-    const bool vec = (q.ld_slab & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
-    const int c4 = (lane & 7) * 4, r0 = lane >> 3;
-    const int colg = n0 + 32 * wn + c4;
-    const int N = q.out_dim;
-#pragma unroll
-    for (int itr = 0; itr < 8; ++itr) {
-        const int rr = 8 * itr + r0;
-        const int row = m0 + rr;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(otile + rr * 36 + c4);
-        if (row < q.d) {
-            float* dst = S + (int64_t)row * q.ld_slab + colg;
-            if (vec && colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
-            else {
-                if (colg < N) dst[0] = v.x;
-                if (colg + 1 < N) dst[1] = v.y;
-                if (colg + 2 < N) dst[2] = v.z;
-                if (colg + 3 < N) dst[3] = v.w;
-            }
-        }
-    }
-#undef W3_BARRIER
+    t3_wgrad_store(q, it, smem, wave, lane, acc, sml);
 #undef W3_INFLIGHT
 }
 
@@ -1422,58 +1491,26 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_kernel(const Wg3Args G, cons
 // shares its CU with two rider workgroups).
 // Banks (tests/test_wgrad_acut_layout.py): a 16-lane group of the fragment read covers 16 distinct 16-byte units of the 64 banks;
 // the 16 lanes of a piece-write phase (rows m .. m + 15 at 48-byte pitch, one 8-byte unit each) take 32 distinct banks of 64.
-#define W3A_LDA 24         // bf16 per LDS row of an A piece plane: 16 k + 8 pad
-#define W3A_NA 2           // A piece buffers (stage s + 1 being read, stage s + 2 being written)
-#define W3A_NB 4           // raw dZ stages in flight
 #define W3A_NR 4           // A stages in flight in registers
-#define W3A_LDS_BYTES (W3A_NA * 3 * 64 * W3A_LDA * 2 + W3A_NB * W3_KS * 128 * 4)
-static_assert(W3A_LDS_BYTES <= 53248, "a host workgroup must leave room for two rider workgroups on its CU");
-static_assert(W3_MAXROWS <= 64 * W3_KS, "one lane per stage holds the slice's row ids");
+static_assert(W3_MAXROWS <= 64 * T3_KS, "one lane per stage holds the slice's row ids");
 
 __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G, const FanoutArgs F, const CoGatherS J) {
-    typedef __attribute__((address_space(3))) void* lds_ptr_t;
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int A_PLANE = 64 * W3A_LDA * 2, A_BYTES = 3 * A_PLANE, B_BYTES = W3_KS * 128 * 4, B_BASE = W3A_NA * A_BYTES;
+    constexpr int A_PLANE = T3_A_PLANE, A_BYTES = T3_A_BYTES, B_BYTES = T3_B_BYTES, B_BASE = T3_B_BASE;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if ((int)blockIdx.x >= G.n_items) {                             // riders: as in wgrad_tiled3_kernel
-        const int64_t r = (int64_t)blockIdx.x - G.n_items;
-        const int64_t sblocks = (F.B + 3) >> 2;
-        if (r < sblocks) {
-            const int64_t root = 4 * r + wave;
-            if (root < F.B) {
-                int32_t* ints = reinterpret_cast<int32_t*>(smem) + wave * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL);
-                sample_fanout_root<GS_FANOUT_LDS_SMALL, true>(F, root, reinterpret_cast<int32_t (*)[GS_FANOUT_LDS_SMALL]>(ints),
-                                                              reinterpret_cast<int32_t (*)[GS_LAW_COLS]>(ints + 2 * GS_FANOUT_LDS_SMALL));
-            }
-            return;
-        }
-        run_gather_item<T3_RIDER_U>(J, (r - sblocks) * 4 + wave, lane);
+    if ((int)blockIdx.x >= G.n_items) {
+        t3_wgrad_riders(F, J, (int64_t)blockIdx.x - G.n_items, smem, wave, lane);
         return;
     }
     const int l31 = lane & 31, lh = lane >> 5;
-    const int nwg = G.n_items;                                      // XCD-aware item order: as in wgrad_tiled3_kernel
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, lcl = blockIdx.x >> 3;
-    const int item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + lcl;
-    int pi = 0;
-    while (pi + 1 < G.n && item >= G.p[pi + 1].item_start) ++pi;
-    const Wg3Prob& q = G.p[pi];
-    const int local = item - q.item_start;
-    const int tiles = q.tiles_m * q.tiles_n;
-    const int z = local / tiles;
-    const int tt = local - z * tiles;
-    const int tile_m = tt / q.tiles_n, tile_n = tt - tile_m * q.tiles_n;
-    const int m0 = tile_m * 64, n0 = tile_n * 128;
-    const int rb = z * q.kchunk, re = min(rb + q.kchunk, q.n);
-    const int len = max(re - rb, 0);                           // (an empty slice still writes its slab: zeros)
-    const int rlast = max(re, 1) - 1;                          // every row read is clamped to a valid one
-    const int stages = (len + W3_KS - 1) / W3_KS;
-    const int stages4 = (stages + 3) & ~3;
+    const Wg3Item it = t3_wgrad_item(G);
+    const Wg3Prob& q = G.p[it.pi];
+    const int m0 = it.m0, n0 = it.n0, rb = it.rb, len = it.len, rlast = it.rlast, stages4 = it.stages4;
     // ---- the source rows of this wave's A requests: lane L holds those of stage L (ids of a gathered problem, else the rows)
     int32_t rid[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int rr = min(rb + W3_KS * lane + 4 * wave + j, rlast);
+        const int rr = min(rb + T3_KS * lane + 4 * wave + j, rlast);
         rid[j] = q.a_idx ? q.a_idx[rr] : rr;
     }
     // ---- requests.  dZ: wave w moves chunks 2 w, 2 w + 1 of a stage (chunk = 2 k rows x 128 n = 1 KB, lane-linear in LDS)
@@ -1483,12 +1520,12 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c = 2 * wave + i;
-            const int r = min(rb + W3_KS * s + 2 * c + lh, rlast);
+            const int r = min(rb + T3_KS * s + 2 * c + lh, rlast);
             __builtin_amdgcn_global_load_lds(zcol + (int64_t)r * ldz, (lds_ptr_t)(smem + B_BASE + slot * B_BYTES + c * 1024), 16, 0, 0);
         }
     };
     // A: row base in SGPRs (64-bit: tables beyond 4 GB), the lane's column as a 32-bit byte offset from the tile's first column.
-    // Hand-written requests as in sage_tiled3_fwd_kernel: the compiler adds no wait of its own; W3A_BARRIER's counted vmcnt
+    // Hand-written requests as in sage_tiled3_fwd_kernel: the compiler adds no wait of its own; T3_BARRIER's counted vmcnt
     // guarantees them and names the registers it releases ("+v"), so nothing may touch them between request and wait.
     const float* __restrict__ abase = q.A + m0;
     const uint32_t acol = (uint32_t)(min(m0 + lane, lda - 1) - m0) * 4u;
@@ -1504,33 +1541,19 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
     };
     const int wn = wave;                                       // 32-column group
     f32x16 acc[2], sml[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[i][e] = 0.f; sml[i][e] = 0.f; }
+    t3_zero(acc, sml);
     u32x4 fa[2][2][3], fb[2][3];
     const int kfrag = 8 * lh;                                  // first of this lane's 8 k inside a stage
-    const int a_rd = (l31 * W3A_LDA + kfrag) * 2;              // + 32 i rows, + piece plane
+    const int a_rd = (l31 * T3_LDA + kfrag) * 2;               // + 32 i rows, + piece plane
     const int b_rd = B_BASE + (kfrag * 128 + 32 * wn + l31) * 4;       // + slot, + i k rows (512 bytes each)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_ptr_t)smem;
-    const uint32_t a_wr = lds0 + (uint32_t)((lane * W3A_LDA + 4 * wave) * 2);          // + buffer
-    // the three ds_write_b64 of a thread's 4 k x 3 pieces (hand-written, no "memory": see sage_tiled3_fwd_kernel's cut_store_a)
-    auto store_a = [&](const int buf_off, const u32x2 vh, const u32x2 vm, const u32x2 vl) {
-        asm volatile("ds_write_b64 %0, %1\n\tds_write_b64 %0, %2 offset:%4\n\tds_write_b64 %0, %3 offset:%5"
-                     :: "v"(a_wr + (uint32_t)buf_off), "v"(vh), "v"(vm), "v"(vl), "n"(A_PLANE), "n"(2 * A_PLANE));
-    };
+    const uint32_t a_wr = lds0 + (uint32_t)((lane * T3_LDA + 4 * wave) * 2);          // + buffer
     auto cut_store_a = [&](const float x0, const float x1, const float x2, const float x3, const int buf_off) {
         uint32_t h0, m0_, l0, h1, m1_, l1;
         gs_split2(x0, x1, h0, m0_, l0);
         gs_split2(x2, x3, h1, m1_, l1);
-        store_a(buf_off, u32x2{h0, h1}, u32x2{m0_, m1_}, u32x2{l0, l1});
+        t3_store_pieces<0>(a_wr + (uint32_t)buf_off, u32x2{h0, h1}, u32x2{m0_, m1_}, u32x2{l0, l1});
     };
-    // Stage barrier by hand (see F3_BARRIER).  What the NEXT stage consumes has landed: the raw dZ of stage ss + 2 (requested
-    // during stage ss - 1) and the A registers it cuts (stage ss + 3, requested during stage ss - 3).  A thread's requests retire
-    // IN ORDER and a stage issues its two DMAs and THEN its four A requests: behind dZ(ss + 2) lie the four A requests of that
-    // stage and this stage's six -- vmcnt(10); A(ss + 3) is older than all of them.
-#define W3A_BARRIER(cnt, r0, r1, r2, r3) do { asm volatile("s_waitcnt vmcnt(" #cnt ") lgkmcnt(0)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) \
-                                                           :: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
     // ---- prologue: ONE round trip -- dZ of stages 0..2 and A of stages 0..5 requested together; the pieces of stages 0, 1 stored,
     //      stage 0's fragments read and cut
     dma_b(0, 0);
@@ -1551,22 +1574,9 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
         cut_store_a(t0[0], t0[1], t0[2], t0[3], 0);
         cut_store_a(t1[0], t1[1], t1[2], t1[3], A_BYTES);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) fa[0][i][p] = *reinterpret_cast<const u32x4*>(smem + a_rd + i * (32 * W3A_LDA * 2) + p * A_PLANE);
-        float bw[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bw[i] = *reinterpret_cast<const float*>(smem + b_rd + i * 512);
-        const int lim = len - kfrag;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
-        gs_split8(f32x4{bw[0], bw[1], bw[2], bw[3]}, f32x4{bw[4], bw[5], bw[6], bw[7]}, fb[0][0], fb[0][1], fb[0][2]);
-    }
+    T3_BARRIER(0);                                             // (nothing in flight: the wait above was for everything)
+    t3_read_a_frags(fa[0], smem + a_rd);
+    t3_read_cut_b<true>(fb[0], smem + b_rd, len - kfrag);
     // byte offsets of the piece buffers of stage ss + 1 | ss + 2 (the latter = the one stage ss was read from, during stage
     // ss - 1: every wave has passed a barrier since); dZ slots are (stage) % 4
     int oa_nxt = A_BYTES, oa_nn = 0;
@@ -1574,10 +1584,10 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
     // (and the zero padding of the ring) the masked copy.
     // The copy without the mask is also the one without clamps in the vector stream: it runs while every dZ request of a ring lies
     // wholly inside the slice (stage ss + 3 for its last stage ss = s + 3: 16 (s + 7) <= len).  Its dZ requests are a wave-uniform
-    // 64-bit base, advanced by 16 rows per stage on the scalar pipe, plus the lane's constant 32-bit byte offset (by hand, as in
-    // sage_tiled3_fwd_kernel's steady stages); the A requests were scalar arithmetic behind their four v_readlane already.
-    const unsigned char* zb = reinterpret_cast<const unsigned char*>(q.dZ) + (int64_t)(rb + 3 * W3_KS + 4 * wave) * ldz * 4;
-    const int64_t zb_pair = (int64_t)ldz * 8, zb_stage = (int64_t)ldz * (W3_KS * 4);
+    // 64-bit base, advanced by 16 rows per stage on the scalar pipe, plus the lane's constant 32-bit byte offset (t3_dma_pair, as
+    // in sage_tiled3_fwd_kernel's steady stages); the A requests were scalar arithmetic behind their four v_readlane already.
+    const unsigned char* zb = reinterpret_cast<const unsigned char*>(q.dZ) + (int64_t)(rb + 3 * T3_KS + 4 * wave) * ldz * 4;
+    const int64_t zb_pair = (int64_t)ldz * 8, zb_stage = (int64_t)ldz * (T3_KS * 4);
     const uint32_t zb_lane = (uint32_t)(lh * ldz + min(n0 + 4 * l31, q.zcols - 4)) * 4u;
     const uint32_t zb_lds = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(B_BASE + 2 * wave * 1024));
     auto run = [&](auto masked, const int s_begin, const int s_end) {
@@ -1591,7 +1601,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
             const unsigned char* nb = smem + ((q4 + 1) & 3) * B_BYTES + b_rd;
 #define W3A_SB __builtin_amdgcn_sched_barrier(0);
 #define W3A_MM(dst, i, pa, pb) dst[i] = gs_mfma_bf16(fa[r][i][pa], fb[r][pb], dst[i]); W3A_SB
-#define W3A_RA(i, p) fa[r ^ 1][i][p] = *reinterpret_cast<const u32x4*>(na + (i) * (32 * W3A_LDA * 2) + (p) * A_PLANE); W3A_SB
+#define W3A_RA(i, p) fa[r ^ 1][i][p] = *reinterpret_cast<const u32x4*>(na + (i) * (32 * T3_LDA * 2) + (p) * A_PLANE); W3A_SB
 #define W3A_RB(i) bw[i] = *reinterpret_cast<const float*>(nb + (i) * 512);
             float bw[8];
             uint32_t ph[4], pm[4], pl[4];
@@ -1607,7 +1617,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
             W3A_MM(acc, 1, 0, 0) W3A_RA(0, 2)
             W3A_MM(sml, 0, 2, 0) W3A_RA(1, 0)
             if constexpr (decltype(masked)::value) {           // the slice ends inside stage ss + 1, or before it
-                const int lim = len - W3_KS * (ss + 1) - kfrag;
+                const int lim = len - T3_KS * (ss + 1) - kfrag;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) bw[i] = i < lim ? bw[i] : 0.f;
             }
@@ -1630,23 +1640,24 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
             W3A_SB
             W3A_MM(sml, 1, 0, 1)
             gs_split2(ra[as][2], ra[as][3], ah[1], am[1], al[1]);
-            store_a(oa_nn, u32x2{ah[0], ah[1]}, u32x2{am[0], am[1]}, u32x2{al[0], al[1]});
+            t3_store_pieces<0>(a_wr + (uint32_t)oa_nn, u32x2{ah[0], ah[1]}, u32x2{am[0], am[1]}, u32x2{al[0], al[1]});
             W3A_SB
             W3A_MM(sml, 0, 1, 0)
             if constexpr (decltype(masked)::value) {
                 dma_b(ss + 3, (q4 + 3) & 3);                   // into the slot stage ss - 1 was read from (during stage ss - 2)
                 gload_a(as, ss + 6);
             } else {
-                asm volatile("s_add_i32 m0, %3, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
-                             "s_add_i32 m0, %3, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %2"
-                             :: "v"(zb_lane), "s"(zb), "s"(zb + zb_pair), "s"(zb_lds), "n"(((q4 + 3) & 3) * B_BYTES),
-                                "n"(((q4 + 3) & 3) * B_BYTES + 1024) : "scc");
+                t3_dma_pair(zb_lane, zb, zb_pair, zb_lds, ((q4 + 3) & 3) * B_BYTES);
                 zb += zb_stage;
                 gload_a(as, ss + 6);
             }
             W3A_SB
             W3A_MM(sml, 1, 1, 0)
-            W3A_BARRIER(10, ra[an][0], ra[an][1], ra[an][2], ra[an][3]);
+            // What the NEXT stage consumes has landed: the raw dZ of stage ss + 2 (requested during stage ss - 1) and the A registers
+            // it cuts (stage ss + 3, requested during stage ss - 3).  A thread's requests retire IN ORDER and a stage issues its two
+            // DMAs and THEN its four A requests: behind dZ(ss + 2) lie the four A requests of that stage and this stage's six --
+            // vmcnt(10); A(ss + 3) is older than all of them.
+            T3_BARRIER(10, "+v"(ra[an][0]), "+v"(ra[an][1]), "+v"(ra[an][2]), "+v"(ra[an][3]));
             W3A_SB
 #undef W3A_MM
 #undef W3A_RA
@@ -1656,7 +1667,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
         }
     }
     };
-    const int whole = len / W3_KS;
+    const int whole = len / T3_KS;
     const int s_plain = (whole >= 7 && ldz < (1 << 29)) ? ((whole - 7) & ~3) + 4 : 0;   // (<= (whole - 1) & ~3: stages ss < s_plain read a full stage ss + 1)
     run(std::false_type{}, 0, s_plain);
     run(std::true_type{}, s_plain, stages4);
@@ -1665,36 +1676,7 @@ __global__ __launch_bounds__(256) void wgrad_tiled3_acut_kernel(const Wg3Args G,
                    "+v"(ra[1][3]), "+v"(ra[2][0]), "+v"(ra[2][1]), "+v"(ra[2][2]), "+v"(ra[2][3]), "+v"(ra[3][0]), "+v"(ra[3][1]),
                    "+v"(ra[3][2]), "+v"(ra[3][3]) :: "memory");
     __syncthreads();
-#undef W3A_BARRIER
-    // ---- the wave's 64 x 32 tile -> its slab, through a wave-private LDS staging tile: as in wgrad_tiled3_kernel
-    float* otile = reinterpret_cast<float*>(smem) + wave * (64 * 36);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e)
-            otile[(32 * i + (e & 3) + 8 * (e >> 2) + 4 * lh) * 36 + l31] = acc[i][e] + sml[i][e];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // (wave-private region: the wave's own writes before its reads)
-    float* __restrict__ S = q.slabs + (int64_t)z * q.d * q.ld_slab;
-    const bool vec = (q.ld_slab & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15u) == 0;
-    const int c4 = (lane & 7) * 4, r0 = lane >> 3;
-    const int colg = n0 + 32 * wn + c4;
-    const int N = q.out_dim;
-#pragma unroll
-    for (int itr = 0; itr < 8; ++itr) {
-        const int rr = 8 * itr + r0;
-        const int row = m0 + rr;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(otile + rr * 36 + c4);
-        if (row < q.d) {
-            float* dst = S + (int64_t)row * q.ld_slab + colg;
-            if (vec && colg + 3 < N) *reinterpret_cast<f32x4*>(dst) = v;
-            else {
-                if (colg < N) dst[0] = v.x;
-                if (colg + 1 < N) dst[1] = v.y;
-                if (colg + 2 < N) dst[2] = v.z;
-                if (colg + 3 < N) dst[3] = v.w;
-            }
-        }
-    }
+    t3_wgrad_store(q, it, smem, wave, lane, acc, sml);
 }
 
 static int g_wgrad_tiled3_form = 1;      // gs_set_wgrad_tiled3_form
@@ -1738,16 +1720,16 @@ static int wgrad_grouped_tiled3_impl(const gs_wgrad_desc* descs_host, int32_t n_
     if (sampler) F = *sampler;
     const int64_t blocks = items + gs_ceil_div(F.B, 4) + gs_ceil_div(waves, 4);
     GS_REQUIRE(blocks < (1ll << 31), "gs_dense_wgrad_grouped_tiled3: grid too large");
-    static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= W3_NS * (W3_KS * 64 * 4 + W3_KS * 128 * 4), "sampler rider LDS");
-    static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= W3A_LDS_BYTES, "sampler rider LDS");
+    static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= W3_NS * (T3_KS * 64 * 4 + T3_KS * 128 * 4), "sampler rider LDS");
+    static_assert(4 * GS_FANOUT_LDS_INTS(GS_FANOUT_LDS_SMALL) * 4 <= T3_LDS_BYTES, "sampler rider LDS");
     if (g_wgrad_tiled3_form == 1) {
-        const size_t lds = W3A_LDS_BYTES;
+        const size_t lds = T3_LDS_BYTES;
         GS_LDS_ATTR(lds, wgrad_tiled3_acut_kernel);
         hipLaunchKernelGGL(wgrad_tiled3_acut_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, G, F, J);
         GS_LAUNCH_CHECK("wgrad_tiled3_acut_kernel");
         return GS_OK;
     }
-    const size_t lds = W3_NS * (W3_KS * 64 * 4 + W3_KS * 128 * 4) + W3_MAXROWS * 4;
+    const size_t lds = W3_NS * (T3_KS * 64 * 4 + T3_KS * 128 * 4) + W3_MAXROWS * 4;
     GS_LDS_ATTR(lds, wgrad_tiled3_kernel);
     hipLaunchKernelGGL(wgrad_tiled3_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, G, F, J);
     GS_LAUNCH_CHECK("wgrad_tiled3_kernel");
