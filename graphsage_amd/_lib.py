@@ -171,6 +171,8 @@ _PROTOS = {
                      _P, _P, _P, _P, _P, c_uint64, _P, c_uint64, _P],
     "gs_csr_reduce_ws_bytes": [c_int64, c_int32, POINTER(c_int64)],
     "gs_csr_reduce_fwd": [_P, _P],
+    "gs_rank_ws_bytes": [c_int64, c_int64, POINTER(c_int64)],
+    "gs_rank_count": [_P, _P],
 }
 
 
@@ -281,6 +283,19 @@ class CsrReduceDesc(ctypes.Structure):
 
 
 assert ctypes.sizeof(CsrReduceDesc) == 200      # static_assert in csrc/gs_csr_reduce.hip (passed by pointer, as LstmSeg)
+
+
+class RankDesc(ctypes.Structure):
+    """struct gs_rank_desc (include/graphsage_amd.h)"""
+    _fields_ = [("Xq", c_void_p), ("Zc", c_void_p), ("dst", c_void_p), ("src", c_void_p), ("f_rowptr", c_void_p),
+                ("f_col", c_void_p), ("t", c_void_p), ("n_gt", c_void_p), ("n_eq", c_void_p), ("ws", c_void_p),
+                ("Q", c_int64), ("ldq", c_int64), ("n_rows", c_int64), ("n_cand", c_int64), ("ldz", c_int64),
+                ("f_nnz", c_int64), ("ws_bytes", c_int64),
+                ("d", c_int32), ("flags", c_int32)]
+
+
+RANK_KEEP_SRC = 1                           # GS_RANK_KEEP_SRC (gs_rank_desc.flags)
+assert ctypes.sizeof(RankDesc) == 144      # static_assert in csrc/gs_rank.hip (passed by pointer, as CsrReduceDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

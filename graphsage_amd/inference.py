@@ -20,6 +20,14 @@ single neighbor N (a mean or max of identical entries is that entry).
 The split rule.  One wave reduces one work item; a row longer than `split_len` (512) edges is cut into items of at most that
 many, reduced by separate waves into a workspace and combined in segment order by a second small launch: a hub of thousands
 of neighbors does not outlive the launch, no float atomics, one fixed summation order.
+
+Link ranking.  What the exact embeddings are for: where does the true partner of a held-out edge (u, v) stand among ALL nodes?
+
+    res = model.rank_full(graph, edges)                         # ranks, ranks_optimistic, n_gt, n_eq, scores, mrr, hits
+    res = rank_full(engine, Z, edges, n_cand=N, filt=RankFilter.from_full_graph(graph))
+
+One fused launch scores every (query, candidate) pair on the matrix cores and counts the candidates above / level with the
+true partner in its epilogue (gs_rank_count, csrc/gs_rank.hip): no score matrix exists.  rank = 1 + n_gt + n_eq: a tie loses.
 """
 import numpy as np
 
@@ -94,6 +102,13 @@ class FullGraph(object):
         self.nnz = int(rowptr_host[-1])
         self.items, self.item_ptr, self.splits = plan_work_items(rowptr_host, self.split_len)
         self._dev = {}
+        self._rank_filter = None
+
+    def rank_filter(self):
+        """Every edge of this graph as a RankFilter (built and uploaded once)."""
+        if self._rank_filter is None:
+            self._rank_filter = RankFilter.from_full_graph(self)
+        return self._rank_filter
 
     def _check(self, rowptr_host):
         """rowptr non-decreasing from 0, rowptr[-1] == len(col), 0 <= col < n_rows: an id outside the table must never reach
@@ -257,3 +272,121 @@ def select_rows(model, table, nodes):
     ops.gather_rows(table, ids_dev, out=out, stream=e.stream)
     e.sync()
     return out, int(ids.size)
+
+
+# ---------------------------------------------------------------------------------------------------- link ranking
+class RankFilter(object):
+    """Known edges to leave out of a ranking: a CSR over the candidate table's rows (row u = the ids that are no candidates for
+    a query from u), rows sorted and de-duplicated, ids checked ONCE on the host (an id outside the table must never reach the
+    kernel), uploaded once per device."""
+
+    def __init__(self, rowptr, col, n_nodes):
+        self.n_nodes = int(n_nodes)
+        self.rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+        self.col = np.ascontiguousarray(col, dtype=np.int32)
+        self._dev = {}
+
+    @classmethod
+    def from_csr(cls, rowptr, col, n_nodes):
+        """rowptr [n_nodes + 1], col with entries in [0, n_nodes); rows in any order, duplicates allowed."""
+        n = int(n_nodes)
+        rp = np.asarray(rowptr.cpu().numpy() if _is_torch(rowptr) else rowptr).astype(np.int64)
+        col = np.asarray(col.cpu().numpy() if _is_torch(col) else col).reshape(-1)
+        if n < 0 or rp.ndim != 1 or rp.shape[0] != n + 1:
+            raise GraphsageAmdError("RankFilter: rowptr must have n_nodes + 1 = %d entries" % (n + 1))
+        if rp[0] != 0 or (np.diff(rp) < 0).any() or int(rp[-1]) != col.shape[0]:
+            raise GraphsageAmdError("RankFilter: rowptr must run from 0 to len(col) without decreasing")
+        if col.size and (col.min() < 0 or col.max() >= n):
+            raise GraphsageAmdError("RankFilter: ids must lie in [0, %d) (found %d .. %d)" % (n, col.min(), col.max()))
+        # rows that already are strictly ascending (a CSR built by sorting edges usually is) are taken as they are: one pass
+        # over neighboring entries, no sort and no 64-bit key per edge
+        rising = col[1:] > col[:-1]
+        starts = rp[1:-1]
+        rising[starts[(starts > 0) & (starts < col.shape[0])] - 1] = True          # the step from one row into the next
+        if rising.all():
+            return cls(rp, col, n)
+        key = np.unique(np.repeat(np.arange(n, dtype=np.int64), np.diff(rp)) * max(n, 1) + col)      # sorts and de-duplicates
+        new_rp = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(key // max(n, 1), minlength=n), out=new_rp[1:])
+        return cls(new_rp, key % max(n, 1), n)
+
+    @classmethod
+    def from_full_graph(cls, graph):
+        """Every edge of a FullGraph (its pad row and pad entries included: the pad node is no candidate anyway)."""
+        rp = graph.rowptr.cpu().numpy() if graph._on_device else graph.rowptr
+        col = graph.col.cpu().numpy() if graph._on_device else graph.col
+        return cls.from_csr(rp, col, graph.n_rows)
+
+    def lists(self):
+        return [self.col[self.rowptr[r]:self.rowptr[r + 1]] for r in range(self.n_nodes)]
+
+    def on(self, device, n_rows):
+        """(rowptr int64 [n_rows + 1], col int32) on `device` for a table of n_rows >= n_nodes rows (the rows beyond the filter's
+        are empty)."""
+        if n_rows < self.n_nodes:
+            raise GraphsageAmdError("RankFilter: the filter covers %d rows, the table has %d" % (self.n_nodes, n_rows))
+        key = (str(device), int(n_rows))
+        if key not in self._dev:
+            import torch
+            rp = np.concatenate([self.rowptr, np.full(n_rows - self.n_nodes, self.rowptr[-1], np.int64)])
+            col = torch.from_numpy(self.col).to(device) if self.col.size else torch.zeros(1, dtype=torch.int32, device=device)
+            self._dev[key] = (torch.from_numpy(rp).to(device), col)
+            torch.cuda.synchronize()
+        return self._dev[key]
+
+
+def rank_metrics(n_gt, n_eq, hits=(1, 10, 50, 100)):
+    """ranks = 1 + n_gt + n_eq (the reference's convention, models.py:392-404: the true score stands last in aff_all and top_k is
+    stable, so a tie loses), ranks_optimistic = 1 + n_gt, mrr = mean(1 / ranks), hits[k] = share of ranks <= k."""
+    n_gt = np.asarray(n_gt, dtype=np.int64)
+    n_eq = np.asarray(n_eq, dtype=np.int64)
+    ranks = 1 + n_gt + n_eq
+    return {"ranks": ranks, "ranks_optimistic": 1 + n_gt, "n_gt": n_gt, "n_eq": n_eq,
+            "mrr": float(np.mean(1.0 / ranks)) if ranks.size else 0.0,
+            "hits": {int(k): (float(np.mean(ranks <= k)) if ranks.size else 0.0) for k in hits}}
+
+
+def rank_full(engine, Z, edges, *, n_cand=None, filt=None, exclude_self=True, weights=None, hits=(1, 10, 50, 100)):
+    """Rank the true partner of every edge (src, dst) among the rows 0 .. n_cand - 1 of the device table Z ([n_rows, d] Mat): the
+    score of a candidate w is <Z[src], Z[w]>, or <Z[src] . A, Z[w]> with the bilinear weights A ([d, d] Mat, prediction.py:68-92,
+    applied on the query side as in neg_cost).  dst itself, src (exclude_self) and the filter row of src (filt: RankFilter;
+    independent of exclude_self: with exclude_self=False the query node only names its filter row and stays a candidate)
+    are no candidates.  One fused score-and-count launch per 65,536 queries (gs_rank_count); no score matrix exists."""
+    import torch
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    Q = edges.shape[0]
+    n_cand = Z.rows if n_cand is None else int(n_cand)
+    if not 0 <= n_cand <= Z.rows:
+        raise GraphsageAmdError("rank_full: n_cand = %d, the table has %d rows" % (n_cand, Z.rows))
+    if Q and (edges.min() < 0 or edges.max() >= Z.rows):
+        raise GraphsageAmdError("rank_full: edge ends must lie in [0, %d)" % Z.rows)
+    if Q == 0:
+        res = rank_metrics(np.zeros(0, np.int64), np.zeros(0, np.int64), hits)
+        res["scores"] = np.zeros(0, np.float32)
+        return res
+    e = engine
+    src = torch.from_numpy(np.ascontiguousarray(edges[:, 0], dtype=np.int32)).to(e.device)
+    dst = torch.from_numpy(np.ascontiguousarray(edges[:, 1], dtype=np.int32)).to(e.device)
+    f_rowptr = f_col = None
+    if filt is not None:
+        f_rowptr, f_col = filt.on(e.device, Z.rows)
+    Xq = _table(e, Q, Z.d)
+    out = (torch.zeros(Q, dtype=torch.float32, device=e.device), torch.zeros(Q, dtype=torch.int32, device=e.device),
+           torch.zeros(Q, dtype=torch.int32, device=e.device))
+    ws = torch.zeros(max(2, max(ops.rank_ws_bytes(n, n_cand) for n in {min(Q, ops.RANK_CHUNK), Q % ops.RANK_CHUNK}) // 4),
+                     dtype=torch.int32, device=e.device)
+    torch.cuda.synchronize()              # uploads and zero-fills ran on torch's stream; order them before the engine's
+    ops.gather_rows(Z, src, out=Xq, stream=e.stream)
+    if weights is not None:
+        if weights.rows != Z.d or weights.d != Z.d:
+            raise GraphsageAmdError("rank_full: bilinear weights must be [%d, %d]" % (Z.d, Z.d))
+        U = _table(e, Q, Z.d)
+        ops.gemm(False, False, Q, Z.d, Z.d, Xq, weights, U, stream=e.stream)
+        Xq = U
+    ops.rank_count(Xq, Z, dst, n_cand=n_cand, src=src if (exclude_self or filt is not None) else None,
+                   keep_src=not exclude_self, f_rowptr=f_rowptr,
+                   f_col=f_col, t=out[0], n_gt=out[1], n_eq=out[2], ws=ws, stream=e.stream)
+    e.sync()
+    res = rank_metrics(out[1].cpu().numpy(), out[2].cpu().numpy(), hits)
+    res["scores"] = out[0].cpu().numpy()
+    return res

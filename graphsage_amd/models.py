@@ -1000,6 +1000,19 @@ class SampleAndAggregate(object):
         e.sync()
         return y.numpy()[:n]
 
+    def rank_full(self, graph, edges, filtered=True, hits=(1, 10, 50, 100)):
+        """Rank the true partner of every edge (src, dst) among ALL N nodes with the exact embeddings of `graph` (the table of
+        embed_full, kept on the device): inference.rank_full with n_cand = N (the pad row is never a candidate), the query
+        node left out, the edges of `graph` filtered (filtered=True) and the head's bilinear weights if it has them."""
+        from . import inference as inf
+        e = self.engine
+        H = inf.layers_full(self, graph)
+        Z = inf._table(e, H.rows, H.d)
+        ops.l2norm_fwd(H, H.rows, Z, None, stream=e.stream)
+        filt = graph.rank_filter() if filtered else None
+        W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
+        return inf.rank_full(e, Z, edges, n_cand=graph.n_nodes, filt=filt, weights=W, hits=hits)
+
     # ------------------------------------------------------------------------------ step machinery (shared)
     def _samplers(self):
         seen = []

@@ -259,6 +259,54 @@ def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, ro
     return out
 
 
+# ------------------------------------------------------------------------------------------ RANK
+RANK_CHUNK = 65536       # query rows per gs_rank_count call: the slab workspace does not grow with Q
+
+
+def rank_ws_bytes(Q, n_cand):
+    """Bytes of the int32 slab workspace gs_rank_count needs for Q queries against n_cand candidates."""
+    out = ctypes.c_int64(0)
+    call("gs_rank_ws_bytes", Q, n_cand, ctypes.byref(out))
+    return out.value
+
+
+def rank_count(Xq, Zc, dst, n_cand=None, src=None, f_rowptr=None, f_col=None, t=None, n_gt=None, n_eq=None, ws=None,
+               keep_src=False, stream=None):
+    """gs_rank_count: t[q] = <Xq[q], Zc[dst[q]]> and the numbers of candidates w < n_cand (dst[q], src[q] and the filter row
+    of src[q] left out) that score above / exactly t[q].  Xq, Zc: Mats of the same width; dst, src: int32 device vectors with
+    entries in [0, Zc.rows) (checked by the caller); f_rowptr int64 [Zc.rows + 1], f_col int32 (a filter needs src).
+    keep_src: src[q] stays a candidate and only names the filter row (GS_RANK_KEEP_SRC).  Returns (t, n_gt, n_eq)."""
+    Q = dst.numel()
+    n_cand = Zc.rows if n_cand is None else int(n_cand)
+    if Xq.d != Zc.d or Xq.rows < Q:
+        raise _lib.GraphsageAmdError("rank_count: Xq is [%d, %d], Zc [%d, %d], %d queries" % (Xq.rows, Xq.d, Zc.rows, Zc.d, Q))
+    if dst.dtype != torch.int32 or (src is not None and (src.dtype != torch.int32 or src.numel() != Q)):
+        raise _lib.GraphsageAmdError("rank_count: dst and src must be int32 vectors of the same length")
+    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
+            f_rowptr.dtype != torch.int64 or f_col.dtype != torch.int32 or f_rowptr.numel() != Zc.rows + 1)):
+        raise _lib.GraphsageAmdError("rank_count: the filter is an int64 rowptr [n_rows + 1] with an int32 col")
+    dev = dst.device
+    t = torch.empty(Q, dtype=torch.float32, device=dev) if t is None else t
+    n_gt = torch.empty(Q, dtype=torch.int32, device=dev) if n_gt is None else n_gt
+    n_eq = torch.empty(Q, dtype=torch.int32, device=dev) if n_eq is None else n_eq
+    need = max(rank_ws_bytes(n, n_cand) for n in {min(Q, RANK_CHUNK), Q % RANK_CHUNK})      # the two chunk sizes that occur
+    if ws is None:
+        ws = torch.empty(max(need // 4, 2), dtype=torch.int32, device=dev)
+    q = _lib.RankDesc()
+    q.Zc, q.f_rowptr, q.f_col, q.ws = Zc.ptr, ptr(f_rowptr), ptr(f_col), ptr(ws)
+    q.n_rows, q.n_cand, q.ldz, q.ldq = Zc.rows, n_cand, Zc.ld, Xq.ld
+    q.f_nnz, q.ws_bytes, q.d = (f_col.numel() if f_col is not None else 0), 4 * ws.numel(), Xq.d
+    q.flags = _lib.RANK_KEEP_SRC if keep_src else 0
+    for q0 in range(0, max(Q, 1), RANK_CHUNK):
+        n = min(RANK_CHUNK, Q - q0)
+        q.Q = n
+        q.Xq = Xq.ptr + 4 * q0 * Xq.ld
+        q.dst, q.src = ptr(dst[q0:q0 + n]), (ptr(src[q0:q0 + n]) if src is not None else None)
+        q.t, q.n_gt, q.n_eq = ptr(t[q0:q0 + n]), ptr(n_gt[q0:q0 + n]), ptr(n_eq[q0:q0 + n])
+        call("gs_rank_count", ctypes.addressof(q), _s(stream))
+    return t, n_gt, n_eq
+
+
 # ------------------------------------------------------------------------------------------ K3
 def sage_dense_fwd(self_m, self_idx, agg, agg_idx, n, W_self, W_neigh, out_dim, concat, act, bias, out,
                    stream=None):

@@ -72,11 +72,13 @@ FLAGS = None
 
 
 def refuse_full_inference(flags):
-    """--full_inference has no meaning for the models without a full-neighborhood form: say so before any work is done."""
-    if getattr(flags, "full_inference", False) and flags.model in ('n2v', 'graphsage_seq'):
-        raise SystemExit("--full_inference is not available with --model %s: %s" % (
-            flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v' else
-            "an LSTM over a random permutation of a neighbor sample has no full-neighborhood form"))
+    """--full_inference (and --rank_full, which ranks the embed_full embeddings) has no meaning for the models without a
+    full-neighborhood form: say so before any work is done."""
+    for flag in ("full_inference", "rank_full"):
+        if getattr(flags, flag, False) and flags.model in ('n2v', 'graphsage_seq'):
+            raise SystemExit("--%s is not available with --model %s: %s" % (
+                flag, flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v'
+                else "an LSTM over a random permutation of a neighbor sample has no full-neighborhood form"))
 
 
 def refuse_dropout(flags):

@@ -64,6 +64,9 @@ def build_flags(argv=None):
     p.add_argument('--full_inference', type=b, nargs='?', const=True, default=False,
                    help='after val.npy: exact layer-wise embeddings of ALL nodes from their whole neighbor lists on the test '
                         'graph (embed_full) -> val_full.npy / val_full.txt; not for n2v / graphsage_seq')
+    p.add_argument('--rank_full', type=b, nargs='?', const=True, default=False,
+                   help='after val.npy: rank every held-out edge (both directions) against ALL nodes with the exact embeddings '
+                        'on the test graph, known edges filtered (rank_full) -> rank_full.txt; not for n2v / graphsage_seq')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     return p.parse_args(argv)
 
@@ -148,6 +151,28 @@ def save_full_embeddings(model, minibatch, out_dir):
     ids = getattr(G, "node_ids", None)
     with open(out_dir + "val_full.txt", "w") as fp:
         fp.write("\n".join(str(ids[i] if ids is not None else i) for i in range(G.n_nodes)))
+
+
+def rank_full_line(res):
+    """The line --rank_full prints and writes to rank_full.txt."""
+    return ("Full-graph link ranking: mrr= {:.5f} ".format(res["mrr"])
+            + " ".join("hits@%d= %.5f" % (k, res["hits"][k]) for k in sorted(res["hits"]))
+            + " edges= %d" % len(res["ranks"]))
+
+
+def save_full_ranking(model, minibatch, out_dir):
+    """rank_full.txt: every held-out edge, in both directions, ranked against all N nodes with the exact embeddings of the
+    test graph; the query node and every edge of the test graph are filtered out of the candidates."""
+    from .supervised_train import full_graph
+    edges = np.asarray(minibatch.val_edges, dtype=np.int64).reshape(-1, 2)
+    res = model.rank_full(full_graph(minibatch, minibatch.G.n_nodes), np.concatenate([edges, edges[:, ::-1]], axis=0))
+    line = rank_full_line(res)
+    print(line)
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    with open(out_dir + "rank_full.txt", "w") as fp:
+        fp.write(line + "\n")
+    return res
 
 
 def construct_placeholders():
@@ -256,6 +281,8 @@ def train(G, context_pairs):
         save_val_embeddings(model, minibatch, FLAGS.validate_batch_size, log_dir())
         if FLAGS.full_inference:
             save_full_embeddings(model, minibatch, log_dir())
+        if FLAGS.rank_full:
+            save_full_ranking(model, minibatch, log_dir())
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
     return shadow_mrr

@@ -1037,6 +1037,44 @@ int gs_csr_reduce_ws_bytes(int64_t n_slots, int32_t d, int64_t* bytes_out_host);
 int gs_csr_reduce_fwd(const gs_csr_reduce_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * RANK link ranking against every node: a contraction with a compare-and-count epilogue; no score is written to memory.
+ *        t[q]    = <Xq[q], Zc[dst[q]]>                                   (fp32 on the matrix cores, fp32 operands)
+ *        n_gt[q] = #{w in C_q : <Xq[q], Zc[w]> >  t[q]}
+ *        n_eq[q] = #{w in C_q : <Xq[q], Zc[w]> == t[q]}
+ *      C_q = {0 <= w < n_cand} without dst[q], without src[q] (if src is given and flags lacks GS_RANK_KEEP_SRC) and without
+ *      the filter row of src[q] (if a filter is given; it needs src, which only indexes it under GS_RANK_KEEP_SRC).  dst[q] may lie at or beyond n_cand; dst and src entries must lie in [0, n_rows) (the
+ *      caller checks them once).  The filter is a CSR over the table's rows: f_rowptr int64 [n_rows + 1], f_col int32
+ *      [f_nnz], strictly ascending within each row, entries in [0, n_rows).
+ *      t comes out of the sweep's own tile code run on the dst-gathered rows, so a candidate row that is bit-identical to
+ *      Zc[dst[q]] scores bit-equal to t[q] and is counted in n_eq.  d is a multiple of 4 in [4, 1024]; ld >= d.
+ *      The grid runs over (query tile of 128) x (candidate slice); per-slice counts go to the int32 workspace
+ *      [slices][Q][2] and a second small launch sums them: integers only, bitwise reproducible, no atomics.
+ *      gs_rank_ws_bytes(Q, n_cand) = slices * Q * 2 * sizeof(int32_t), where, with tiles = ceil(n_cand / 128) and
+ *      q_tiles = max(1, ceil(Q / 128)):  tiles_per_slice = min(16384, max(4, ceil(tiles / max(1, ceil(2048 / q_tiles))))),
+ *      slices = max(1, ceil(tiles / tiles_per_slice)).  Callers with many queries pass them in chunks (the binding: 65,536)
+ *      so that the workspace does not grow with Q.
+ *      gs_rank_desc is 144 bytes on every target (checked at compile time and by the binding; passed by pointer, not part
+ *      of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_RANK_KEEP_SRC 1     /* gs_rank_desc.flags: src[q] stays a candidate (src is then only the filter's row index) */
+typedef struct gs_rank_desc {
+    const float* Xq;           /* device [Q][ldq] query rows */
+    const float* Zc;           /* device [n_rows][ldz] candidate table */
+    const int32_t* dst;        /* device [Q]: table row of the true partner */
+    const int32_t* src;        /* device [Q]: table row of the query node; nullable */
+    const int64_t* f_rowptr;   /* device [n_rows + 1]; nullable (with f_col) */
+    const int32_t* f_col;      /* device [f_nnz] */
+    float* t;                  /* device [Q] */
+    int32_t* n_gt;             /* device [Q] */
+    int32_t* n_eq;             /* device [Q] */
+    void* ws;                  /* device, 8-byte aligned, ws_bytes >= gs_rank_ws_bytes(Q, n_cand) */
+    int64_t Q, ldq, n_rows, n_cand, ldz, f_nnz, ws_bytes;
+    int32_t d, flags;          /* flags: 0 or GS_RANK_KEEP_SRC */
+} gs_rank_desc;
+int gs_rank_ws_bytes(int64_t Q, int64_t n_cand, int64_t* bytes_out_host);
+int gs_rank_count(const gs_rank_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
