@@ -138,7 +138,10 @@ static inline int build_cojobs_s(const gs_gather_desc* jobs_host, int32_t n_jobs
         GS_CHECK_MAT(q.X, q.ldx, "co-gather job X");
         GS_CHECK_MAT(q.out, q.ldo, "co-gather job out");
         GS_REQUIRE(q.n > 0 && q.s > 0 && q.d > 0 && q.ldx >= gs_rup4(q.d) && q.ldo >= gs_rup4(q.d), "co-gather: bad job %d", i);
-        if (q.self_src) GS_CHECK_MAT(q.self_src, q.ld_self, "co-gather job self");
+        if (q.self_src) {
+            GS_CHECK_MAT(q.self_src, q.ld_self, "co-gather job self");
+            GS_REQUIRE(q.ld_self >= gs_rup4(q.d), "co-gather: job %d: ld_self must be >= round_up(d,4)", i);
+        }
         const int chunks = ((q.d + 3) / 4 + 63) / 64;
         J.job[i] = GatherArgs{q.X, q.ldx, q.idx, q.n, q.s, q.d, q.self_src, q.ld_self, q.self_idx, q.out, q.ldo,
                               q.self_src ? 1.0f / (float)(q.s + 1) : 1.0f / (float)q.s, chunks,

@@ -856,6 +856,20 @@ def adam_step(p, grad, m, v, count, lr, step_dev, beta1=0.9, beta2=0.999, eps=1e
          ptr(step_dev), int(step_offset), _s(stream))
 
 
+def flat_reduce_adam_sample(var_descs, params, grads, m, v, total, weight_decay, fuse_adam, lr, step_dev, beta1=0.9, beta2=0.999,
+                            eps=1e-8, clip=5.0, grad_scale=1.0, step_offset=1, loss=None, sampler=None, jobs=(), stream=None):
+    """gs_flat_reduce_adam_sample: the slab reduce (+ weight decay, + clip and Adam when fuse_adam) over the ctypes array
+    `var_descs` of VarDesc, with its riders -- loss = (loss_rows, n, scale, loss_out, accumulate) or None, sampler = a fanout_desc()
+    or None, jobs = gather_job() descriptors of the next mini-batch."""
+    lr_, ln, lscale, lout, lacc = loss if loss is not None else (None, 0, 0.0, None, False)
+    jobs = list(jobs or ())
+    jarr = (_lib.GatherDesc * max(len(jobs), 1))(*jobs)
+    call("gs_flat_reduce_adam_sample", ctypes.addressof(var_descs), len(var_descs), ptr(params), ptr(grads), ptr(m), ptr(v), total,
+         float(weight_decay), 1 if fuse_adam else 0, lr, beta1, beta2, eps, clip, grad_scale, ptr(step_dev), int(step_offset),
+         ptr(lr_), ln, float(lscale), ptr(lout), 1 if lacc else 0, ctypes.addressof(sampler) if sampler is not None else None,
+         ctypes.addressof(jarr), len(jobs), _s(stream))
+
+
 def sum_scaled(x, count, scale, out, accumulate=False, stream=None):
     call("gs_sum_scaled", ptr(x), count, scale, ptr(out), 1 if accumulate else 0, _s(stream))
 

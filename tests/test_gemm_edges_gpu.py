@@ -264,7 +264,15 @@ class GatherJob(object):
         self.tag = "gather job n=%d s=%d d=%d gcn=%d" % (n, s, d, gcn)
 
     def check(self):
-        _note("gather_job", go.assert_within(self.out.read(self.tag), self.want, self.bound, self.tag))
+        got = self.out.read(self.tag)
+        _note("gather_job", go.assert_within(got, self.want, self.bound, self.tag))
+        # ... and the rider has the BITS of the stand-alone launch of the same descriptor (the summation order is fixed)
+        j = self.desc
+        alone = Out(self.out.t.device, j.n, j.d)
+        ops.call("gs_gather_mean_fwd", j.X, j.ldx, j.idx, j.n, j.s, j.d, j.self_src, j.ld_self, j.self_idx, alone.ptr, alone.ld, _st())
+        want = alone.read(self.tag + " (stand-alone)")
+        assert np.array_equal(np.ascontiguousarray(got).view(np.uint32), np.ascontiguousarray(want).view(np.uint32)), \
+            "%s: the rider's bits differ from gs_gather_mean_fwd's" % self.tag
 
 
 def _gather_jobs(dev, rng, n_jobs):
