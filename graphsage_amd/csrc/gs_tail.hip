@@ -86,7 +86,6 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
     constexpr int DPW = DSLABS / TAIL_WAVES / NH;                 // ... per wave of this workgroup (1 or 2)
 
     constexpr int M7 = O / 16;                                    // macro steps (16 k each) of the input-gradient contraction
-    constexpr int ldi = 2 * D + 8;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int C = a.C;
     const int Cp4 = (C + 3) & ~3, Cp32 = (C + 31) & ~31;
@@ -108,40 +107,12 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
     const int j = lane & 15, q = lane >> 4;
     const int r0 = grp * TAIL_ROWS;                   // (n + n*s) * ld < 2^31 is checked on the host: 32-bit offsets
     const int n = (int)a.n;
-    const int s = a.s;
-    const int ldh0 = (int)a.ldh;
-    const float inv_s = 1.0f / (float)s;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-    // ================= S0: issue this thread's h0 rows and the wave's z-contraction weight slab
-    f32x4 hself[PASSES], hnb[PASSES][TAIL_NB];
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p) {
-        const int it = tid + p * TAIL_THREADS;
-        const int r = it / D4H, c = (half * D4H + it % D4H) * 4;
-        const int i = min(r0 + r, n - 1);
-        hself[p] = *reinterpret_cast<const f32x4*>(a.h0 + i * ldh0 + c);
-        const float* nb = a.h0 + (n + i * s) * ldh0 + c;
-#pragma unroll
-        for (int u = 0; u < TAIL_NB; ++u) hnb[p][u] = *reinterpret_cast<const f32x4*>(nb + min(u, s - 1) * ldh0);
-    }
-    // ---------------- phase 0: the relu mask bits of this thread's h0 rows (for phase 8); the rows themselves are only
-    // needed by the z helpers
-    uint32_t mself[PASSES], mnb[PASSES][2];            // 4 bits per row: h > 0 of the float4's elements
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p) {
-        mnb[p][0] = mnb[p][1] = 0u;
-#pragma unroll
-        for (int u = 0; u < TAIL_NB; ++u) {
-            const f32x4 v = hnb[p][u];
-            const uint32_t bits = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-            mnb[p][u >> 3] |= bits << (4 * (u & 7));
-        }
-        const f32x4 hs = hself[p];
-        mself[p] = (hs.x > 0.f ? 1u : 0u) | (hs.y > 0.f ? 2u : 0u) | (hs.z > 0.f ? 4u : 0u) | (hs.w > 0.f ? 8u : 0u);
-        // pin the flags here: otherwise the compiler keeps the 12 float4 rows alive until phase 8 and re-derives them
-        asm volatile("" : "+v"(mself[p]), "+v"(mnb[p][0]), "+v"(mnb[p][1]));
-    }
+    // ================= S0 / phase 0: issue this thread's h0 rows and keep their relu mask bits (for phase 8); the rows
+    // themselves are only needed by the z helpers
+    uint32_t mself[PASSES], mnb[PASSES][2];
+    tail_relu_mask_bits<D4H, PASSES>(a, half * D4H, [&](const int r) { return min(r0 + r, n - 1); }, mself, mnb);
     TAIL_STAMP(1);
 
     // ================= S1: issue the operands of every later phase (they land while the helpers compute z)
@@ -172,17 +143,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
         if (NH == 1) return (wave + sl * TAIL_WAVES) * 32;
         return (wave >> 2) * D + half * (D / 2) + (wave & 3) * 32;     // waves 0-3: d_self, 4-7: d_means, this half's 128 columns
     };
-    auto load_b7 = [&](const int sl) {
-        const int col0 = slab_col0(sl);
-        const int term = col0 >= D ? 1 : 0;
-        const int ldw = (int)(term ? a.ldwn : a.ldws);
-        const float* B0 = (term ? a.Wn : a.Ws) + (col0 - term * D + j) * ldw + 4 * q;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) {
-            b7[sl][m][0] = *reinterpret_cast<const f32x4*>(B0 + 16 * m);
-            b7[sl][m][1] = *reinterpret_cast<const f32x4*>(B0 + 16 * ldw + 16 * m);
-        }
-    };
+    auto load_b7 = [&](const int sl) { tail_din_slab_load<D, O>(a, slab_col0(sl), b7[sl]); };
     // phase 5 (d_y, NT form): rows n0 .. n0+31 of W_head, K = Cp32 <= 64 CW -> up to 4 CW macro steps x 2 tiles
     f32x4 bh5[4 * CW][2];
     {
@@ -225,24 +186,16 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         const int row = wave * 2 + rr;
-        float v[Z / 64];
-        float ss = 0.f;
-#pragma unroll
-        for (int m = 0; m < Z / 64; ++m) {
-            v[m] = Zs[row * ldzs + lane + 64 * m];
-            ss += v[m] * v[m];
-        }
-        ss = tail_wave_sum(ss);
-        const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));      // v_rsq_f32 (1 ulp)
-#pragma unroll
-        for (int m = 0; m < Z / 64; ++m) {
-            const float y = v[m] * inv;
-            Zs[row * ldzs + lane + 64 * m] = y;
-            if (r0 + row < n && half == 0) {
-                a.y[(r0 + row) * (int)a.ldy + lane + 64 * m] = y;
-                if (!a.z_ready) a.z[(r0 + row) * (int)a.ldz + lane + 64 * m] = v[m];    // (the granules are kernel-internal)
+        const bool mine = r0 + row < n && half == 0, keep_z = !a.z_ready;
+        float* const yp = a.y;
+        float* const zp = a.z;
+        const int yi = (r0 + row) * (int)a.ldy + lane, zi = (r0 + row) * (int)a.ldz + lane;
+        const float inv = tail_l2norm_row<Z / 64>(Zs, row * ldzs, [=](const int m, const float zv, const float y) {
+            if (mine) {
+                yp[yi + 64 * m] = y;
+                if (keep_z) zp[zi + 64 * m] = zv;                    // (the granules are kernel-internal)
             }
-        }
+        });
         if (lane == 0) invs[row] = inv;
     }
     lds_barrier();
@@ -334,11 +287,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
     }
     if (!a.train) {
         if (!a.z_ready) tail_epoch_done<NH>(a, G, grp, z_tag);
-        if (grp == 0 && half == 0 && tid == 0) {
-            if (a.c0) *a.c0 += a.d0;
-            if (a.c1) *a.c1 += a.d1;
-            if (a.c2) *a.c2 += a.d2;
-        }
+        if (grp == 0 && half == 0 && tid == 0) tail_bump_counters(a.c0, a.d0, a.c1, a.d1, a.c2, a.d2);
         return;
     }
     if (DPW > 1 && CW > 1) load_b7(DPW - 1);
@@ -375,22 +324,17 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
 #pragma unroll
     for (int rr = 0; rr < 2; ++rr) {
         const int row = wave * 2 + rr;
-        float dy[Z / 64], yv[Z / 64];
-        float dot = 0.f;
+        float dy[Z / 64], yv[Z / 64], g[Z / 64];
 #pragma unroll
         for (int m = 0; m < Z / 64; ++m) {
             dy[m] = DYs[row * ldzs + lane + 64 * m];
             yv[m] = Zs[row * ldzs + lane + 64 * m];
-            dot += dy[m] * yv[m];
         }
-        dot = tail_wave_sum(dot);
-        const float inv = invs[row];
-        const bool clamped = inv >= 1.0e6f;   // sum(z^2) < 1e-12: y = z * 1e6, no normalisation term
+        tail_l2norm_bwd_row(dy, yv, invs[row], g);
 #pragma unroll
         for (int m = 0; m < Z / 64; ++m) {
-            const float g = clamped ? dy[m] * inv : inv * (dy[m] - yv[m] * dot);
-            DZs[row * ldzs + lane + 64 * m] = g;
-            if (r0 + row < n && half == 0) a.dz[(r0 + row) * (int)a.lddz + lane + 64 * m] = g;
+            DZs[row * ldzs + lane + 64 * m] = g[m];
+            if (r0 + row < n && half == 0) a.dz[(r0 + row) * (int)a.lddz + lane + 64 * m] = g[m];
         }
     }
     lds_barrier();
@@ -399,75 +343,16 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
     // ---------------- phase 7: [d_self | d_means] = [d_z[:, :O] . W_self^T | d_z[:, O:] . W_neigh^T]  -> DIN
     float* DIN = Hs;                                   // [16][2D + 8]   (Hs | Ms are dead since phase 1)
 #pragma unroll
-    for (int sl = 0; sl < DPW; ++sl) {
-        const int col0 = slab_col0(sl);
-        const int term = col0 >= D ? 1 : 0;
-        const float* A = DZs + term * O + j * ldzs + 4 * q;
-        f32x4 acc0 = zero4, acc1 = zero4;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(A + 16 * m);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc0 = mfma16(a4[e], b7[sl][m][0][e], acc0);
-                acc1 = mfma16(a4[e], b7[sl][m][1][e], acc1);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            DIN[(4 * q + i) * ldi + col0 + j] = acc0[i];
-            DIN[(4 * q + i) * ldi + col0 + 16 + j] = acc1[i];
-        }
-    }
+    for (int sl = 0; sl < DPW; ++sl) tail_din_slab_contract<D, O>(DZs, DIN, slab_col0(sl), b7[sl]);
     lds_barrier();
     TAIL_STAMP(9);
 
     // ---------------- phase 8: d_h0 = relu'(h0) * (d_self on the self row, d_means / s on each of the s neighbor rows);
     // the relu masks are the bit flags kept from phase 0 (h0 is read once).
-    {
-        const int lddh0 = (int)a.lddh;
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int it = tid + p * TAIL_THREADS;
-            const int r = it / D4H, c = (half * D4H + it % D4H) * 4;
-            const int i = r0 + r;
-            if (i < n) {
-                f32x4 g_self = *reinterpret_cast<const f32x4*>(DIN + r * ldi + c);
-                f32x4 g_mean = *reinterpret_cast<const f32x4*>(DIN + r * ldi + D + c);
-                if (a.gcn) {                                       // one operand, the mean over {neighbors} U {self}: both column
-                    g_self = (g_self + g_mean) * (1.0f / (float)(s + 1));   // halves' input gradients add up, every row gets 1/(s+1)
-                    g_mean = g_self;
-                } else {
-                    g_mean *= inv_s;
-                }
-                f32x4 o;
-                o.x = (mself[p] & 1u) ? g_self.x : 0.f;
-                o.y = (mself[p] & 2u) ? g_self.y : 0.f;
-                o.z = (mself[p] & 4u) ? g_self.z : 0.f;
-                o.w = (mself[p] & 8u) ? g_self.w : 0.f;
-                *reinterpret_cast<f32x4*>(a.d_h0 + i * lddh0 + c) = o;
-                float* dst = a.d_h0 + (n + i * s) * lddh0 + c;
-#pragma unroll
-                for (int u = 0; u < TAIL_NB; ++u) {
-                    if (u < s) {
-                        const uint32_t bits = mnb[p][u >> 3] >> (4 * (u & 7));
-                        o.x = (bits & 1u) ? g_mean.x : 0.f;
-                        o.y = (bits & 2u) ? g_mean.y : 0.f;
-                        o.z = (bits & 4u) ? g_mean.z : 0.f;
-                        o.w = (bits & 8u) ? g_mean.w : 0.f;
-                        *reinterpret_cast<f32x4*>(dst + u * lddh0) = o;
-                    }
-                }
-            }
-        }
-    }
+    tail_store_dh0<D, D4H, PASSES>(a, DIN, half * D4H, [&](const int r, bool& valid) { valid = r0 + r < n; return r0 + r; }, a.gcn, mself, mnb);
     TAIL_STAMP(10);
     if (!a.z_ready) tail_epoch_done<NH>(a, G, grp, z_tag);
-    if (grp == 0 && half == 0 && tid == 0) {                       // device counters (sampler clock / epoch cursor / optimizer step)
-        if (a.c0) *a.c0 += a.d0;
-        if (a.c1) *a.c1 += a.d1;
-        if (a.c2) *a.c2 += a.d2;
-    }
+    if (grp == 0 && half == 0 && tid == 0) tail_bump_counters(a.c0, a.d0, a.c1, a.d1, a.c2, a.d2);
 }
 
 // Split form, first launch: only the z helpers (+ gather riders).  A lean kernel -- no main-workgroup code path, so it
@@ -487,11 +372,11 @@ __global__ __launch_bounds__(TAIL_THREADS, 4) void sage_tail_z_kernel(const Tail
 static size_t tail_z_lds_bytes(int D) { return ((size_t)TAIL_ROWS * (D + 4) + (size_t)TAIL_WAVES * TAIL_ROWS * 64) * sizeof(float); }
 
 template <int D, int O>
-static int launch_tail_z(const TailArgs& a, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_tail_z(const TailArgs& a, const TailRiders& R) {
     const int tail_blocks = (int)gs_ceil_div(a.n, TAIL_ROWS);
-    const int64_t blocks = (int64_t)tail_blocks * (2 * O / 64) + gs_ceil_div(gather_waves, TAIL_WAVES);
+    const int64_t blocks = (int64_t)tail_blocks * (2 * O / 64) + gs_ceil_div(R.waves, TAIL_WAVES);
     GS_REQUIRE(blocks < (1ll << 31), "gs_sage_tail_z: grid too large");
-    hipLaunchKernelGGL((sage_tail_z_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), tail_z_lds_bytes(D), st, a, tail_blocks, J);
+    hipLaunchKernelGGL((sage_tail_z_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), tail_z_lds_bytes(D), R.st, a, tail_blocks, R.J);
     GS_LAUNCH_CHECK("sage_tail_z_kernel");
     return GS_OK;
 }
@@ -517,93 +402,33 @@ __global__ __launch_bounds__(TAIL_THREADS, 4) void sage_tail_dh0_kernel(const Ta
     const int colbase = part * 128;                    // in [0, 2D)
     const int term = colbase >= D ? 1 : 0;             // workgroup-uniform
     const int cb = colbase - term * D;                 // first of this slab's 128 columns inside the term's D columns
-    constexpr int M7 = O / 16;
-    constexpr int ldzs = O + 4, ldi = 128 + 4;
+    constexpr int ldzs = O + 4;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* DZs = lds;                                  // [16][ldzs]   the term's half of dz
-    float* DIN = DZs + TAIL_ROWS * ldzs;               // [16][ldi]    this slab of [d_self | d_means]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, q = lane >> 4;
+    float* DIN = DZs + TAIL_ROWS * ldzs;               // [16][128 + 4]   this slab of [d_self | d_means]
+    const int tid = threadIdx.x;
     const int r0 = grp * TAIL_ROWS;
     const int n = (int)a.n;
-    const int s = a.s;
-    const int ldh0 = (int)a.ldh;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // ---- everything this workgroup reads is an input: issue it all up front
     // (1) the term's half of dz: 16 rows x O columns
     const int zr = min(tid / (O / 4), TAIL_ROWS - 1), zc = (tid % (O / 4)) * 4;
     const f32x4 dzv = *reinterpret_cast<const f32x4*>(a.dz + (int64_t)min(r0 + zr, n - 1) * a.lddz + term * O + zc);
-    // (2) this wave's 16 weight rows cb + 16 wave + j, all K = O columns (NT form, as phase 7 of the fused kernel)
-    f32x4 b7[M7];
-    {
-        const int ldw = (int)(term ? a.ldwn : a.ldws);
-        const float* B0 = (term ? a.Wn : a.Ws) + (cb + 16 * wave + j) * ldw + 4 * q;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) b7[m] = *reinterpret_cast<const f32x4*>(B0 + 16 * m);
-    }
-    // (3) the h0 values behind this thread's output float4s (their signs are the relu mask): thread = (row, float4 column)
-    const int hr = tid >> 5, hc = cb + 4 * (tid & 31);
-    const int hi = min(r0 + hr, n - 1);
-    f32x4 hv[TAIL_NB];
-    if (term == 0) {
-        hv[0] = *reinterpret_cast<const f32x4*>(a.h0 + hi * ldh0 + hc);
-    } else {
-        const float* nb = a.h0 + (n + hi * s) * ldh0 + hc;
-#pragma unroll
-        for (int u = 0; u < TAIL_NB; ++u) hv[u] = *reinterpret_cast<const f32x4*>(nb + min(u, s - 1) * ldh0);
-    }
+    // (2) this wave's 16 weight rows, (3) the h0 values behind this thread's output float4s
+    f32x4 b7[O / 16], hv[TAIL_NB];
+    tail_lean_dh0_load<O>(a, term, cb, r0, b7, hv);
     if (tid < TAIL_ROWS * (O / 4)) *reinterpret_cast<f32x4*>(DZs + zr * ldzs + zc) = (r0 + zr < n) ? dzv : zero4;
     lds_barrier();
-    // ---- the slab of [d_self | d_means]: one 16 x 16 tile per wave
-    {
-        const float* A = DZs + j * ldzs + 4 * q;
-        f32x4 acc = zero4;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(A + 16 * m);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = mfma16(a4[e], b7[m][e], acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) DIN[(4 * q + i) * ldi + 16 * wave + j] = acc[i];
-    }
-    lds_barrier();
-    // ---- d_h0: relu mask (+ the 1/s broadcast over the row's s neighbor rows for the d_means slabs)
-    if (r0 + hr < n) {
-        const int lddh0 = (int)a.lddh;
-        f32x4 g = *reinterpret_cast<const f32x4*>(DIN + hr * ldi + 4 * (tid & 31));
-        if (term == 0) {
-            f32x4 o;
-            o.x = hv[0].x > 0.f ? g.x : 0.f;
-            o.y = hv[0].y > 0.f ? g.y : 0.f;
-            o.z = hv[0].z > 0.f ? g.z : 0.f;
-            o.w = hv[0].w > 0.f ? g.w : 0.f;
-            *reinterpret_cast<f32x4*>(a.d_h0 + (r0 + hr) * lddh0 + hc) = o;
-        } else {
-            g *= 1.0f / (float)s;
-            float* dst = a.d_h0 + (n + (r0 + hr) * s) * lddh0 + hc;
-#pragma unroll
-            for (int u = 0; u < TAIL_NB; ++u) {
-                if (u < s) {
-                    f32x4 o;
-                    o.x = hv[u].x > 0.f ? g.x : 0.f;
-                    o.y = hv[u].y > 0.f ? g.y : 0.f;
-                    o.z = hv[u].z > 0.f ? g.z : 0.f;
-                    o.w = hv[u].w > 0.f ? g.w : 0.f;
-                    *reinterpret_cast<f32x4*>(dst + u * lddh0) = o;
-                }
-            }
-        }
-    }
+    tail_lean_dh0_finish<O, ldzs>(a, DZs, DIN, term, cb, r0, b7, hv);
 }
 
 template <int D, int O>
-static int launch_tail_dh0(const TailArgs& a, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_tail_dh0(const TailArgs& a, const TailRiders& R) {
     const size_t lds = ((size_t)TAIL_ROWS * (O + 4) + (size_t)TAIL_ROWS * (128 + 4)) * sizeof(float);
     const int tail_blocks = (int)gs_ceil_div(a.n, TAIL_ROWS);
-    const int64_t blocks = (int64_t)tail_blocks * (2 * D / 128) + gs_ceil_div(gather_waves, TAIL_WAVES);
+    const int64_t blocks = (int64_t)tail_blocks * (2 * D / 128) + gs_ceil_div(R.waves, TAIL_WAVES);
     GS_REQUIRE(blocks < (1ll << 31), "gs_sage_tail_dh0: grid too large");
-    hipLaunchKernelGGL((sage_tail_dh0_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, st, a, tail_blocks, J);
+    hipLaunchKernelGGL((sage_tail_dh0_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, R.st, a, tail_blocks, R.J);
     GS_LAUNCH_CHECK("sage_tail_dh0_kernel");
     return GS_OK;
 }
@@ -623,13 +448,13 @@ extern "C" int gs_sage_tail_supported(int32_t d_in, int32_t out_dim, int32_t C) 
 }
 
 template <int D, int O, int CW, int NH>
-static int launch_tail_nh(const TailArgs& a, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_tail_nh(const TailArgs& a, const TailRiders& R) {
     const size_t lds = tail_lds_bytes(a.D, a.O, a.C);
     GS_LDS_ATTR(160 * 1024, sage_tail_kernel<D, O, CW, NH>);
     const int tail_blocks = (int)gs_ceil_div(a.n, TAIL_ROWS);       // groups of 16 rows: (2 O / 64) z helpers + NH main workgroups each
-    const int64_t blocks = (int64_t)tail_blocks * ((a.z_ready ? 0 : 2 * O / 64) + NH) + gs_ceil_div(gather_waves, TAIL_WAVES);
+    const int64_t blocks = (int64_t)tail_blocks * ((a.z_ready ? 0 : 2 * O / 64) + NH) + gs_ceil_div(R.waves, TAIL_WAVES);
     GS_REQUIRE(blocks < (1ll << 31), "gs_sage_tail_fwd_bwd: grid too large");
-    hipLaunchKernelGGL((sage_tail_kernel<D, O, CW, NH>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, st, a, tail_blocks, J);
+    hipLaunchKernelGGL((sage_tail_kernel<D, O, CW, NH>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, R.st, a, tail_blocks, R.J);
     GS_LAUNCH_CHECK("sage_tail_kernel");
     return GS_OK;
 }
@@ -637,17 +462,17 @@ static int launch_tail_nh(const TailArgs& a, const CoGatherS& J, int64_t gather_
 // Training launches over 256 input columns run two main workgroups per group (see sage_tail_kernel); forward-only launches
 // (the second workgroup would have nothing of its own) and D = 128 (one input-gradient slab per wave already) run one.
 template <int D, int O, int CW>
-static int launch_tail_cw(const TailArgs& a, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_tail_cw(const TailArgs& a, const TailRiders& R) {
     if constexpr (D == 256) {
-        if (a.train && g_tail_halves) return launch_tail_nh<D, O, CW, 2>(a, J, gather_waves, st);
+        if (a.train && g_tail_halves) return launch_tail_nh<D, O, CW, 2>(a, R);
     }
-    return launch_tail_nh<D, O, CW, 1>(a, J, gather_waves, st);
+    return launch_tail_nh<D, O, CW, 1>(a, R);
 }
 
 template <int D, int O>
-static int launch_tail(const TailArgs& a, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_tail(const TailArgs& a, const TailRiders& R) {
     // C <= 64: one class per lane; 64 < C <= 128 (e.g. PPI's 121 sigmoid labels, example_supervised.sh): two
-    return a.C > 64 ? launch_tail_cw<D, O, 2>(a, J, gather_waves, st) : launch_tail_cw<D, O, 1>(a, J, gather_waves, st);
+    return a.C > 64 ? launch_tail_cw<D, O, 2>(a, R) : launch_tail_cw<D, O, 1>(a, R);
 }
 
 // means_ready: gs_sage_tail_fwd_bwd_means (`means` is an input, see TailArgs.means_ready)
@@ -655,21 +480,10 @@ static int tail_fwd_bwd_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_h
     GS_REQUIRE(q, "gs_sage_tail_fwd_bwd: null descriptor");
     if (q->n == 0) return GS_OK;
     GS_REQUIRE(q->n > 0 && q->s > 0, "gs_sage_tail_fwd_bwd: bad sizes");
-    if (q->s > TAIL_NB) {
-        gs_set_error("gs_sage_tail_fwd_bwd: at most %d samples per node (got %d)", TAIL_NB, q->s);
-        return GS_ENOTSUP;
-    }
-    GS_REQUIRE((q->n + q->n * (int64_t)q->s) * std::max(q->ldh, std::max(q->lddh, (int64_t)1)) < (1ll << 31),
-               "gs_sage_tail_fwd_bwd: (n + n*s) * ld must be < 2^31 (32-bit row offsets)");
-    if (!gs_sage_tail_supported(q->d_in, q->out_dim, q->C)) {
-        gs_set_error("gs_sage_tail_fwd_bwd: unsupported shape d_in=%d out_dim=%d C=%d (d_in in {128,256}, out_dim in {64,128}, C <= 128)",
-                     q->d_in, q->out_dim, q->C);
-        return GS_ENOTSUP;
-    }
+    if (int rc = tail_check_shared("gs_sage_tail_fwd_bwd", q->n, q->s, q->d_in, q->out_dim, q->C, true, q->h0, q->ldh, q->lddh, q->W_self,
+                                   q->ldws, q->W_neigh, q->ldwn))
+        return rc;
     const int D = q->d_in, O = q->out_dim, Z = 2 * O, Cp4 = (q->C + 3) & ~3;
-    GS_CHECK_MAT(q->h0, q->ldh, "gs_sage_tail_fwd_bwd h0");
-    GS_CHECK_MAT(q->W_self, q->ldws, "gs_sage_tail_fwd_bwd W_self");
-    GS_CHECK_MAT(q->W_neigh, q->ldwn, "gs_sage_tail_fwd_bwd W_neigh");
     GS_CHECK_MAT(q->W_head, q->ldwh, "gs_sage_tail_fwd_bwd W_head");
     GS_CHECK_MAT(q->means, q->ldm, "gs_sage_tail_fwd_bwd means");
     GS_CHECK_MAT(q->z, q->ldz, "gs_sage_tail_fwd_bwd z");
@@ -685,13 +499,11 @@ static int tail_fwd_bwd_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_h
         GS_REQUIRE(q->lddz >= Z && q->lddh >= D, "gs_sage_tail_fwd_bwd: gradient leading dimension too small");
     }
     TailArgs a = {};
-    a.h0 = q->h0; a.ldh = q->ldh; a.n = q->n; a.s = q->s; a.D = D;
-    a.Ws = q->W_self; a.ldws = q->ldws; a.Wn = q->W_neigh; a.ldwn = q->ldwn; a.O = O;
+    tail_args_shared(a, q, q->n);
     a.Wh = q->W_head; a.ldwh = q->ldwh; a.bh = q->b_head; a.labels = q->labels; a.ldlab = q->ldlab; a.C = q->C;
     a.sigmoid = q->sigmoid;
-    a.means = q->means; a.ldm = q->ldm; a.z = q->z; a.ldz = q->ldz; a.y = q->y; a.ldy = q->ldy;
     a.logits = q->logits; a.ldlo = q->ldlo; a.preds = q->preds; a.ldp = q->ldp; a.dlogits = q->dlogits; a.lddl = q->lddl;
-    a.loss_rows = q->loss_rows; a.dz = q->dz; a.lddz = q->lddz; a.d_h0 = q->d_h0; a.lddh = q->lddh;
+    a.loss_rows = q->loss_rows;
     a.c0 = q->c0; a.d0 = q->d0; a.c1 = q->c1; a.d1 = q->d1; a.c2 = q->c2; a.d2 = q->d2;
     a.train = q->train ? 1 : 0;
     a.z_ready = q->z_ready ? 1 : 0;
@@ -709,17 +521,9 @@ static int tail_fwd_bwd_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_h
                                       "private to the caller's stream) missing");
     GS_REQUIRE(!q->sync || (reinterpret_cast<uintptr_t>(q->sync) & 7u) == 0, "gs_sage_tail_fwd_bwd: sync must be 8-byte aligned");
     a.sync = q->sync;
-    hipStream_t st = (hipStream_t)stream;
-    CoGatherS J = {};
-    int64_t gw = 0;
-    {
-        int rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
-        if (rc != GS_OK) return rc;
-    }
-    if (D == 256 && O == 128) return launch_tail<256, 128>(a, J, gw, st);
-    if (D == 256 && O == 64) return launch_tail<256, 64>(a, J, gw, st);
-    if (D == 128 && O == 128) return launch_tail<128, 128>(a, J, gw, st);
-    return launch_tail<128, 64>(a, J, gw, st);
+    TailRiders R;
+    if (int rc = tail_riders(jobs_host, n_jobs, stream, &R)) return rc;
+    return TAIL_DISPATCH(D, O, launch_tail, a, R);
 }
 
 extern "C" int gs_sage_tail_fwd_bwd(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
@@ -737,27 +541,15 @@ static int tail_z_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_host, i
     GS_REQUIRE(q, "gs_sage_tail_z: null descriptor");
     if (q->n == 0) return GS_OK;
     GS_REQUIRE(q->n > 0 && q->s > 0, "gs_sage_tail_z: bad sizes");
-    if (q->s > TAIL_NB) {
-        gs_set_error("gs_sage_tail_z: at most %d samples per node (got %d)", TAIL_NB, q->s);
-        return GS_ENOTSUP;
-    }
-    GS_REQUIRE((q->n + q->n * (int64_t)q->s) * std::max(q->ldh, (int64_t)1) < (1ll << 31),
-               "gs_sage_tail_z: (n + n*s) * ld must be < 2^31 (32-bit row offsets)");
-    if (!gs_sage_tail_supported(q->d_in, q->out_dim, q->C > 0 ? q->C : 1)) {
-        gs_set_error("gs_sage_tail_z: unsupported shape d_in=%d out_dim=%d", q->d_in, q->out_dim);
-        return GS_ENOTSUP;
-    }
+    if (int rc = tail_check_shared("gs_sage_tail_z", q->n, q->s, q->d_in, q->out_dim, q->C > 0 ? q->C : 1, false, q->h0, q->ldh, 0, q->W_self,
+                                   q->ldws, q->W_neigh, q->ldwn))
+        return rc;
     const int D = q->d_in, O = q->out_dim, Z = 2 * O;
-    GS_CHECK_MAT(q->h0, q->ldh, "gs_sage_tail_z h0");
-    GS_CHECK_MAT(q->W_self, q->ldws, "gs_sage_tail_z W_self");
-    GS_CHECK_MAT(q->W_neigh, q->ldwn, "gs_sage_tail_z W_neigh");
     GS_CHECK_MAT(q->means, q->ldm, "gs_sage_tail_z means");
     GS_CHECK_MAT(q->z, q->ldz, "gs_sage_tail_z z");
     GS_REQUIRE(q->ldh >= D && q->ldws >= O && q->ldwn >= O && q->ldm >= D && q->ldz >= Z, "gs_sage_tail_z: leading dimension too small");
     TailArgs a = {};
-    a.h0 = q->h0; a.ldh = q->ldh; a.n = q->n; a.s = q->s; a.D = D;
-    a.Ws = q->W_self; a.ldws = q->ldws; a.Wn = q->W_neigh; a.ldwn = q->ldwn; a.O = O;
-    a.means = q->means; a.ldm = q->ldm; a.z = q->z; a.ldz = q->ldz;
+    tail_args_shared(a, q, q->n);
     a.z_ready = 1;
     a.gcn = q->gcn ? 1 : 0;
     if (means_ready && q->gcn) {
@@ -767,17 +559,9 @@ static int tail_z_impl(const gs_tail_desc* q, const gs_gather_desc* jobs_host, i
     a.means_ready = means_ready ? 1 : 0;
     GS_REQUIRE(q->ids_copy_n >= 0 && (q->ids_copy_n == 0 || (q->ids_copy_src && q->ids_copy_dst)), "gs_sage_tail_z: ids_copy pointers missing");
     a.ids_copy_src = q->ids_copy_src; a.ids_copy_dst = q->ids_copy_dst; a.ids_copy_n = q->ids_copy_n;
-    hipStream_t st = (hipStream_t)stream;
-    CoGatherS J = {};
-    int64_t gw = 0;
-    {
-        int rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
-        if (rc != GS_OK) return rc;
-    }
-    if (D == 256 && O == 128) return launch_tail_z<256, 128>(a, J, gw, st);
-    if (D == 256 && O == 64) return launch_tail_z<256, 64>(a, J, gw, st);
-    if (D == 128 && O == 128) return launch_tail_z<128, 128>(a, J, gw, st);
-    return launch_tail_z<128, 64>(a, J, gw, st);
+    TailRiders R;
+    if (int rc = tail_riders(jobs_host, n_jobs, stream, &R)) return rc;
+    return TAIL_DISPATCH(D, O, launch_tail_z, a, R);
 }
 
 extern "C" int gs_sage_tail_z(const gs_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
@@ -794,20 +578,10 @@ extern "C" int gs_sage_tail_dh0(const gs_tail_desc* q, const gs_gather_desc* job
     GS_REQUIRE(q, "gs_sage_tail_dh0: null descriptor");
     if (q->n == 0) return GS_OK;
     GS_REQUIRE(q->n > 0 && q->s > 0, "gs_sage_tail_dh0: bad sizes");
-    if (q->s > TAIL_NB) {
-        gs_set_error("gs_sage_tail_dh0: at most %d samples per node (got %d)", TAIL_NB, q->s);
-        return GS_ENOTSUP;
-    }
-    GS_REQUIRE((q->n + q->n * (int64_t)q->s) * std::max(q->ldh, std::max(q->lddh, (int64_t)1)) < (1ll << 31),
-               "gs_sage_tail_dh0: (n + n*s) * ld must be < 2^31 (32-bit row offsets)");
-    if (!gs_sage_tail_supported(q->d_in, q->out_dim, 1)) {
-        gs_set_error("gs_sage_tail_dh0: unsupported shape d_in=%d out_dim=%d", q->d_in, q->out_dim);
-        return GS_ENOTSUP;
-    }
+    if (int rc = tail_check_shared("gs_sage_tail_dh0", q->n, q->s, q->d_in, q->out_dim, 1, false, q->h0, q->ldh, q->lddh, q->W_self, q->ldws,
+                                   q->W_neigh, q->ldwn))
+        return rc;
     const int D = q->d_in, O = q->out_dim, Z = 2 * O;
-    GS_CHECK_MAT(q->h0, q->ldh, "gs_sage_tail_dh0 h0");
-    GS_CHECK_MAT(q->W_self, q->ldws, "gs_sage_tail_dh0 W_self");
-    GS_CHECK_MAT(q->W_neigh, q->ldwn, "gs_sage_tail_dh0 W_neigh");
     GS_CHECK_MAT(q->dz, q->lddz, "gs_sage_tail_dh0 dz");
     GS_CHECK_MAT(q->d_h0, q->lddh, "gs_sage_tail_dh0 d_h0");
     GS_REQUIRE(q->ldh >= D && q->ldws >= O && q->ldwn >= O && q->lddz >= Z && q->lddh >= D, "gs_sage_tail_dh0: leading dimension too small");
@@ -816,19 +590,9 @@ extern "C" int gs_sage_tail_dh0(const gs_tail_desc* q, const gs_gather_desc* job
         return GS_ENOTSUP;
     }
     TailArgs a = {};
-    a.h0 = q->h0; a.ldh = q->ldh; a.n = q->n; a.s = q->s; a.D = D;
-    a.Ws = q->W_self; a.ldws = q->ldws; a.Wn = q->W_neigh; a.ldwn = q->ldwn; a.O = O;
-    a.dz = q->dz; a.lddz = q->lddz; a.d_h0 = q->d_h0; a.lddh = q->lddh;
+    tail_args_shared(a, q, q->n);
     a.z_ready = 1;
-    hipStream_t st = (hipStream_t)stream;
-    CoGatherS J = {};
-    int64_t gw = 0;
-    {
-        int rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
-        if (rc != GS_OK) return rc;
-    }
-    if (D == 256 && O == 128) return launch_tail_dh0<256, 128>(a, J, gw, st);
-    if (D == 256 && O == 64) return launch_tail_dh0<256, 64>(a, J, gw, st);
-    if (D == 128 && O == 128) return launch_tail_dh0<128, 128>(a, J, gw, st);
-    return launch_tail_dh0<128, 64>(a, J, gw, st);
+    TailRiders R;
+    if (int rc = tail_riders(jobs_host, n_jobs, stream, &R)) return rc;
+    return TAIL_DISPATCH(D, O, launch_tail_dh0, a, R);
 }

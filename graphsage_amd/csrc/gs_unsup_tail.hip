@@ -68,56 +68,17 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
     float* gqs = Ns + LP_MAX_NEG * ldzs;               // [8][64]        dLoss/d(neg_aff) of pair p, negative q
     float* invs = gqs + 8 * 64;                        // [16]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int j = lane & 15, q = lane >> 4;
-    const int n = (int)a.n, s = a.s, ldh0 = (int)a.ldh;
     const int B = L.B, n_neg = L.n_neg;
-    const float inv_s = 1.0f / (float)s;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-    // ================= S0: this thread's h0 rows -> relu mask bits (phase 8 reads h0 exactly once, as bit flags)
+    // ================= S0: this thread's h0 rows -> relu mask bits (phase 6 reads h0 exactly once, as bit flags)
     uint32_t mself[PASSES], mnb[PASSES][2];
-    {
-        f32x4 hself[PASSES], hnb[PASSES][TAIL_NB];
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int it = tid + p * TAIL_THREADS;
-            const int r = it / D4, c = (it % D4) * 4;
-            bool valid;
-            const int i = tail_row(a, grp, r, valid);
-            hself[p] = *reinterpret_cast<const f32x4*>(a.h0 + i * ldh0 + c);
-            const float* nb = a.h0 + (n + i * s) * ldh0 + c;
-#pragma unroll
-            for (int u = 0; u < TAIL_NB; ++u) hnb[p][u] = *reinterpret_cast<const f32x4*>(nb + min(u, s - 1) * ldh0);
-        }
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            mnb[p][0] = mnb[p][1] = 0u;
-#pragma unroll
-            for (int u = 0; u < TAIL_NB; ++u) {
-                const f32x4 v = hnb[p][u];
-                const uint32_t bits = (v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u);
-                mnb[p][u >> 3] |= bits << (4 * (u & 7));
-            }
-            const f32x4 hs = hself[p];
-            mself[p] = (hs.x > 0.f ? 1u : 0u) | (hs.y > 0.f ? 2u : 0u) | (hs.z > 0.f ? 4u : 0u) | (hs.w > 0.f ? 8u : 0u);
-            asm volatile("" : "+v"(mself[p]), "+v"(mnb[p][0]), "+v"(mnb[p][1]));      // pin the flags, free the rows
-        }
-    }
+    tail_relu_mask_bits<D4, PASSES>(a, 0, [&](const int r) { bool valid; return tail_row(a, grp, r, valid); }, mself, mnb);
     // ================= S1: the weight slabs of the input-gradient contraction (they land while the helpers compute z)
     f32x4 b7[DPW][M7][2];
     if (a.train) {
 #pragma unroll
-        for (int sl = 0; sl < DPW; ++sl) {
-            const int col0 = (wave + sl * TAIL_WAVES) * 32;          // in [0, 2D)
-            const int term = col0 >= D ? 1 : 0;
-            const int ldw = (int)(term ? a.ldwn : a.ldws);
-            const float* B0 = (term ? a.Wn : a.Ws) + (col0 - term * D + j) * ldw + 4 * q;
-#pragma unroll
-            for (int m = 0; m < M7; ++m) {
-                b7[sl][m][0] = *reinterpret_cast<const f32x4*>(B0 + 16 * m);
-                b7[sl][m][1] = *reinterpret_cast<const f32x4*>(B0 + 16 * ldw + 16 * m);
-            }
-        }
+        for (int sl = 0; sl < DPW; ++sl) tail_din_slab_load<D, O>(a, (wave + sl * TAIL_WAVES) * 32, b7[sl]);
     }
 
     // ---------------- phase 1: pick up z of the own group and of the negatives (bounded waits, see sage_tail_kernel)
@@ -169,39 +130,19 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
         const int row = wave * 2 + rr;
         bool valid;
         const int i = tail_row(a, grp, row, valid);
-        float v[DJ];
-        float ss = 0.f;
-#pragma unroll
-        for (int m = 0; m < DJ; ++m) {
-            v[m] = Zs[row * ldzs + lane + 64 * m];
-            ss += v[m] * v[m];
-        }
-        ss = tail_wave_sum(ss);
-        const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
-#pragma unroll
-        for (int m = 0; m < DJ; ++m) {
-            const float y = v[m] * inv;
-            Zs[row * ldzs + lane + 64 * m] = y;
-            if (valid) a.y[i * (int)a.ldy + lane + 64 * m] = y;
-        }
+        float* const yp = a.y;
+        const int yi = i * (int)a.ldy + lane;
+        const float inv = tail_l2norm_row<DJ>(Zs, row * ldzs, [=](const int m, float, const float y) {
+            if (valid) yp[yi + 64 * m] = y;
+        });
         if (lane == 0) invs[row] = inv;
     }
     for (int nq = wave; nq < n_neg; nq += TAIL_WAVES) {
-        float v[DJ];
-        float ss = 0.f;
-#pragma unroll
-        for (int m = 0; m < DJ; ++m) {
-            v[m] = Ns[nq * ldzs + lane + 64 * m];
-            ss += v[m] * v[m];
-        }
-        ss = tail_wave_sum(ss);
-        const float inv = __builtin_amdgcn_rsqf(fmaxf(ss, 1e-12f));
-#pragma unroll
-        for (int m = 0; m < DJ; ++m) {
-            const float y = v[m] * inv;
-            Ns[nq * ldzs + lane + 64 * m] = y;
-            if (grp == 0) a.y[(2 * B + nq) * (int)a.ldy + lane + 64 * m] = y;
-        }
+        float* const yp = a.y;
+        const int yi = (2 * B + nq) * (int)a.ldy + lane;
+        tail_l2norm_row<DJ>(Ns, nq * ldzs, [=](const int m, float, const float y) {
+            if (grp == 0) yp[yi + 64 * m] = y;
+        });
     }
     lds_barrier();
 
@@ -278,22 +219,15 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
 #pragma unroll
                 for (int m = 0; m < DJ; ++m) g1[m] += gq * Ns[qn * ldzs + lane + 64 * m];
             }
-            // back through y = z * inv:  dz = inv (g - y <g, y>);  clamped (sum z^2 < 1e-12, inv = 1e6): dz = g * inv
-            float dot1 = 0.f, dot2 = 0.f;
+            float gb[DJ], dz1[DJ], dz2[DJ];
+#pragma unroll
+            for (int m = 0; m < DJ; ++m) gb[m] = da * o1[m];
+            tail_l2norm_bwd_row(g1, o1, invs[p], dz1);
+            tail_l2norm_bwd_row(gb, o2, invs[8 + p], dz2);
 #pragma unroll
             for (int m = 0; m < DJ; ++m) {
-                dot1 += g1[m] * o1[m];
-                dot2 += da * o1[m] * o2[m];
-            }
-            dot1 = tail_wave_sum(dot1);
-            dot2 = tail_wave_sum(dot2);
-            const float inv1 = invs[p], inv2 = invs[8 + p];
-            const bool c1 = inv1 >= 1.0e6f, c2 = inv2 >= 1.0e6f;
-#pragma unroll
-            for (int m = 0; m < DJ; ++m) {
-                const float ga = g1[m], gb = da * o1[m];
-                const float d1 = live ? (c1 ? ga * inv1 : inv1 * (ga - o1[m] * dot1)) : 0.f;
-                const float d2 = live ? (c2 ? gb * inv2 : inv2 * (gb - o2[m] * dot2)) : 0.f;
+                const float d1 = live ? dz1[m] : 0.f;
+                const float d2 = live ? dz2[m] : 0.f;
                 DZs[p * ldzs + lane + 64 * m] = d1;
                 DZs[(8 + p) * ldzs + lane + 64 * m] = d2;
                 if (live) {
@@ -324,61 +258,11 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_lp_tail_kernel(const LpArgs
 
     // ---------------- phase 5: [d_self | d_means] = [d_z[:, :O] . W_self^T | d_z[:, O:] . W_neigh^T]  -> DIN
 #pragma unroll
-    for (int sl = 0; sl < DPW; ++sl) {
-        const int col0 = (wave + sl * TAIL_WAVES) * 32;
-        const int term = col0 >= D ? 1 : 0;
-        const float* A = DZs + term * O + j * ldzs + 4 * q;
-        f32x4 acc0 = zero4, acc1 = zero4;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(A + 16 * m);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc0 = mfma16(a4[e], b7[sl][m][0][e], acc0);
-                acc1 = mfma16(a4[e], b7[sl][m][1][e], acc1);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            DIN[(4 * q + i) * ldi + col0 + j] = acc0[i];
-            DIN[(4 * q + i) * ldi + col0 + 16 + j] = acc1[i];
-        }
-    }
+    for (int sl = 0; sl < DPW; ++sl) tail_din_slab_contract<D, O>(DZs, DIN, (wave + sl * TAIL_WAVES) * 32, b7[sl]);
     lds_barrier();
 
     // ---------------- phase 6: d_h0 = relu'(h0) * (d_self on the self row, d_means / s on each of the s neighbor rows)
-    {
-        const int lddh0 = (int)a.lddh;
-#pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int it = tid + p * TAIL_THREADS;
-            const int r = it / D4, c = (it % D4) * 4;
-            bool valid;
-            const int i = tail_row(a, grp, r, valid);
-            if (valid) {
-                const f32x4 g_self = *reinterpret_cast<const f32x4*>(DIN + r * ldi + c);
-                const f32x4 g_mean = *reinterpret_cast<const f32x4*>(DIN + r * ldi + D + c) * inv_s;
-                f32x4 o;
-                o.x = (mself[p] & 1u) ? g_self.x : 0.f;
-                o.y = (mself[p] & 2u) ? g_self.y : 0.f;
-                o.z = (mself[p] & 4u) ? g_self.z : 0.f;
-                o.w = (mself[p] & 8u) ? g_self.w : 0.f;
-                *reinterpret_cast<f32x4*>(a.d_h0 + i * lddh0 + c) = o;
-                float* dst = a.d_h0 + (n + i * s) * lddh0 + c;
-#pragma unroll
-                for (int u = 0; u < TAIL_NB; ++u) {
-                    if (u < s) {
-                        const uint32_t bits = mnb[p][u >> 3] >> (4 * (u & 7));
-                        o.x = (bits & 1u) ? g_mean.x : 0.f;
-                        o.y = (bits & 2u) ? g_mean.y : 0.f;
-                        o.z = (bits & 4u) ? g_mean.z : 0.f;
-                        o.w = (bits & 8u) ? g_mean.w : 0.f;
-                        *reinterpret_cast<f32x4*>(dst + u * lddh0) = o;
-                    }
-                }
-            }
-        }
-    }
+    tail_store_dh0<D, D4, PASSES>(a, DIN, 0, [&](const int r, bool& valid) { return tail_row(a, grp, r, valid); }, false, mself, mnb);
     tail_sync_done<HP>(a, G, grp, sync_base);
 }
 
@@ -389,8 +273,8 @@ template <int D, int O>
 __global__ __launch_bounds__(TAIL_THREADS, 2) void lp_neg_tail_kernel(const LpArgs L, const StepEpilogue epi, const CoGatherS J) {
     const TailArgs& a = L.t;
     constexpr int HP = 2;                              // as in sage_lp_tail_kernel
-    constexpr int NWG = 2 * D / 128, Z = 2 * O, Z4 = Z / 4, M7 = O / 16;
-    constexpr int ldzs = Z + 4, ldi = 128 + 4;
+    constexpr int NWG = 2 * D / 128, Z = 2 * O, Z4 = Z / 4;
+    constexpr int ldzs = Z + 4;
     const int GP = a.pair_groups;
     const int NGH = (L.n_neg + TAIL_ROWS - 1) / TAIL_ROWS;
     const int G = GP + NGH;
@@ -433,11 +317,7 @@ __global__ __launch_bounds__(TAIL_THREADS, 2) void lp_neg_tail_kernel(const LpAr
                 else epi.aux_out[0] = tot * epi.aux_scale;
             }
         }
-        if (tid == 0) {
-            if (epi.c0) *epi.c0 += epi.d0;
-            if (epi.c1) *epi.c1 += epi.d1;
-            if (epi.c2) *epi.c2 += epi.d2;
-        }
+        if (tid == 0) tail_bump_counters(epi.c0, epi.d0, epi.c1, epi.d1, epi.c2, epi.d2);
         return;
     }
     const int ng = (int)blockIdx.x / NWG, part = (int)blockIdx.x % NWG;
@@ -445,29 +325,13 @@ __global__ __launch_bounds__(TAIL_THREADS, 2) void lp_neg_tail_kernel(const LpAr
     const int term = colbase >= D ? 1 : 0;
     const int cb = colbase - term * D;
     float* DZs = lds;                                  // [16][ldzs]   dz of the group's 16 negative rows (all Z columns)
-    float* DIN = DZs + TAIL_ROWS * ldzs;               // [16][ldi]    this slab of [d_self | d_means]
-    const int j = lane & 15, q = lane >> 4;
-    const int n = (int)a.n, s = a.s, ldh0 = (int)a.ldh, B = L.B, n_neg = L.n_neg;
+    float* DIN = DZs + TAIL_ROWS * ldzs;               // [16][128 + 4]   this slab of [d_self | d_means]
+    const int B = L.B, n_neg = L.n_neg;
     const int r0 = 2 * B + TAIL_ROWS * ng;             // first row of the group
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // ---- inputs that depend on nothing computed here: issue them first
-    f32x4 b7[M7];
-    {
-        const int ldw = (int)(term ? a.ldwn : a.ldws);
-        const float* B0 = (term ? a.Wn : a.Ws) + (cb + 16 * wave + j) * ldw + 4 * q;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) b7[m] = *reinterpret_cast<const f32x4*>(B0 + 16 * m);
-    }
-    const int hr = tid >> 5, hc = cb + 4 * (tid & 31);
-    const int hi = min(r0 + hr, n - 1);
-    f32x4 hv[TAIL_NB];
-    if (term == 0) {
-        hv[0] = *reinterpret_cast<const f32x4*>(a.h0 + hi * ldh0 + hc);
-    } else {
-        const float* nb = a.h0 + (n + hi * s) * ldh0 + hc;
-#pragma unroll
-        for (int u = 0; u < TAIL_NB; ++u) hv[u] = *reinterpret_cast<const f32x4*>(nb + min(u, s - 1) * ldh0);
-    }
+    f32x4 b7[O / 16], hv[TAIL_NB];
+    tail_lean_dh0_load<O>(a, term, cb, r0, b7, hv);
     // ---- the rows' gradient w.r.t. their normalised embeddings: slabs of all mains, summed in main order (16 loads in flight);
     //      wave w owns rows w and w + 8, lane = float4 column
     // (both rows' slab loads are issued together: 2 x 16 float4 in flight per lane, 4 round trips for 64 slabs instead of 8)
@@ -520,47 +384,7 @@ __global__ __launch_bounds__(TAIL_THREADS, 2) void lp_neg_tail_kernel(const LpAr
         }
     }
     lds_barrier();
-    // ---- the slab of [d_self | d_means]: one 16 x 16 tile per wave
-    {
-        const float* A = DZs + term * O + j * ldzs + 4 * q;
-        f32x4 acc = zero4;
-#pragma unroll
-        for (int m = 0; m < M7; ++m) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(A + 16 * m);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = mfma16(a4[e], b7[m][e], acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) DIN[(4 * q + i) * ldi + 16 * wave + j] = acc[i];
-    }
-    lds_barrier();
-    // ---- d_h0: relu mask (+ the 1/s broadcast over the row's s neighbor rows for the d_means slabs)
-    if (r0 + hr < n) {
-        const int lddh0 = (int)a.lddh;
-        f32x4 g = *reinterpret_cast<const f32x4*>(DIN + hr * ldi + 4 * (tid & 31));
-        if (term == 0) {
-            f32x4 o;
-            o.x = hv[0].x > 0.f ? g.x : 0.f;
-            o.y = hv[0].y > 0.f ? g.y : 0.f;
-            o.z = hv[0].z > 0.f ? g.z : 0.f;
-            o.w = hv[0].w > 0.f ? g.w : 0.f;
-            *reinterpret_cast<f32x4*>(a.d_h0 + (r0 + hr) * lddh0 + hc) = o;
-        } else {
-            g *= 1.0f / (float)s;
-            float* dst = a.d_h0 + (n + (r0 + hr) * s) * lddh0 + hc;
-#pragma unroll
-            for (int u = 0; u < TAIL_NB; ++u) {
-                if (u < s) {
-                    f32x4 o;
-                    o.x = hv[u].x > 0.f ? g.x : 0.f;
-                    o.y = hv[u].y > 0.f ? g.y : 0.f;
-                    o.z = hv[u].z > 0.f ? g.z : 0.f;
-                    o.w = hv[u].w > 0.f ? g.w : 0.f;
-                    *reinterpret_cast<f32x4*>(dst + u * lddh0) = o;
-                }
-            }
-        }
-    }
+    tail_lean_dh0_finish<O, ldzs>(a, DZs + term * O, DIN, term, cb, r0, b7, hv);
 }
 
 static size_t lp_tail_lds_bytes(int D, int O) {
@@ -577,24 +401,24 @@ extern "C" int gs_linkpred_tail_supported(int32_t d_in, int32_t out_dim, int32_t
 }
 
 template <int D, int O>
-static int launch_lp_tail(const LpArgs& L, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_lp_tail(const LpArgs& L, const TailRiders& R) {
     GS_LDS_ATTR(160 * 1024, sage_lp_tail_kernel<D, O>);
     const int NGH = (L.n_neg + TAIL_ROWS - 1) / TAIL_ROWS;
     const int G = L.t.pair_groups + NGH;
-    const int64_t blocks = (int64_t)2 * G + L.t.pair_groups + gs_ceil_div(gather_waves, TAIL_WAVES);
+    const int64_t blocks = (int64_t)2 * G + L.t.pair_groups + gs_ceil_div(R.waves, TAIL_WAVES);
     GS_REQUIRE(blocks < (1ll << 31), "gs_linkpred_tail: grid too large");
-    hipLaunchKernelGGL((sage_lp_tail_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lp_tail_lds_bytes(D, O), st, L, J);
+    hipLaunchKernelGGL((sage_lp_tail_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lp_tail_lds_bytes(D, O), R.st, L, R.J);
     GS_LAUNCH_CHECK("sage_lp_tail_kernel");
     return GS_OK;
 }
 
 template <int D, int O>
-static int launch_lp_neg(const LpArgs& L, const StepEpilogue& epi, const CoGatherS& J, int64_t gather_waves, hipStream_t st) {
+static int launch_lp_neg(const LpArgs& L, const StepEpilogue& epi, const TailRiders& R) {
     const int NGH = (L.n_neg + TAIL_ROWS - 1) / TAIL_ROWS;
     const size_t lds = ((size_t)TAIL_ROWS * (2 * O + 4) + (size_t)TAIL_ROWS * (128 + 4)) * sizeof(float);
-    const int64_t blocks = (L.t.train ? (2 * D / 128) * NGH : 0) + 1 + gs_ceil_div(gather_waves, TAIL_WAVES);
+    const int64_t blocks = (L.t.train ? (2 * D / 128) * NGH : 0) + 1 + gs_ceil_div(R.waves, TAIL_WAVES);
     GS_REQUIRE(blocks < (1ll << 31), "gs_linkpred_tail_neg: grid too large");
-    hipLaunchKernelGGL((lp_neg_tail_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, st, L, epi, J);
+    hipLaunchKernelGGL((lp_neg_tail_kernel<D, O>), dim3((unsigned)blocks), dim3(TAIL_THREADS), lds, R.st, L, epi, R.J);
     GS_LAUNCH_CHECK("lp_neg_tail_kernel");
     return GS_OK;
 }
@@ -609,11 +433,7 @@ static int lp_args(const gs_lp_tail_desc* q, LpArgs* out, const char* who) {
     }
     const int D = q->d_in, O = q->out_dim, Z = 2 * O;
     const int64_t n = 2 * q->B + q->n_neg;
-    GS_REQUIRE((n + n * (int64_t)q->s) * std::max(q->ldh, std::max(q->lddh, (int64_t)1)) < (1ll << 31),
-               "%s: (n + n*s) * ld must be < 2^31 (32-bit row offsets)", who);
-    GS_CHECK_MAT(q->h0, q->ldh, "gs_linkpred_tail h0");
-    GS_CHECK_MAT(q->W_self, q->ldws, "gs_linkpred_tail W_self");
-    GS_CHECK_MAT(q->W_neigh, q->ldwn, "gs_linkpred_tail W_neigh");
+    if (int rc = tail_check_shared(who, n, q->s, D, O, -1, false, q->h0, q->ldh, q->lddh, q->W_self, q->ldws, q->W_neigh, q->ldwn)) return rc;
     GS_CHECK_MAT(q->means, q->ldm, "gs_linkpred_tail means");
     GS_CHECK_MAT(q->z, q->ldz, "gs_linkpred_tail z");
     GS_CHECK_MAT(q->y, q->ldy, "gs_linkpred_tail y");
@@ -626,10 +446,7 @@ static int lp_args(const gs_lp_tail_desc* q, LpArgs* out, const char* who) {
     }
     LpArgs L = {};
     TailArgs& a = L.t;
-    a.h0 = q->h0; a.ldh = q->ldh; a.n = n; a.s = q->s; a.D = D;
-    a.Ws = q->W_self; a.ldws = q->ldws; a.Wn = q->W_neigh; a.ldwn = q->ldwn; a.O = O;
-    a.means = q->means; a.ldm = q->ldm; a.z = q->z; a.ldz = q->ldz; a.y = q->y; a.ldy = q->ldy;
-    a.dz = q->dz; a.lddz = q->lddz; a.d_h0 = q->d_h0; a.lddh = q->lddh;
+    tail_args_shared(a, q, n);
     a.train = q->train ? 1 : 0;
     a.sync = q->sync;
     a.pairB = (int32_t)q->B;
@@ -647,16 +464,10 @@ static int linkpred_tail_impl(const gs_lp_tail_desc* q, const gs_gather_desc* jo
     int rc = lp_args(q, &L, "gs_linkpred_tail");
     if (rc != GS_OK) return rc;
     L.t.means_ready = means_ready ? 1 : 0;
-    CoGatherS J = {};
-    int64_t gw = 0;
-    rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
+    TailRiders R;
+    rc = tail_riders(jobs_host, n_jobs, stream, &R);
     if (rc != GS_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int D = q->d_in, O = q->out_dim;
-    if (D == 256 && O == 128) return launch_lp_tail<256, 128>(L, J, gw, st);
-    if (D == 256 && O == 64) return launch_lp_tail<256, 64>(L, J, gw, st);
-    if (D == 128 && O == 128) return launch_lp_tail<128, 128>(L, J, gw, st);
-    return launch_lp_tail<128, 64>(L, J, gw, st);
+    return TAIL_DISPATCH(q->d_in, q->out_dim, launch_lp_tail, L, R);
 }
 
 extern "C" int gs_linkpred_tail(const gs_lp_tail_desc* q, const gs_gather_desc* jobs_host, int32_t n_jobs, void* stream) {
@@ -673,9 +484,8 @@ extern "C" int gs_linkpred_tail_neg(const gs_lp_tail_desc* q, float* loss_out, i
     LpArgs L;
     int rc = lp_args(q, &L, "gs_linkpred_tail_neg");
     if (rc != GS_OK) return rc;
-    CoGatherS J = {};
-    int64_t gw = 0;
-    rc = build_cojobs_s(jobs_host, n_jobs, &J, &gw);
+    TailRiders R;
+    rc = tail_riders(jobs_host, n_jobs, stream, &R);
     if (rc != GS_OK) return rc;
     StepEpilogue epi = {};
     if (loss_out) {
@@ -683,10 +493,5 @@ extern "C" int gs_linkpred_tail_neg(const gs_lp_tail_desc* q, float* loss_out, i
         const float inv_b = 1.0f / (float)q->B;
         epi = StepEpilogue{q->loss_rows, q->B, inv_b, loss_out, accumulate, q->rr_rows, inv_b, mrr_out, c0, d0, c1, d1, c2, d2};
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int D = q->d_in, O = q->out_dim;
-    if (D == 256 && O == 128) return launch_lp_neg<256, 128>(L, epi, J, gw, st);
-    if (D == 256 && O == 64) return launch_lp_neg<256, 64>(L, epi, J, gw, st);
-    if (D == 128 && O == 128) return launch_lp_neg<128, 128>(L, epi, J, gw, st);
-    return launch_lp_neg<128, 64>(L, epi, J, gw, st);
+    return TAIL_DISPATCH(q->d_in, q->out_dim, launch_lp_neg, L, epi, R);
 }
