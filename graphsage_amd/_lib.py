@@ -173,6 +173,8 @@ _PROTOS = {
     "gs_csr_reduce_fwd": [_P, _P],
     "gs_rank_ws_bytes": [c_int64, c_int64, POINTER(c_int64)],
     "gs_rank_count": [_P, _P],
+    "gs_topk_ws_bytes": [c_int64, c_int64, c_int32, POINTER(c_int64)],
+    "gs_topk_select": [_P, _P],
 }
 
 
@@ -296,6 +298,19 @@ class RankDesc(ctypes.Structure):
 
 RANK_KEEP_SRC = 1                           # GS_RANK_KEEP_SRC (gs_rank_desc.flags)
 assert ctypes.sizeof(RankDesc) == 144      # static_assert in csrc/gs_rank.hip (passed by pointer, as CsrReduceDesc)
+
+
+class TopkDesc(ctypes.Structure):
+    """struct gs_topk_desc (include/graphsage_amd.h)"""
+    _fields_ = [("Xq", c_void_p), ("Zc", c_void_p), ("src", c_void_p), ("f_rowptr", c_void_p), ("f_col", c_void_p),
+                ("ids", c_void_p), ("scores", c_void_p), ("count", c_void_p), ("ws", c_void_p),
+                ("Q", c_int64), ("ldq", c_int64), ("n_rows", c_int64), ("n_cand", c_int64), ("ldz", c_int64),
+                ("f_nnz", c_int64), ("ws_bytes", c_int64),
+                ("d", c_int32), ("k", c_int32), ("flags", c_int32)]
+
+
+TOPK_MAX = 128                              # GS_TOPK_MAX
+assert ctypes.sizeof(TopkDesc) == 144      # static_assert in csrc/gs_topk.hip (passed by pointer, as RankDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -38,17 +38,12 @@
 // row of src[q] that fall into the tile.  The filter row is sorted, so the thread keeps a cursor into it (binary search at the
 // slice's first candidate, then it only moves forward).  The epilogue tests the bit, so a filtered cell is skipped with the
 // very score that would have been counted; dst listed in its own filter row just sets the same bit twice.
-#include "gs_common.h"
+//
+// The operand loads and stores, the compute stage, the exclusion-word builder and the slice plan live in gs_rank_dev.h, which
+// gs_topk.hip (the same sweep with a select epilogue) includes too; this kernel's resource report is what it was before.
+#include "gs_rank_dev.h"
 
 static_assert(sizeof(gs_rank_desc) == 144, "gs_rank_desc layout (mirrored by graphsage_amd/_lib.py)");
-
-#define RK_BM 128
-#define RK_BN 128
-#define RK_BK 32
-#define RK_KP 36                 // padded k stride (conflict-free ds_read_b128)
-#define RK_WG_TARGET 2048        // workgroups aimed at when the candidates are cut into slices
-#define RK_MIN_TILES 4           // candidate tiles per slice, at least (the t tile is a fifth)
-#define RK_MAX_TILES 16384       // ... and at most (packed 16-bit per-lane counters, unsigned)
 
 struct RankArgs {
     const float* Xq; const float* Zc;
@@ -60,15 +55,10 @@ struct RankArgs {
     int32_t keep_src;            // GS_RANK_KEEP_SRC: src only indexes the filter
 };
 
-// the word of 32 exclusion bits whose first `lim` columns exist (lim <= 0: none, lim >= 32: all)
-__device__ __forceinline__ uint32_t rank_tail_word(const int lim) {
-    return lim <= 0 ? 0xffffffffu : (lim < 32 ? (0xffffffffu << lim) : 0u);
-}
-
 // (256, 2): a budget of 256 registers per lane, two workgroups per CU
 __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
     constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
-    constexpr int STAGE_FLOATS = (BM + BN) * KP;
+    constexpr int STAGE_FLOATS = RK_STAGE_FLOATS;
     __shared__ __attribute__((aligned(16))) float smem[2 * STAGE_FLOATS];
     __shared__ __attribute__((aligned(16))) uint32_t excl[BM][4];      // bit c of row r: (query r, column c of the tile) is not a candidate
     __shared__ float tq[BM];
@@ -98,19 +88,7 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
             if (g.src) {
                 ss = g.src[q];
                 ss = ss < 0 ? 0 : ((int64_t)ss >= g.n_rows ? (int32_t)(g.n_rows - 1) : ss);
-                if (g.f_rowptr) {
-                    int64_t r0 = g.f_rowptr[ss], r1 = g.f_rowptr[ss + 1];
-                    r0 = min(max(r0, (int64_t)0), g.f_nnz);
-                    r1 = min(max(r1, r0), g.f_nnz);
-                    const int64_t first = (int64_t)tile0 * BN;
-                    int64_t lo = r0, hi = r1;                    // first entry >= the slice's first candidate
-                    while (lo < hi) {
-                        const int64_t mid = lo + ((hi - lo) >> 1);
-                        if ((int64_t)g.f_col[mid] < first) lo = mid + 1; else hi = mid;
-                    }
-                    cur = lo;
-                    cend = r1;
-                }
+                if (g.f_rowptr) rank_filter_cursor(g.f_rowptr, g.f_col, g.f_nnz, ss, (int64_t)tile0 * BN, cur, cend);
             }
         }
         dq[tid] = dd;
@@ -159,31 +137,8 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
                 b_ok[p] = r < g.n_cand;
                 b_row[p] = g.Zc + (b_ok[p] ? r : 0) * g.ldz + sk;
             }
-            if (tid < BM) {
-                uint32_t w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;         // four named words: an indexed array would live in scratch
-                const int64_t hi = n0 + BN;
-                if (g.n_cand < hi) {
-                    const int lim = (int)(g.n_cand - n0);            // 1 .. BN-1 columns exist
-                    w0 = rank_tail_word(lim); w1 = rank_tail_word(lim - 32);
-                    w2 = rank_tail_word(lim - 64); w3 = rank_tail_word(lim - 96);
-                }
-                auto set_bit = [&](const int cidx) {
-                    const uint32_t b = 1u << (cidx & 31);
-                    const int j = cidx >> 5;
-                    w0 |= j == 0 ? b : 0u; w1 |= j == 1 ? b : 0u;
-                    w2 |= j == 2 ? b : 0u; w3 |= j == 3 ? b : 0u;
-                };
-                const int64_t dd = dq[tid], ss = sq[tid];
-                if (dd >= n0 && dd < hi) set_bit((int)(dd - n0));
-                if (ss >= n0 && ss < hi) set_bit((int)(ss - n0));
-                while (cur < cend) {
-                    const int64_t cc = g.f_col[cur];
-                    if (cc >= hi) break;
-                    if (cc >= n0) set_bit((int)(cc - n0));
-                    ++cur;
-                }
-                *reinterpret_cast<uint4*>(&excl[tid][0]) = make_uint4(w0, w1, w2, w3);
-            }
+            if (tid < BM)
+                *reinterpret_cast<uint4*>(&excl[tid][0]) = rank_excl_words(n0, g.n_cand, dq[tid], sq[tid], g.f_col, cur, cend);
         }
 
         f32x16 acc[2][2];
@@ -195,50 +150,14 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
         f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
+        // (the three lambdas stay: with the helpers called directly the compiler's report moves from 229 to 237 registers)
         auto load_tiles = [&](const int k0, f32x4 (&ra)[4], f32x4 (&rb)[4]) {
-            const bool k_ok = k0 + sk < d;           // d % 4 == 0: a float4 is whole or absent (the zero-padded K tail)
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (a_ok[p] && k_ok) v = *reinterpret_cast<const f32x4*>(a_row[p] + k0);
-                ra[p] = v;
-            }
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (b_ok[p] && k_ok) v = *reinterpret_cast<const f32x4*>(b_row[p] + k0);
-                rb[p] = v;
-            }
+            rank_load_tiles(k0, sk, d, a_row, a_ok, b_row, b_ok, ra, rb);
         };
         auto store_tiles = [&](const f32x4 (&ra)[4], const f32x4 (&rb)[4], float* As, float* Bs) {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4*>(&As[(p * 32 + srow) * KP + sk]) = ra[p];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) *reinterpret_cast<f32x4*>(&Bs[(p * 32 + srow) * KP + sk]) = rb[p];
+            rank_store_tiles(ra, rb, As, Bs, srow, sk);
         };
-        auto compute = [&](const float* As, const float* Bs) {
-#pragma unroll
-            for (int gk = 0; gk < BK / 8; ++gk) {
-                float a[2][4], b[2][4];
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(&As[(wm * 64 + tm * 32 + l31) * KP + gk * 8 + lh * 4]);
-                    a[tm][0] = v.x; a[tm][1] = v.y; a[tm][2] = v.z; a[tm][3] = v.w;
-                }
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(&Bs[(wn * 64 + tn * 32 + l31) * KP + gk * 8 + lh * 4]);
-                    b[tn][0] = v.x; b[tn][1] = v.y; b[tn][2] = v.z; b[tn][3] = v.w;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < 2; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm][i], b[tn][i], acc[tm][tn], 0, 0, 0);
-            }
-        };
+        auto compute = [&](const float* As, const float* Bs) { rank_compute(As, Bs, wm, wn, l31, lh, acc); };
 
         // the software pipeline of gs_gemm.hip: the global loads of stage s + 2 are in flight while stage s is consumed
         load_tiles(0, ra0, rb0);
@@ -327,15 +246,6 @@ __global__ __launch_bounds__(256) void rank_sum_kernel(const int32_t* __restrict
     }
     n_gt[q] = gt;
     n_eq[q] = eq;
-}
-
-// (tiles per slice, slices) for Q queries against n_cand candidates: the rule of the header comment
-static void rank_plan(const int64_t Q, const int64_t n_cand, int64_t* tiles_n, int64_t* tps, int64_t* slices) {
-    *tiles_n = gs_ceil_div(n_cand, RK_BN);
-    const int64_t q_tiles = std::max<int64_t>(1, gs_ceil_div(Q, RK_BM));
-    const int64_t want = std::max<int64_t>(1, gs_ceil_div(RK_WG_TARGET, q_tiles));
-    *tps = std::min<int64_t>(RK_MAX_TILES, std::max<int64_t>(RK_MIN_TILES, gs_ceil_div(*tiles_n, want)));
-    *slices = std::max<int64_t>(1, gs_ceil_div(*tiles_n, *tps));
 }
 
 extern "C" int gs_rank_ws_bytes(int64_t Q, int64_t n_cand, int64_t* bytes_out_host) {

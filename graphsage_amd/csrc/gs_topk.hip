@@ -1,0 +1,382 @@
+// Top-k partners against every node: the sweep of gs_rank.hip with a select epilogue where that kernel counts (no score row is
+// ever written to memory).
+//
+//   C_q     = {0 <= w < n_cand} \ {src[q]} \ filter row of src[q]        (src kept under GS_RANK_KEEP_SRC; there is no dst)
+//   s(q, w) = <Xq[q], Zc[w]>
+//   out     = the k members of C_q that come first in the total order (s descending, w ascending)
+//
+// The sweep is gs_rank_dev.h, shared with rank_count_kernel: fp32 MFMA (v_mfma_f32_32x32x2_f32), BM = BN = 128, BK = 32, two
+// LDS stages, the slice plan, one 128-bit exclusion word per query row written before a tile's K loop from the sorted filter
+// row with a forward-only cursor.  Same helpers, same k-ordered chain: s(q, w) here is bit-equal to the t that gs_rank_count
+// returns for dst[q] = w.
+//
+// Order: a key is one uint64 -- high half the score's bits mapped monotonically to unsigned (-0.0f first made +0.0f), low half
+// ~w.  Keys are distinct, a larger key comes first, one unsigned compare is the whole order, and the k largest keys of a set do
+// not depend on the order in which they were met.  Key 0 is no candidate ("nothing": ~w >= 2^31 for every real w).  A NaN
+// score is just some key: it lands somewhere, nothing is indexed by it.
+//
+// Epilogue, per candidate tile.  After the K loop the two stage buffers (73,728 B) are dead until the next tile's first
+// store: the 128 x 128 accumulator tile is dumped into them as [128][129] floats (66,048 B; lane = column on the way in and on
+// the way out, the pad of 1 keeps both free of bank conflicts).  Then the next tile's first two K stages are requested from
+// global memory, and under those loads every wave takes 32 of the 128 query rows, ONE ROW AT A TIME WITH ALL 64 LANES (two
+// columns per lane; the scores of TK_ROWS = 8 rows are read from LDS together, one latency for the batch), rather than one row
+// per thread: a wave-wide ballot of `key > tau` says at once whether the row has anything to keep (after warm-up: usually
+// not), and what passes is appended to the row's list in the workspace at ballot-prefix positions -- fire-and-forget stores.
+// With one row per thread the 64 rows of a wave would run in lockstep and every insertion of any of them (k (1 + ln(n_slice /
+// k)) per row: about 740 at k = 100 in a 58 k slice) would stall all 64 behind a chain of dependent global loads.
+//   Per row the slice keeps a list of cap = 64 (1 + ceil(k / 64)) keys (128 or 192) in the workspace, its length and its
+// threshold tau (LDS; wave-uniform).  tau is the k-th largest key at the last compaction (0 before the first), so everything
+// the list holds beyond the true top k is merely superfluous.  When an append would overflow, the wave compacts the row: all
+// keys into registers (three per lane), the k-th largest found by a 64-step radix select on ballots, the k survivors written
+// back in place, tau raised.  A list with room for m = cap - k >= 64 new keys multiplies the candidates seen between two
+// compactions by e^(m / k): a handful of compactions per row and slice.  The lists are unsorted; only their owning wave
+// touches them inside the launch (stores and loads of one workgroup: a workgroup-scope fence before the compaction's loads).
+//   Three barriers per tile where the count kernel has one: stages dead -> dump -> rows -> next tile's first store.
+//
+// topk_merge_kernel: one wave per query pushes the `slices` lists through the same append / compact code on a list in LDS,
+// compacts to k, ranks the survivors by counting (keys are distinct: ranks are a permutation) and writes ids int32 [Q, k],
+// scores float [Q, k] and count int32 [Q] = min(k, |C_q|); entries at and beyond count are -1 / -inf.
+//
+// Integers and compares only after the MFMA chain: bitwise reproducible.  No atomics, no workgroup waits on another, plain
+// launches on the caller's stream.
+//
+// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; quoted in profiles/topk_full.md):
+// topk_select_kernel 206 vector registers, 102 scalar, no scratch, no spill of either kind, 77,824 B of LDS: two workgroups per
+// CU under __launch_bounds__(256, 2), as the count kernel (229 registers; unchanged by the shared header).  topk_merge_kernel 30
+// registers, 6,144 B of LDS.  The report depends on the K loop having ONE exit (the odd last stage is an `if`, not the count
+// kernel's `break`: with two exits the accumulators, which here outlive the loop into the dump, were kept in two register
+// sets and 49 to 70 registers spilled).  The order of the arithmetic is the same either way.
+#include "gs_rank_dev.h"
+
+static_assert(sizeof(gs_topk_desc) == 144, "gs_topk_desc layout (mirrored by graphsage_amd/_lib.py)");
+static_assert(GS_TOPK_MAX == 128, "the merge kernel ranks two keys per lane");
+
+#define TK_LD 129                // row stride of the dumped accumulator tile, in floats
+#define TK_E 3                   // keys per lane when a list is compacted: cap <= 192
+#define TK_ROWS 8                // query rows whose scores a wave reads from LDS together
+static_assert(RK_BM * TK_LD <= 2 * RK_STAGE_FLOATS, "the dumped tile lives in the two stage buffers");
+static_assert(64 * TK_E >= GS_TOPK_MAX + 64, "a compacted list takes 64 more keys");
+
+struct TopkArgs {
+    const float* Xq; const float* Zc;
+    const int32_t* src;
+    const int64_t* f_rowptr; const int32_t* f_col;
+    uint64_t* lists; int32_t* counts;        // workspace: [slices][Q][cap] keys, then [slices][Q] list lengths
+    int64_t Q, ldq, n_rows, n_cand, ldz, f_nnz;
+    int32_t d, k, cap, tiles_n, tiles_per_slice, q_tiles;
+    int32_t keep_src;            // GS_RANK_KEEP_SRC: src only indexes the filter
+};
+
+__device__ __forceinline__ uint64_t topk_key(const float s, const uint32_t w) {
+    uint32_t b = s == 0.f ? 0u : __float_as_uint(s);
+    b ^= (b >> 31) ? 0xffffffffu : 0x80000000u;
+    return ((uint64_t)b << 32) | (uint64_t)(uint32_t)~w;
+}
+__device__ __forceinline__ float topk_score(const uint64_t key) {
+    uint32_t b = (uint32_t)(key >> 32);
+    b ^= (b >> 31) ? 0x80000000u : 0xffffffffu;
+    return __uint_as_float(b);
+}
+__device__ __forceinline__ int topk_uniform(const int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t topk_uniform(const uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
+// One wave: keep the k largest of list[0 .. cnt) (distinct keys, k <= cnt <= 64 TK_E) in place and return the k-th largest.
+__device__ __forceinline__ uint64_t topk_compact(uint64_t* list, const int cnt, const int k, const int lane) {
+    uint64_t key[TK_E];
+#pragma unroll
+    for (int e = 0; e < TK_E; ++e) key[e] = e * 64 + lane < cnt ? list[e * 64 + lane] : 0ull;
+    uint64_t kth = 0ull;         // radix select from the top bit down: wave-uniform all along
+    int rem = k;
+#pragma unroll 1
+    for (int bit = 63; bit >= 0; --bit) {
+        const uint64_t want = kth | (1ull << bit);
+        const uint64_t mask = ~((1ull << bit) - 1ull);
+        int c = 0;
+#pragma unroll
+        for (int e = 0; e < TK_E; ++e) c += __popcll(__ballot((key[e] & mask) == want));
+        if (c >= rem) kth = want; else rem -= c;
+    }
+    const uint64_t below = (1ull << lane) - 1ull;
+    int pos = 0;
+#pragma unroll
+    for (int e = 0; e < TK_E; ++e) {
+        const bool keep = key[e] >= kth && key[e] != 0ull;
+        const uint64_t b = __ballot(keep);
+        if (keep) list[pos + __popcll(b & below)] = key[e];
+        pos += __popcll(b);
+    }
+    return kth;
+}
+
+// One wave appends the keys of its lanes that beat tau (key 0: nothing to offer) to a list of capacity cap >= k + 64.
+__device__ __forceinline__ void topk_push(uint64_t* list, const int cap, const int k, int& cnt, uint64_t& tau, const uint64_t key,
+                                          const int lane) {
+    uint64_t b = __ballot(key > tau);
+    if (b == 0ull) return;
+    if (cnt + __popcll(b) > cap) {           // cnt > cap - 64 >= k: there is something to drop
+        __threadfence_block();               // the appends of this wave's other lanes
+        tau = topk_compact(list, cnt, k, lane);
+        cnt = k;
+        b = __ballot(key > tau);
+    }
+    if (key > tau) list[cnt + __popcll(b & ((1ull << lane) - 1ull))] = key;
+    cnt += __popcll(b);
+}
+
+// (256, 2): a budget of 256 registers per lane, two workgroups per CU
+__global__ __launch_bounds__(256, 2) void topk_select_kernel(const TopkArgs g) {
+    constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
+    __shared__ __attribute__((aligned(16))) float smem[2 * RK_STAGE_FLOATS];
+    __shared__ __attribute__((aligned(16))) uint32_t excl[BM][4];      // bit c of row r: (query r, column c of the tile) is not a candidate
+    __shared__ uint64_t tauS[BM];
+    __shared__ int32_t cntS[BM], sq[BM];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = topk_uniform(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int l31 = lane & 31, lh = lane >> 5;
+
+    const int q_tile = (int)(blockIdx.x % (unsigned)g.q_tiles);
+    const int slice = (int)(blockIdx.x / (unsigned)g.q_tiles);
+    const int64_t m0 = (int64_t)q_tile * BM;
+    const int tile0 = slice * g.tiles_per_slice;
+    const int tile1 = min(tile0 + g.tiles_per_slice, g.tiles_n);
+    const int d = g.d;
+
+    // ---- per-query state: own row, cursor into the filter row (threads 0 .. BM-1 own one query each), an empty list
+    int64_t cur = 0, cend = 0;
+    if (tid < BM) {
+        const int64_t q = m0 + tid;
+        int32_t ss = -1;
+        if (q < g.Q && g.src) {
+            ss = g.src[q];
+            ss = ss < 0 ? 0 : ((int64_t)ss >= g.n_rows ? (int32_t)(g.n_rows - 1) : ss);      // the caller checked; never a stray read
+            if (g.f_rowptr) rank_filter_cursor(g.f_rowptr, g.f_col, g.f_nnz, ss, (int64_t)tile0 * BN, cur, cend);
+        }
+        sq[tid] = g.keep_src ? -1 : ss;          // the cursor above is all that a kept src is needed for
+        cntS[tid] = 0;
+        tauS[tid] = 0ull;
+    }
+    __syncthreads();
+
+    // ---- operand rows of this thread: 4 query rows (fixed), 4 candidate rows (per tile); 8 threads x float4 span BK
+    const int srow = tid >> 3, sk = (tid & 7) * 4;
+    const float* a_row[4];
+    bool a_ok[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int64_t r = m0 + p * 32 + srow;
+        a_ok[p] = r < g.Q;
+        a_row[p] = g.Xq + (a_ok[p] ? r : 0) * g.ldq + sk;
+    }
+    const float* b_row[4];
+    bool b_ok[4];
+    auto candidate_rows = [&](const int tile) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const int64_t r = (int64_t)tile * BN + p * 32 + srow;
+            b_ok[p] = r < g.n_cand;
+            b_row[p] = g.Zc + (b_ok[p] ? r : 0) * g.ldz + sk;
+        }
+    };
+
+    float* As0 = smem;
+    float* Bs0 = smem + BM * KP;
+    float* As1 = smem + RK_STAGE_FLOATS;
+    float* Bs1 = smem + RK_STAGE_FLOATS + BM * KP;
+
+    // the software pipeline of gs_gemm.hip, with a tile's first two stages requested before the previous tile's rows are scanned
+    f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
+    auto first_loads = [&](const int tile) {
+        candidate_rows(tile);
+        rank_load_tiles(0, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
+        if (BK < d) rank_load_tiles(BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
+    };
+    if (tile0 < tile1) first_loads(tile0);
+
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int64_t n0 = (int64_t)tile * BN;
+        if (tid < BM)
+            *reinterpret_cast<uint4*>(&excl[tid][0]) = rank_excl_words(n0, g.n_cand, -1, sq[tid], g.f_col, cur, cend);
+
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+        for (int k0 = 0; k0 < d; k0 += 2 * BK) {
+            rank_store_tiles(ra0, rb0, As0, Bs0, srow, sk);
+            __syncthreads();
+            if (k0 + 2 * BK < d) rank_load_tiles(k0 + 2 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
+            rank_compute(As0, Bs0, wm, wn, l31, lh, acc);
+            if (k0 + BK < d) {
+                rank_store_tiles(ra1, rb1, As1, Bs1, srow, sk);
+                __syncthreads();
+                if (k0 + 3 * BK < d) rank_load_tiles(k0 + 3 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
+                rank_compute(As1, Bs1, wm, wn, l31, lh, acc);
+            }
+        }
+
+        // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+        __syncthreads();                         // every wave is done with the stage buffers
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    smem[(wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * TK_LD + wn * 64 + tn * 32 + l31] = acc[tm][tn][e];
+        __syncthreads();
+        if (tile + 1 < tile1) first_loads(tile + 1);
+
+#pragma unroll 1
+        for (int r0 = wave * (BM / 4); r0 < (wave + 1) * (BM / 4); r0 += TK_ROWS) {      // this wave's 32 query rows, 64 lanes on one row
+            uint64_t key[TK_ROWS][2], tau_r[TK_ROWS];        // a batch of rows is read from LDS at once: one latency, not TK_ROWS
+#pragma unroll
+            for (int i = 0; i < TK_ROWS; ++i) {
+                const int r = r0 + i;
+                tau_r[i] = tauS[r];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float s = smem[r * TK_LD + h * 64 + lane];
+                    const uint32_t word = excl[r][h * 2 + lh];
+                    key[i][h] = ((word >> l31) & 1u) ? 0ull : topk_key(s, (uint32_t)(n0 + h * 64 + lane));
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TK_ROWS; ++i) {
+                const int r = r0 + i;
+                const int64_t q = m0 + r;
+                uint64_t tau = topk_uniform(tau_r[i]);
+                if (q >= g.Q || __ballot(key[i][0] > tau || key[i][1] > tau) == 0ull) continue;      // after warm-up: the usual case
+                int cnt = topk_uniform(cntS[r]);
+                uint64_t* list = g.lists + ((int64_t)slice * g.Q + q) * g.cap;
+                topk_push(list, g.cap, g.k, cnt, tau, key[i][0], lane);
+                topk_push(list, g.cap, g.k, cnt, tau, key[i][1], lane);
+                if (lane == 0) {
+                    cntS[r] = cnt;
+                    tauS[r] = tau;
+                }
+            }
+        }
+        // the stage buffers and the exclusion words change hands here
+        __syncthreads();
+    }
+
+    if (tid < BM && m0 + tid < g.Q) g.counts[(int64_t)slice * g.Q + m0 + tid] = cntS[tid];
+}
+
+// one wave per query: the slices' lists -> the k first keys, in order
+__global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restrict__ lists, const int32_t* __restrict__ counts,
+                                                         const int64_t Q, const int slices, const int cap, const int k,
+                                                         int32_t* __restrict__ ids, float* __restrict__ scores,
+                                                         int32_t* __restrict__ count) {
+    __shared__ uint64_t listS[4][64 * TK_E];
+    const int lane = threadIdx.x & 63, wave = topk_uniform((int)(threadIdx.x >> 6));
+    const int64_t q = (int64_t)blockIdx.x * 4 + wave;
+    if (q >= Q) return;                          // (no barrier below: a wave only reads what it wrote)
+    uint64_t* list = listS[wave];
+    int cnt = 0;
+    uint64_t tau = 0ull;
+    for (int s = 0; s < slices; ++s) {
+        const int n = min(max(topk_uniform(counts[(int64_t)s * Q + q]), 0), cap);
+        const uint64_t* in = lists + ((int64_t)s * Q + q) * cap;
+        for (int c0 = 0; c0 < n; c0 += 64)
+            topk_push(list, 64 * TK_E, k, cnt, tau, c0 + lane < n ? in[c0 + lane] : 0ull, lane);
+    }
+    __threadfence_block();
+    if (cnt > k) {
+        topk_compact(list, cnt, k, lane);
+        cnt = k;
+        __threadfence_block();
+    }
+    // rank by counting: at most 128 distinct keys, two per lane
+    const uint64_t key0 = lane < cnt ? list[lane] : 0ull;
+    const uint64_t key1 = lane + 64 < cnt ? list[lane + 64] : 0ull;
+    int r0 = 0, r1 = 0;
+    for (int j = 0; j < cnt; ++j) {
+        const uint64_t kj = list[j];
+        r0 += kj > key0 ? 1 : 0;
+        r1 += kj > key1 ? 1 : 0;
+    }
+    int32_t* ids_q = ids + q * k;
+    float* scores_q = scores + q * k;
+    if (lane < cnt) {
+        ids_q[r0] = (int32_t)~(uint32_t)key0;
+        scores_q[r0] = topk_score(key0);
+    }
+    if (lane + 64 < cnt) {
+        ids_q[r1] = (int32_t)~(uint32_t)key1;
+        scores_q[r1] = topk_score(key1);
+    }
+    for (int p = lane; p < k; p += 64)
+        if (p >= cnt) {
+            ids_q[p] = -1;
+            scores_q[p] = -INFINITY;
+        }
+    if (lane == 0) count[q] = cnt;
+}
+
+static int64_t topk_cap(const int k) { return 64 * (1 + gs_ceil_div(k, 64)); }
+
+extern "C" int gs_topk_ws_bytes(int64_t Q, int64_t n_cand, int32_t k, int64_t* bytes_out_host) {
+    GS_REQUIRE(bytes_out_host && Q >= 0 && n_cand >= 0 && n_cand <= 0x7fffffffll, "gs_topk_ws_bytes: bad args");
+    GS_REQUIRE(k >= 1 && k <= GS_TOPK_MAX, "gs_topk_ws_bytes: k=%d must lie in [1, %d]", k, GS_TOPK_MAX);
+    int64_t tiles_n, tps, slices;
+    rank_plan(Q, n_cand, &tiles_n, &tps, &slices);
+    *bytes_out_host = slices * Q * (topk_cap(k) * (int64_t)sizeof(uint64_t) + (int64_t)sizeof(int32_t));
+    return GS_OK;
+}
+
+extern "C" int gs_topk_select(const gs_topk_desc* desc_host, void* stream) {
+    GS_REQUIRE(desc_host, "gs_topk_select: null descriptor");
+    const gs_topk_desc& q = *desc_host;
+    GS_REQUIRE(q.Q >= 0 && q.n_rows >= 0 && q.n_rows <= 0x7fffffffll && q.n_cand >= 0,
+               "gs_topk_select: bad sizes Q=%lld n_rows=%lld n_cand=%lld", (long long)q.Q, (long long)q.n_rows, (long long)q.n_cand);
+    GS_REQUIRE(q.n_cand <= q.n_rows, "gs_topk_select: n_cand=%lld exceeds the table's n_rows=%lld", (long long)q.n_cand,
+               (long long)q.n_rows);
+    GS_REQUIRE(q.d >= 4 && q.d <= 1024 && (q.d & 3) == 0, "gs_topk_select: d=%d must be a multiple of 4 in [4, 1024]", q.d);
+    GS_REQUIRE(q.k >= 1 && q.k <= GS_TOPK_MAX, "gs_topk_select: k=%d must lie in [1, %d]", q.k, GS_TOPK_MAX);
+    if (q.Q == 0) return GS_OK;
+    GS_CHECK_MAT(q.Xq, q.ldq, "gs_topk_select Xq");
+    GS_CHECK_MAT(q.Zc, q.ldz, "gs_topk_select Zc");
+    GS_REQUIRE(q.ldq >= q.d && q.ldz >= q.d, "gs_topk_select: ld must be >= d");
+    GS_REQUIRE(q.ids && q.scores && q.count, "gs_topk_select: ids, scores and count must be non-null");
+    GS_REQUIRE((q.f_rowptr == nullptr) == (q.f_col == nullptr), "gs_topk_select: f_rowptr and f_col go together");
+    GS_REQUIRE(!q.f_rowptr || q.src, "gs_topk_select: a filter is indexed by src, which is null");
+    GS_REQUIRE(!q.src || q.n_rows >= 1, "gs_topk_select: the candidate table is empty (src needs a row)");
+    GS_REQUIRE(q.f_nnz >= 0, "gs_topk_select: f_nnz=%lld", (long long)q.f_nnz);
+    GS_REQUIRE((q.flags & ~GS_RANK_KEEP_SRC) == 0, "gs_topk_select: unknown flags 0x%x", (unsigned)q.flags);
+    int64_t tiles_n, tps, slices;
+    rank_plan(q.Q, q.n_cand, &tiles_n, &tps, &slices);
+    const int64_t cap = topk_cap(q.k);
+    const int64_t need = slices * q.Q * (cap * (int64_t)sizeof(uint64_t) + (int64_t)sizeof(int32_t));
+    GS_REQUIRE(q.ws && (reinterpret_cast<uintptr_t>(q.ws) & 7u) == 0 && q.ws_bytes >= need,
+               "gs_topk_select: needs an 8-byte aligned workspace of %lld bytes (gs_topk_ws_bytes), got %lld", (long long)need,
+               (long long)q.ws_bytes);
+    const int64_t q_tiles = gs_ceil_div(q.Q, RK_BM);
+    const int64_t blocks = q_tiles * slices;
+    GS_REQUIRE(blocks < (1ll << 31) && gs_ceil_div(q.Q, 4) < (1ll << 31),
+               "gs_topk_select: grid too large (%lld blocks); call it on chunks of the queries", (long long)blocks);
+    TopkArgs g;
+    g.Xq = q.Xq; g.Zc = q.Zc; g.src = q.src; g.f_rowptr = q.f_rowptr; g.f_col = q.f_col;
+    g.lists = reinterpret_cast<uint64_t*>(q.ws);
+    g.counts = reinterpret_cast<int32_t*>(g.lists + slices * q.Q * cap);
+    g.Q = q.Q; g.ldq = q.ldq; g.n_rows = q.n_rows; g.n_cand = q.n_cand; g.ldz = q.ldz; g.f_nnz = q.f_nnz;
+    g.d = q.d; g.k = q.k; g.cap = (int32_t)cap;
+    g.tiles_n = (int32_t)tiles_n; g.tiles_per_slice = (int32_t)tps; g.q_tiles = (int32_t)q_tiles;
+    g.keep_src = (q.flags & GS_RANK_KEEP_SRC) ? 1 : 0;
+    const hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(topk_select_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
+    GS_LAUNCH_CHECK("topk_select_kernel");
+    hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)gs_ceil_div(q.Q, 4)), dim3(256), 0, st, g.lists, g.counts, q.Q, (int)slices,
+                       (int)cap, q.k, q.ids, q.scores, q.count);
+    GS_LAUNCH_CHECK("topk_merge_kernel");
+    return GS_OK;
+}

@@ -28,6 +28,14 @@ Link ranking.  What the exact embeddings are for: where does the true partner of
 
 One fused launch scores every (query, candidate) pair on the matrix cores and counts the candidates above / level with the
 true partner in its epilogue (gs_rank_count, csrc/gs_rank.hip): no score matrix exists.  rank = 1 + n_gt + n_eq: a tie loses.
+
+Retrieval.  The answer itself: which k nodes should u be linked to?
+
+    res = model.topk_full(graph, nodes, k=10)                   # ids [n, k], scores [n, k], count [n]
+    res = topk_full(engine, Z, nodes, 10, n_cand=N, filt=RankFilter.from_full_graph(graph))
+
+The same sweep with a select epilogue (gs_topk_select, csrc/gs_topk.hip): order (score descending, id ascending), the scores
+bit-equal to those rank_full reports for the same pair.
 """
 import numpy as np
 
@@ -390,3 +398,49 @@ def rank_full(engine, Z, edges, *, n_cand=None, filt=None, exclude_self=True, we
     res = rank_metrics(out[1].cpu().numpy(), out[2].cpu().numpy(), hits)
     res["scores"] = out[0].cpu().numpy()
     return res
+
+
+# ---------------------------------------------------------------------------------------------------- retrieval
+def topk_full(engine, Z, nodes, k, *, n_cand=None, filt=None, exclude_self=True, weights=None):
+    """The k best-scoring partners of every node in `nodes` among the rows 0 .. n_cand - 1 of the device table Z ([n_rows, d]
+    Mat): the score of a candidate w for the query node u is <Z[u], Z[w]>, or <Z[u] . A, Z[w]> with the bilinear weights A (as
+    rank_full).  u itself (exclude_self) and the filter row of u (filt: RankFilter; independent of exclude_self: with
+    exclude_self=False the query node only names its filter row and stays a candidate) are no candidates.  Returns
+    {"ids": int32 [n, k], "scores": float32 [n, k], "count": int32 [n]} as NumPy arrays, every row in the order (score
+    descending, id ascending); entries at and beyond count = min(k, candidates) are -1 / -inf.  One fused score-and-select
+    launch per 65,536 queries (gs_topk_select); no score matrix exists."""
+    import torch
+    nodes = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int64)
+    Q, k = nodes.shape[0], int(k)
+    n_cand = Z.rows if n_cand is None else int(n_cand)
+    if not 1 <= k <= ops.TOPK_MAX:
+        raise GraphsageAmdError("topk_full: k = %d must lie in [1, %d]" % (k, ops.TOPK_MAX))
+    if not 0 <= n_cand <= Z.rows:
+        raise GraphsageAmdError("topk_full: n_cand = %d, the table has %d rows" % (n_cand, Z.rows))
+    if Q and (nodes.min() < 0 or nodes.max() >= Z.rows):
+        raise GraphsageAmdError("topk_full: node ids must lie in [0, %d)" % Z.rows)
+    if Q == 0:
+        return {"ids": np.zeros((0, k), np.int32), "scores": np.zeros((0, k), np.float32), "count": np.zeros(0, np.int32)}
+    e = engine
+    src = torch.from_numpy(nodes.astype(np.int32)).to(e.device)
+    f_rowptr = f_col = None
+    if filt is not None:
+        f_rowptr, f_col = filt.on(e.device, Z.rows)
+    Xq = _table(e, Q, Z.d)
+    out = (torch.zeros((Q, k), dtype=torch.int32, device=e.device), torch.zeros((Q, k), dtype=torch.float32, device=e.device),
+           torch.zeros(Q, dtype=torch.int32, device=e.device))
+    need = max(ops.topk_ws_bytes(n, n_cand, k) for n in {min(Q, ops.RANK_CHUNK), Q % ops.RANK_CHUNK})
+    ws = torch.zeros(max(1, (need + 7) // 8), dtype=torch.int64, device=e.device)
+    torch.cuda.synchronize()              # uploads and zero-fills ran on torch's stream; order them before the engine's
+    ops.gather_rows(Z, src, out=Xq, stream=e.stream)
+    if weights is not None:
+        if weights.rows != Z.d or weights.d != Z.d:
+            raise GraphsageAmdError("topk_full: bilinear weights must be [%d, %d]" % (Z.d, Z.d))
+        U = _table(e, Q, Z.d)
+        ops.gemm(False, False, Q, Z.d, Z.d, Xq, weights, U, stream=e.stream)
+        Xq = U
+    ops.topk_select(Xq, Z, k, n_cand=n_cand, src=src if (exclude_self or filt is not None) else None,
+                    keep_src=not exclude_self, f_rowptr=f_rowptr, f_col=f_col, ids=out[0], scores=out[1], count=out[2], ws=ws,
+                    stream=e.stream)
+    e.sync()
+    return {"ids": out[0].cpu().numpy(), "scores": out[1].cpu().numpy(), "count": out[2].cpu().numpy()}

@@ -1013,6 +1013,22 @@ class SampleAndAggregate(object):
         W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
         return inf.rank_full(e, Z, edges, n_cand=graph.n_nodes, filt=filt, weights=W, hits=hits)
 
+    def topk_full(self, graph, nodes=None, k=10, filtered=True):
+        """The k best-scoring partners of `nodes` (default: all N real nodes in id order) among ALL N nodes with the exact
+        embeddings of `graph` (the table of embed_full, kept on the device): inference.topk_full with n_cand = N (the pad row is
+        never a candidate), the query node left out, the edges of `graph` filtered (filtered=True) and the head's bilinear weights
+        if it has them.  Returns {"ids": int32 [n, k], "scores": float32 [n, k], "count": int32 [n]}."""
+        from . import inference as inf
+        e = self.engine
+        H = inf.layers_full(self, graph)
+        Z = inf._table(e, H.rows, H.d)
+        ops.l2norm_fwd(H, H.rows, Z, None, stream=e.stream)
+        filt = graph.rank_filter() if filtered else None
+        W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
+        if nodes is None:
+            nodes = np.arange(graph.n_nodes)
+        return inf.topk_full(e, Z, nodes, k, n_cand=graph.n_nodes, filt=filt, weights=W)
+
     # ------------------------------------------------------------------------------ step machinery (shared)
     def _samplers(self):
         seen = []

@@ -307,6 +307,61 @@ def rank_count(Xq, Zc, dst, n_cand=None, src=None, f_rowptr=None, f_col=None, t=
     return t, n_gt, n_eq
 
 
+# ------------------------------------------------------------------------------------------ TOPK
+TOPK_MAX = _lib.TOPK_MAX  # largest k of gs_topk_select
+
+
+def topk_ws_bytes(Q, n_cand, k):
+    """Bytes of the workspace gs_topk_select needs for Q queries against n_cand candidates at this k."""
+    out = ctypes.c_int64(0)
+    call("gs_topk_ws_bytes", Q, n_cand, k, ctypes.byref(out))
+    return out.value
+
+
+def topk_select(Xq, Zc, k, n_cand=None, src=None, f_rowptr=None, f_col=None, keep_src=False, ids=None, scores=None, count=None,
+                ws=None, stream=None):
+    """gs_topk_select: for every row q of Xq the k candidates w < n_cand (src[q] and the filter row of src[q] left out) that come
+    first by (<Xq[q], Zc[w]> descending, w ascending).  Xq, Zc: Mats of the same width; src: int32 device vector [Xq.rows] with
+    entries in [0, Zc.rows) (checked by the caller); f_rowptr int64 [Zc.rows + 1], f_col int32 (a filter needs src).
+    keep_src: src[q] stays a candidate and only names the filter row (GS_RANK_KEEP_SRC).  Returns (ids int32 [Q, k], scores
+    float32 [Q, k], count int32 [Q]); entries at and beyond count[q] = min(k, candidates of q) are -1 / -inf."""
+    Q, k = Xq.rows, int(k)
+    n_cand = Zc.rows if n_cand is None else int(n_cand)
+    if Xq.d != Zc.d:
+        raise _lib.GraphsageAmdError("topk_select: Xq is [%d, %d], Zc [%d, %d]" % (Xq.rows, Xq.d, Zc.rows, Zc.d))
+    if not 1 <= k <= TOPK_MAX:
+        raise _lib.GraphsageAmdError("topk_select: k=%d must lie in [1, %d]" % (k, TOPK_MAX))
+    if src is not None and (src.dtype != torch.int32 or src.numel() != Q):
+        raise _lib.GraphsageAmdError("topk_select: src must be an int32 vector with one entry per query")
+    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
+            f_rowptr.dtype != torch.int64 or f_col.dtype != torch.int32 or f_rowptr.numel() != Zc.rows + 1)):
+        raise _lib.GraphsageAmdError("topk_select: the filter is an int64 rowptr [n_rows + 1] with an int32 col")
+    dev = Xq.buf.device
+    ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if ids is None else ids
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev) if scores is None else scores
+    count = torch.empty(Q, dtype=torch.int32, device=dev) if count is None else count
+    if tuple(ids.shape) != (Q, k) or tuple(scores.shape) != (Q, k) or count.numel() != Q or not (
+            ids.is_contiguous() and scores.is_contiguous() and count.is_contiguous()) or (
+            ids.dtype, scores.dtype, count.dtype) != (torch.int32, torch.float32, torch.int32):
+        raise _lib.GraphsageAmdError("topk_select: ids int32 [Q, k], scores float32 [Q, k] and count int32 [Q] must be dense")
+    need = max(topk_ws_bytes(n, n_cand, k) for n in {min(Q, RANK_CHUNK), Q % RANK_CHUNK})     # the two chunk sizes that occur
+    if ws is None:
+        ws = torch.empty(max((need + 7) // 8, 1), dtype=torch.int64, device=dev)
+    q = _lib.TopkDesc()
+    q.Zc, q.f_rowptr, q.f_col, q.ws = Zc.ptr, ptr(f_rowptr), ptr(f_col), ptr(ws)
+    q.n_rows, q.n_cand, q.ldz, q.ldq = Zc.rows, n_cand, Zc.ld, Xq.ld
+    q.f_nnz, q.ws_bytes = (f_col.numel() if f_col is not None else 0), ws.element_size() * ws.numel()
+    q.d, q.k, q.flags = Xq.d, k, (_lib.RANK_KEEP_SRC if keep_src else 0)
+    for q0 in range(0, max(Q, 1), RANK_CHUNK):
+        n = min(RANK_CHUNK, Q - q0)
+        q.Q = n
+        q.Xq = Xq.ptr + 4 * q0 * Xq.ld
+        q.src = ptr(src[q0:q0 + n]) if src is not None else None
+        q.ids, q.scores, q.count = ptr(ids[q0:q0 + n]), ptr(scores[q0:q0 + n]), ptr(count[q0:q0 + n])
+        call("gs_topk_select", ctypes.addressof(q), _s(stream))
+    return ids, scores, count
+
+
 # ------------------------------------------------------------------------------------------ K3
 def sage_dense_fwd(self_m, self_idx, agg, agg_idx, n, W_self, W_neigh, out_dim, concat, act, bias, out,
                    stream=None):

@@ -72,9 +72,9 @@ FLAGS = None
 
 
 def refuse_full_inference(flags):
-    """--full_inference (and --rank_full, which ranks the embed_full embeddings) has no meaning for the models without a
-    full-neighborhood form: say so before any work is done."""
-    for flag in ("full_inference", "rank_full"):
+    """--full_inference (and --rank_full / --topk_full, which rank the embed_full embeddings) has no meaning for the models
+    without a full-neighborhood form: say so before any work is done."""
+    for flag in ("full_inference", "rank_full", "topk_full"):
         if getattr(flags, flag, False) and flags.model in ('n2v', 'graphsage_seq'):
             raise SystemExit("--%s is not available with --model %s: %s" % (
                 flag, flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v'

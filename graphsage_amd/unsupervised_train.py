@@ -67,6 +67,10 @@ def build_flags(argv=None):
     p.add_argument('--rank_full', type=b, nargs='?', const=True, default=False,
                    help='after val.npy: rank every held-out edge (both directions) against ALL nodes with the exact embeddings '
                         'on the test graph, known edges filtered (rank_full) -> rank_full.txt; not for n2v / graphsage_seq')
+    p.add_argument('--topk_full', type=int, default=0,
+                   help='K > 0: after val.npy, the K best-scoring partners of every node among ALL nodes with the exact '
+                        'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
+                        'topk_full_scores.npy; not for n2v / graphsage_seq')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     return p.parse_args(argv)
 
@@ -172,6 +176,27 @@ def save_full_ranking(model, minibatch, out_dir):
         os.makedirs(out_dir)
     with open(out_dir + "rank_full.txt", "w") as fp:
         fp.write(line + "\n")
+    return res
+
+
+def topk_full_line(res):
+    """The line --topk_full prints."""
+    ids = res["ids"]
+    return "Full-graph top-K partners: k= %d nodes= %d filled= %.5f" % (
+        ids.shape[1], ids.shape[0], float(np.mean(ids >= 0)) if ids.size else 0.0)
+
+
+def save_full_topk(model, minibatch, out_dir, k):
+    """topk_full.npy (int32 [N, K]) / topk_full_scores.npy (float32 [N, K]): for every node in id order its K best-scoring
+    partners among all N nodes with the exact embeddings of the test graph, best first (-1 / -inf where a node has fewer
+    candidates); the node itself and every edge of the test graph are filtered out of the candidates."""
+    from .supervised_train import full_graph
+    res = model.topk_full(full_graph(minibatch, minibatch.G.n_nodes), k=k)
+    print(topk_full_line(res))
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    np.save(out_dir + "topk_full.npy", res["ids"])
+    np.save(out_dir + "topk_full_scores.npy", res["scores"])
     return res
 
 
@@ -283,6 +308,8 @@ def train(G, context_pairs):
             save_full_embeddings(model, minibatch, log_dir())
         if FLAGS.rank_full:
             save_full_ranking(model, minibatch, log_dir())
+        if FLAGS.topk_full:
+            save_full_topk(model, minibatch, log_dir(), FLAGS.topk_full)
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
     return shadow_mrr

@@ -1075,6 +1075,41 @@ int gs_rank_ws_bytes(int64_t Q, int64_t n_cand, int64_t* bytes_out_host);
 int gs_rank_count(const gs_rank_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * TOPK the k best-scoring partners of every query among all nodes: the sweep of gs_rank_count with a select epilogue; no score
+ *      row is written to memory.
+ *        C_q     = {0 <= w < n_cand} without src[q] (if src is given and flags lacks GS_RANK_KEEP_SRC) and without the filter
+ *                  row of src[q] (filter and src as in gs_rank_desc; there is no dst)
+ *        s(q, w) = <Xq[q], Zc[w]>                                        (the arithmetic of gs_rank_count, bit for bit: s(q, w)
+ *                  equals the t that gs_rank_count returns for dst[q] = w)
+ *        ids[q], scores[q] = the first count[q] = min(k, |C_q|) members of C_q in the total order (s descending, w ascending)
+ *                  and their scores; entries at and beyond count[q] are -1 / -inf.  A score of -0.0f is reported as +0.0f.
+ *      Inputs are finite by contract (a NaN score lands at an unspecified position).  1 <= k <= GS_TOPK_MAX; d is a multiple
+ *      of 4 in [4, 1024]; ld >= d; ids and scores are dense [Q][k].  src entries must lie in [0, n_rows).
+ *      Per (slice, query) the first launch keeps an unsorted list of at most cap = 64 * (1 + ceil(k / 64)) uint64 keys
+ *      (score bits mapped monotonically to unsigned in the high half, ~w in the low half) and its length; a second launch
+ *      merges the slices.  Compares only: bitwise reproducible, no atomics.
+ *      gs_topk_ws_bytes(Q, n_cand, k) = slices * Q * (8 * cap + 4) with the slices of gs_rank_ws_bytes.  Callers with many
+ *      queries pass them in chunks (the binding: 65,536).
+ *      gs_topk_desc is 144 bytes on every target (checked at compile time and by the binding; passed by pointer).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_TOPK_MAX 128
+typedef struct gs_topk_desc {
+    const float* Xq;           /* device [Q][ldq] query rows */
+    const float* Zc;           /* device [n_rows][ldz] candidate table */
+    const int32_t* src;        /* device [Q] or NULL: table row of the query node */
+    const int64_t* f_rowptr;   /* device [n_rows + 1] or NULL */
+    const int32_t* f_col;      /* device [f_nnz] or NULL (with f_rowptr) */
+    int32_t* ids;              /* device [Q][k] */
+    float* scores;             /* device [Q][k] */
+    int32_t* count;            /* device [Q] */
+    void* ws;                  /* device, 8-byte aligned, ws_bytes >= gs_topk_ws_bytes(Q, n_cand, k) */
+    int64_t Q, ldq, n_rows, n_cand, ldz, f_nnz, ws_bytes;
+    int32_t d, k, flags;       /* flags: 0 or GS_RANK_KEEP_SRC */
+} gs_topk_desc;
+int gs_topk_ws_bytes(int64_t Q, int64_t n_cand, int32_t k, int64_t* bytes_out_host);
+int gs_topk_select(const gs_topk_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
