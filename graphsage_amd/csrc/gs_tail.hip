@@ -152,9 +152,16 @@ __global__ __launch_bounds__(TAIL_THREADS) void sage_tail_kernel(const TailArgs 
         const float* B0 = a.Wh + (n0 + j) * ldw;
 #pragma unroll
         for (int m = 0; m < 4 * CW; ++m) {
-            const int kq = min(16 * m + 4 * q, Cp4 - 4);     // clamped: dlogits are zero beyond C
+            const int k0 = 16 * m + 4 * q;                   // first class of this float4
+            const int kq = min(k0, Cp4 - 4);                 // clamped: dlogits are zero beyond C
             bh5[m][0] = *reinterpret_cast<const f32x4*>(B0 + kq);
             bh5[m][1] = *reinterpret_cast<const f32x4*>(B0 + 16 * ldw + kq);
+            // ... but 0 * NaN is not: W_head's pad columns [C, Cp4) may hold anything, so classes >= C are SELECTED to zero here,
+            // ahead of the z pick-up (finite pads: the same bits, their products were zeros)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (k0 + e >= C) { bh5[m][0][e] = 0.f; bh5[m][1][e] = 0.f; }
+            }
         }
     }
     // (two class groups: the wider logits / d_y operands take the registers of the second input-gradient slab, which is

@@ -655,7 +655,23 @@ int gs_dense_wgrad_grouped_tiled3_sample(const gs_wgrad_desc* descs_host, int32_
  *   c0..c2 (nullable device counters) are advanced by d0..d2 at the end of the launch.
  * Supported: concat, no aggregator bias, s <= 11, d_in in {128, 256}, out_dim in {64, 128}, C <= 128
  * (gs_sage_tail_supported);
- * anything else returns GS_ENOTSUP and the caller uses the per-operator entry points. */
+ * anything else returns GS_ENOTSUP and the caller uses the per-operator entry points.
+ *
+ * Operand / output contract of every entry point of this section (gs_sage_tail_fwd_bwd[_means], gs_sage_tail_z[_means],
+ * gs_sage_tail_dh0, gs_linkpred_tail[_means], gs_linkpred_tail_neg), as K3's:
+ *   readable: operands are read as whole float4 / float2, so columns up to round_up(width, 4) of a row must be readable
+ *     (W_head: ldwh >= round_up(C, 4)); of h0 the n + n*s rows; bias and labels the C logical elements only.
+ *   may hold anything, NaN included (masks are selects, never products): every pad column -- of h0, W_self, W_neigh, W_head
+ *     (columns [C, round_up(C, 4)) among them), labels, dz (gs_sage_tail_dh0), means (the *_means entries) --, h0 rows behind row
+ *     n + n*s, the words behind the bias.  gcn: the pad is behind column 2*out_dim of the ONE matrix.
+ *   written: the logical block of every output of the form; columns [C, round_up(C, 4)) of logits / preds / dlogits as
+ *     zeros; d_h0 elements with h0 <= 0 (-0 included; a positive subnormal keeps its gradient) as +0; all n + n*s rows of d_h0.
+ *     No other word: not the rows around a row-sliced output, not the columns from round_up(width, 4) on.
+ *   untouched by form: means under the *_means entries; z and means in the z_ready launch (they are its inputs); dz and d_h0
+ *     with train == 0 (gs_linkpred_tail*: neg_slabs too); logits / preds / aff_all when NULL; loss_out / mrr_out and the
+ *     counters when loss_out == NULL; ids_copy_dst under z_ready; every output when an entry refuses its arguments (nothing is
+ *     launched) or n == 0 (GS_OK).
+ * tests/test_tail_edges_gpu.py holds this, and every stage to a float64 reference (tests/tail_oracle.py). */
 typedef struct gs_tail_desc {
     const float* h0; int64_t ldh; int64_t n;
     const float* W_self; int64_t ldws;
