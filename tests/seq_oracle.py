@@ -86,6 +86,50 @@ def lstm_bwd(dh_last, cache):
     return dx, np.concatenate([dWx, dWh], axis=0), db
 
 
+def recurrence_fwd(G, L, W_h):
+    """The contract of gs_lstm_fwd (include/graphsage_amd.h): gate pre-activations G [n, T, 4H] from the input projection, lengths
+    L [n], W_h [H, 4H] -> (A [n, T, 4H] activated gates, C [n, T, H] cell states, H_prev [n, T, H] = h_{t-1}, h_last [n, H],
+    ran [n, T] = t < L).  A, C and H_prev are exact zeros where the step does not run (the kernel leaves A and C untouched there
+    and zero-fills H_prev); H_prev is exact zero at t = 0."""
+    n, T, H4 = G.shape
+    H = H4 // 4
+    dt = G.dtype
+    A, C, Hp = np.zeros((n, T, H4), dt), np.zeros((n, T, H), dt), np.zeros((n, T, H), dt)
+    ran = np.arange(T)[None, :] < np.asarray(L)[:, None]
+    c, h = np.zeros((n, H), dt), np.zeros((n, H), dt)
+    for t in range(T):
+        m = ran[:, t]
+        z = G[m, t] + h[m] @ W_h
+        a = np.concatenate([_sig(z[:, :H]), np.tanh(z[:, H:2 * H]), _sig(z[:, 2 * H:3 * H] + dt.type(1.0)), _sig(z[:, 3 * H:])], axis=1)
+        Hp[m, t] = h[m]
+        c[m] = c[m] * a[:, 2 * H:3 * H] + a[:, :H] * a[:, H:2 * H]
+        h[m] = np.tanh(c[m]) * a[:, 3 * H:]
+        A[m, t], C[m, t] = a, c[m]
+    return A, C, Hp, h, ran
+
+
+def recurrence_bwd(dh_last, L, W_h, A, C):
+    """The contract of gs_lstm_bwd: BPTT from dh_last [n, H] over the saved A and C of recurrence_fwd -> dG [n, T, 4H], exact zero
+    for t >= L.  The gradient enters sequence r at its last step L_r - 1."""
+    n, T, H4 = A.shape
+    H = H4 // 4
+    L = np.asarray(L)
+    dG = np.zeros_like(A)
+    dh, dc = np.zeros_like(dh_last), np.zeros_like(dh_last)
+    for t in range(T - 1, -1, -1):
+        m = t < L
+        dh[L - 1 == t] += dh_last[L - 1 == t]
+        i, j, f, o = A[m, t, :H], A[m, t, H:2 * H], A[m, t, 2 * H:3 * H], A[m, t, 3 * H:]
+        cp = C[m, t - 1] if t > 0 else np.zeros_like(dh_last[m])
+        tc = np.tanh(C[m, t])
+        dct = dc[m] + dh[m] * o * (1 - tc * tc)
+        dz = np.concatenate([dct * j * i * (1 - i), dct * i * (1 - j * j), dct * cp * f * (1 - f), dh[m] * tc * o * (1 - o)], axis=1)
+        dG[m, t] = dz
+        dh[m] = dz @ W_h.T
+        dc[m] = dct * f
+    return dG
+
+
 def seq_aggregator_fwd(self_vecs, neigh_vecs, p, concat, act):
     L = lengths(neigh_vecs)
     h_last, lcache = lstm_fwd(neigh_vecs, L, p["lstm_kernel"], p["lstm_bias"])
