@@ -175,6 +175,8 @@ _PROTOS = {
     "gs_rank_count": [_P, _P],
     "gs_topk_ws_bytes": [c_int64, c_int64, c_int32, POINTER(c_int64)],
     "gs_topk_select": [_P, _P],
+    "gs_walk_paths": [_P, _P],
+    "gs_walk_pairs": [_P, _P],
 }
 
 
@@ -311,6 +313,22 @@ class TopkDesc(ctypes.Structure):
 
 TOPK_MAX = 128                              # GS_TOPK_MAX
 assert ctypes.sizeof(TopkDesc) == 144      # static_assert in csrc/gs_topk.hip (passed by pointer, as RankDesc)
+
+
+class WalkDesc(ctypes.Structure):
+    """struct gs_walk_desc (include/graphsage_amd.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("starts", c_void_p), ("paths", c_void_p), ("counts", c_void_p),
+                ("offsets", c_void_p), ("pairs", c_void_p),
+                ("n_nodes", c_int64), ("nnz", c_int64), ("n_starts", c_int64), ("walk0", c_int64), ("n_walks", c_int64),
+                ("ld_paths", c_int64), ("pairs_cap", c_int64),
+                ("seed", c_uint64), ("thr_return", c_uint64), ("thr_common", c_uint64), ("thr_far", c_uint64),
+                ("num_walks", c_int32), ("walk_len", c_int32)]
+
+
+WALK_TAG = 0xA7 << 56                       # GS_WALK_TAG
+WALK_ATTEMPTS = 256                         # GS_WALK_ATTEMPTS
+WALK_MAX_LEN = 4096                         # GS_WALK_MAX_LEN
+assert ctypes.sizeof(WalkDesc) == 152      # static_assert in csrc/gs_walk.hip (passed by pointer, as RankDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

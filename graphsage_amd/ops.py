@@ -362,6 +362,90 @@ def topk_select(Xq, Zc, k, n_cand=None, src=None, f_rowptr=None, f_col=None, kee
     return ids, scores, count
 
 
+# ------------------------------------------------------------------------------------------ WALK
+WALK_MIN_RATIO = 16  # min(1/p, 1, 1/q) / max(1/p, 1, 1/q) >= 1 / 16: what the attempt cap's bound rests on
+
+
+def walk_thresholds(p, q):
+    """(p, q) of node2vec -> (thr_return, thr_common, thr_far), the integer acceptance thresholds of gs_walk_paths:
+    floor(w / wmax * 2^32) for w = (1/p, 1, 1/q), in exact rational arithmetic (the largest is exactly 2^32).  Refuses p, q
+    whose smallest weight is below 1/16 of the largest."""
+    from fractions import Fraction
+    try:
+        fp, fq = Fraction(float(p)), Fraction(float(q))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("walk parameters p=%r q=%r must be finite positive numbers" % (p, q))
+    if fp <= 0 or fq <= 0:
+        raise ValueError("walk parameters p=%r q=%r must be positive" % (p, q))
+    w = (1 / fp, Fraction(1), 1 / fq)
+    wmax = max(w)
+    if min(w) * WALK_MIN_RATIO < wmax:
+        raise ValueError("walk parameters p=%g q=%g are out of range: min(1/p, 1, 1/q) / max(1/p, 1, 1/q) = %.4g must be at "
+                         "least 1/%d (rejection sampling with a bounded number of attempts; p and q within [0.25, 4] with "
+                         "max(p, q, 1) / min(p, q, 1) <= %d qualify)"
+                         % (p, q, float(min(w) / wmax), WALK_MIN_RATIO, WALK_MIN_RATIO))
+    return tuple(int(x / wmax * (1 << 32)) for x in w)
+
+
+def _walk_desc(rowptr, col, starts, num_walks, walk_len, walk0, n_walks, paths):
+    n_starts = starts.numel()
+    total = n_starts * int(num_walks)
+    n_walks = total - walk0 if n_walks is None else int(n_walks)
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or starts.dtype != torch.int32 or not (
+            rowptr.is_contiguous() and col.is_contiguous() and starts.is_contiguous()) or rowptr.numel() < 1:
+        raise _lib.GraphsageAmdError("walks: rowptr int64 [n_nodes + 1], col int32 and starts int32 must be dense vectors")
+    if num_walks < 1 or walk0 < 0 or n_walks < 0 or walk0 + n_walks > total:
+        raise _lib.GraphsageAmdError("walks: walks %d .. %d lie outside the job of %d starts x %d walks"
+                                     % (walk0, walk0 + n_walks, n_starts, num_walks))
+    if paths is not None and (paths.dtype != torch.int32 or paths.dim() != 2 or paths.shape[0] != n_walks
+                              or paths.shape[1] != walk_len or paths.stride(1) != 1):
+        raise _lib.GraphsageAmdError("walks: paths must be int32 [n_walks, walk_len] with unit column stride")
+    d = _lib.WalkDesc()
+    d.rowptr, d.col, d.starts = ptr(rowptr), (ptr(col) if col.numel() else None), (ptr(starts) if n_starts else None)
+    d.n_nodes, d.nnz, d.n_starts, d.walk0, d.n_walks = rowptr.numel() - 1, col.numel(), n_starts, walk0, n_walks
+    d.num_walks, d.walk_len = int(num_walks), int(walk_len)
+    return d
+
+
+def walk_paths(rowptr, col, starts, num_walks, walk_len, thresholds, seed, walk0=0, n_walks=None, paths=None, counts=None,
+               stream=None):
+    """gs_walk_paths: walks walk0 .. walk0 + n_walks - 1 of the job `num_walks walks of walk_len nodes from every entry of
+    starts` under the (p, q) law given by `thresholds` (walk_thresholds).  rowptr int64 [n_nodes + 1], col int32 with ascending
+    rows, starts int32: device vectors.  Returns (paths int32 [n_walks, walk_len], counts int32 [n_walks])."""
+    d = _walk_desc(rowptr, col, starts, num_walks, walk_len, int(walk0), n_walks, paths)
+    dev = rowptr.device
+    paths = torch.empty((d.n_walks, max(int(walk_len), 0)), dtype=torch.int32, device=dev) if paths is None else paths
+    counts = torch.empty(d.n_walks, dtype=torch.int32, device=dev) if counts is None else counts
+    if counts.dtype != torch.int32 or counts.numel() != d.n_walks or not counts.is_contiguous():
+        raise _lib.GraphsageAmdError("walk_paths: counts must be a dense int32 [n_walks]")
+    d.paths, d.counts = (ptr(paths) if paths.numel() else None), (ptr(counts) if d.n_walks else None)
+    d.ld_paths = paths.stride(0) if d.n_walks > 1 else max(int(walk_len), 1)
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    d.thr_return, d.thr_common, d.thr_far = (int(t) for t in thresholds)
+    call("gs_walk_paths", ctypes.addressof(d), _s(stream))
+    return paths, counts
+
+
+def walk_pairs(paths, offsets, total, pairs=None, stream=None):
+    """gs_walk_pairs: the (start, current) pairs of `paths` (walk_paths) written at `offsets` = the exclusive prefix sum of its
+    counts (int64 [n_walks]); total = the sum of the counts.  Returns pairs int32 [total, 2], by walk and then by position."""
+    n_walks, walk_len = paths.shape
+    if offsets.dtype != torch.int64 or offsets.numel() != n_walks or not offsets.is_contiguous() or paths.dtype != torch.int32 \
+            or paths.stride(1) != 1:
+        raise _lib.GraphsageAmdError("walk_pairs: paths int32 [n_walks, walk_len], offsets a dense int64 [n_walks]")
+    pairs = torch.empty((int(total), 2), dtype=torch.int32, device=paths.device) if pairs is None else pairs
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous() \
+            or pairs.shape[0] < total:
+        raise _lib.GraphsageAmdError("walk_pairs: pairs must be a dense int32 [>= total, 2]")
+    d = _lib.WalkDesc()
+    d.paths, d.offsets, d.pairs = (ptr(paths) if paths.numel() else None), (ptr(offsets) if n_walks else None), \
+        (ptr(pairs) if pairs.numel() else None)
+    d.n_walks, d.walk_len, d.pairs_cap = n_walks, walk_len, int(total)
+    d.ld_paths = paths.stride(0) if n_walks > 1 else max(int(walk_len), 1)
+    call("gs_walk_pairs", ctypes.addressof(d), _s(stream))
+    return pairs[:int(total)]
+
+
 # ------------------------------------------------------------------------------------------ K3
 def sage_dense_fwd(self_m, self_idx, agg, agg_idx, n, W_self, W_neigh, out_dim, concat, act, bias, out,
                    stream=None):

@@ -72,7 +72,50 @@ def build_flags(argv=None):
                         'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
                         'topk_full_scores.npy; not for n2v / graphsage_seq')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
+    p.add_argument('--walk_p', type=float, default=1.0,
+                   help='return parameter p of node2vec\'s second-order walk (a step back to the previous node weighs 1/p)')
+    p.add_argument('--walk_q', type=float, default=1.0,
+                   help='in-out parameter q of node2vec\'s second-order walk (a step away from the previous node\'s '
+                        'neighborhood weighs 1/q); p = q = 1 is the uniform walk of DeepWalk')
+    p.add_argument('--walk_len', type=int, default=5, help='nodes per generated random walk, the start included')
+    p.add_argument('--num_walks', type=int, default=50, help='generated random walks per start node')
+    p.add_argument('--device_walks', type=b, nargs='?', const=True, default=False,
+                   help='generate the random walks on the device (gs_walk_paths / gs_walk_pairs); implied by --walk_p / '
+                        '--walk_q other than 1')
     return p.parse_args(argv)
+
+
+def use_device_walks(flags):
+    return bool(getattr(flags, "device_walks", False)) or getattr(flags, "walk_p", 1.0) != 1.0 \
+        or getattr(flags, "walk_q", 1.0) != 1.0
+
+
+def refuse_walk_flags(flags):
+    """Out-of-range walk parameters are refused before any work is done, with the rule in the message."""
+    if flags.walk_len < 1 or flags.num_walks < 1:
+        raise SystemExit("--walk_len and --num_walks must be at least 1")
+    if not use_device_walks(flags):
+        return
+    from .ops import walk_thresholds
+    try:
+        walk_thresholds(flags.walk_p, flags.walk_q)
+    except ValueError as e:
+        raise SystemExit("--walk_p / --walk_q: %s" % e)
+
+
+def device_walks(rowptr, col, nodes, max_pairs=None):
+    """(start, current) pairs of (p, q) walks over a host CSR, generated on the device; prints the `Random walks:` line."""
+    import torch
+    from . import utils
+    dev = torch.device("cuda")
+    t0 = time.time()
+    pairs = utils.device_walk_pairs(torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(dev),
+                                    torch.from_numpy(np.ascontiguousarray(col, dtype=np.int32)).to(dev), nodes,
+                                    num_walks=FLAGS.num_walks, walk_len=FLAGS.walk_len, p=FLAGS.walk_p, q=FLAGS.walk_q,
+                                    seed=seed, max_pairs=max_pairs).cpu().numpy()
+    print("Random walks:", "law=", "node2vec", "p=", "{:g}".format(FLAGS.walk_p), "q=", "{:g}".format(FLAGS.walk_q),
+          "len=", FLAGS.walk_len, "walks=", FLAGS.num_walks, "pairs=", len(pairs), "time=", "{:.5f}".format(time.time() - t0))
+    return pairs
 
 
 def log_dir():
@@ -328,7 +371,10 @@ def n2v_retrain(G, model, minibatch, placeholders):
     nodes = np.where((G.val_mask | G.test_mask) & G.present)[0]
     start_time = time.time()
     rowptr, col = minibatch.test_csr                              # the walks see every edge (:335-338 walks on G)
-    pairs = utils.run_random_walks(rowptr, col, nodes, num_walks=50)
+    if use_device_walks(FLAGS):
+        pairs = device_walks(rowptr, col, nodes)
+    else:
+        pairs = utils.run_random_walks(rowptr, col, nodes, num_walks=FLAGS.num_walks, walk_len=FLAGS.walk_len)
     walk_time = time.time() - start_time
     test_minibatch = EdgeMinibatchIterator(G, None, placeholders, batch_size=FLAGS.batch_size, max_degree=FLAGS.max_degree,
                                            num_neg_samples=FLAGS.neg_sample_size, context_pairs=pairs, n2v_retrain=True,
@@ -361,6 +407,7 @@ def main(argv=None):
     from . import supervised_train as st
     st.refuse_full_inference(FLAGS)
     st.refuse_dropout(FLAGS)
+    refuse_walk_flags(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)
     G = st.load_graph()
@@ -372,7 +419,11 @@ def main(argv=None):
         else:
             rp, col = utils.build_csr(G.n_nodes, G.src, G.dst, keep=~G.train_removed)
             train_nodes = np.where(~(G.val_mask | G.test_mask))[0]
-            pairs = utils.run_random_walks(rp, col, train_nodes, max_pairs=FLAGS.max_walk_pairs)
+            if use_device_walks(FLAGS):
+                pairs = device_walks(rp, col, train_nodes, max_pairs=FLAGS.max_walk_pairs)
+            else:
+                pairs = utils.run_random_walks(rp, col, train_nodes, num_walks=FLAGS.num_walks, walk_len=FLAGS.walk_len,
+                                               max_pairs=FLAGS.max_walk_pairs)
     print("Done loading training data..")
     return train(G, pairs)
 

@@ -484,3 +484,75 @@ def random_walk_pairs_device(rowptr, col, nodes, num_walks=N_WALKS, walk_len=WAL
     if max_pairs is not None and pairs.shape[0] > max_pairs:
         pairs = pairs[torch.randperm(pairs.shape[0], device=device, generator=g)[:max_pairs]]
     return pairs
+
+
+WALK_CHUNK = 1 << 22      # walks per launch of device_walk_pairs (80 MB of paths at walk_len 5)
+_rows_checked = {}        # graphs whose rows were found ascending: one check per graph
+
+
+def check_rows_ascending(rowptr, col):
+    """Raise unless every row of the CSR (device tensors) is ascending: the membership test of the second-order walk is a
+    binary search over the previous node's row.  The verdict is kept per graph (storage, size, version)."""
+    import torch
+    import weakref
+    seen = _rows_checked.get("last")                # (weak rowptr, weak col, their versions): the same live tensors, unwritten
+    if seen is not None and seen[0]() is rowptr and seen[1]() is col and seen[2] == (rowptr._version, col._version):
+        return
+    if col.numel() > 1:
+        first = torch.zeros(col.numel() + 1, dtype=torch.bool, device=col.device)
+        first[rowptr.clamp(0, col.numel())] = True                  # a descent is fine where a new row begins
+        bad = (col[1:] < col[:-1]) & ~first[1:-1]
+        if bool(bad.any()):
+            k = int(torch.nonzero(bad)[0]) + 1
+            row = int(torch.searchsorted(rowptr, torch.tensor([k], device=col.device), right=True)[0]) - 1
+            raise ValueError("device_walk_pairs: row %d of the adjacency is not ascending (col[%d] = %d after %d); the (p, q) "
+                             "walk finds common neighbors by binary search and needs sorted rows -- sort each row of col, "
+                             "or walk with p = q = 1" % (row, k, int(col[k]), int(col[k - 1])))
+    _rows_checked["last"] = (weakref.ref(rowptr), weakref.ref(col), (rowptr._version, col._version))
+
+
+def device_walk_pairs(rowptr, col, nodes, num_walks=N_WALKS, walk_len=WALK_LEN, p=1.0, q=1.0, seed=123, max_pairs=None,
+                      return_paths=False, chunk_walks=None):
+    """Co-occurrence pairs (utils.py:77-92: (start, current) wherever they differ) from node2vec's second-order (p, q) walks,
+    generated by the gs_walk_* kernels from a CSR in HBM (rowptr int64 [N + 1], col int32; for (p, q) != (1, 1) every row
+    ascending, which is verified once per graph).  p = q = 1 is the uniform walk of DeepWalk.  Degree-0 starts are dropped
+    (:80-81); with max_pairs the start nodes are subsampled and the pairs truncated by a seeded permutation, as in
+    random_walk_pairs_device.  The walks run in chunks of chunk_walks; the result does not depend on the chunking.  A random
+    stream of its own: not that of run_random_walks or random_walk_pairs_device.
+    Returns an int32 [n_pairs, 2] device tensor (with return_paths: and the int32 [n_walks, walk_len] paths)."""
+    import torch
+    from . import ops
+    thr = ops.walk_thresholds(p, q)
+    num_walks, walk_len = int(num_walks), int(walk_len)
+    if num_walks < 1 or walk_len < 1:
+        raise ValueError("device_walk_pairs: num_walks=%d and walk_len=%d must be at least 1" % (num_walks, walk_len))
+    device = rowptr.device
+    n_nodes = rowptr.numel() - 1
+    if len(set(thr)) > 1:
+        check_rows_ascending(rowptr, col)
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    nodes = torch.as_tensor(nodes, device=device).to(torch.int64).reshape(-1)
+    if nodes.numel() and bool(((nodes < 0) | (nodes >= n_nodes)).any()):
+        raise ValueError("device_walk_pairs: start ids must lie in [0, %d)" % n_nodes)
+    deg = rowptr[1:] - rowptr[:-1]
+    nodes = nodes[deg[nodes] > 0]                               # :80-81
+    if max_pairs is not None and nodes.numel():
+        per_node = max(1, (walk_len - 1) * num_walks)
+        keep = max(1, min(int(nodes.numel()), int(np.ceil(max_pairs / per_node))))
+        nodes = nodes[torch.randperm(nodes.numel(), device=device, generator=g)[:keep]]
+    starts = nodes.to(torch.int32).contiguous()
+    total_walks = starts.numel() * num_walks
+    chunk = max(1, int(chunk_walks or WALK_CHUNK))
+    all_paths = torch.empty((total_walks, walk_len), dtype=torch.int32, device=device) if return_paths else None
+    out = []
+    for w0 in range(0, total_walks, chunk):
+        n = min(chunk, total_walks - w0)
+        paths, counts = ops.walk_paths(rowptr, col, starts, num_walks, walk_len, thr, seed, walk0=w0, n_walks=n,
+                                       paths=all_paths[w0:w0 + n] if return_paths else None)
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        out.append(ops.walk_pairs(paths, ends - counts, int(ends[-1])))
+    pairs = torch.cat(out, dim=0) if out else torch.zeros((0, 2), dtype=torch.int32, device=device)
+    if max_pairs is not None and pairs.shape[0] > max_pairs:
+        pairs = pairs[torch.randperm(pairs.shape[0], device=device, generator=g)[:max_pairs]]
+    return (pairs, all_paths) if return_paths else pairs

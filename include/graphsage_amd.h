@@ -1126,6 +1126,49 @@ int gs_topk_ws_bytes(int64_t Q, int64_t n_cand, int32_t k, int64_t* bytes_out_ho
 int gs_topk_select(const gs_topk_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * WALK second-order (p, q) random walks of node2vec over a CSR adjacency (rowptr int64 [n_nodes + 1], col int32 [nnz], every
+ *      row ASCENDING; duplicates allowed and drawn as often as they are stored).  The job is the walk list
+ *      g = 0 .. n_starts * num_walks - 1, walk g starting at starts[g / num_walks]; one call runs the n_walks walks
+ *      g = walk0 .. walk0 + n_walks - 1 and its outputs are indexed by i = g - walk0.  The stream of walk g depends on
+ *      (seed, g) only: a job cut into several calls gives the walks of one call.
+ *        paths[i][0] = start; paths[i][j], 1 <= j < walk_len, the node after j steps.
+ *        Step j from v (previous node t; none before the first move): a node with no row entries keeps the walk where it is
+ *        and leaves t as it was.  Otherwise attempt a = 0, 1, .. draws h = mix64(walkkey + 256 j + a) with
+ *        walkkey = mix64(seed ^ GS_WALK_TAG) + g * 0xD1342543DE82EF95 (mix64: the sampler's splitmix64 finalizer), takes
+ *        x = col[rowptr[v] + (((h >> 32) * deg) >> 32)] and accepts it iff (h & 0xFFFFFFFF) < thr, where thr = 2^32 when there
+ *        is no t, thr_return when x == t, thr_common when x occurs in t's row (binary search, at most 32 probes), thr_far
+ *        otherwise.  Attempt 255 is taken whatever it draws.  On a move t = v, v = x.
+ *        thr_* = floor(w / wmax * 2^32) for the weights w = (1/p, 1, 1/q): the largest must be exactly 2^32 and the smallest
+ *        at least 2^28 (min(w) / wmax >= 1/16: a step then reaches the cap with probability <= (15/16)^256); else GS_EINVAL.
+ *        No float reaches the kernel.  With all three at 2^32 the search is skipped; the walks are the same.
+ *        A start id outside [0, n_nodes) gives a row of -1 and counts[i] = 0.  A col entry outside [0, n_nodes) can be walked
+ *        to but never from (it has no row), and appears in paths and pairs as it is stored.
+ *        counts[i] = #{1 <= j < walk_len : paths[i][j] != paths[i][0]}   (utils.py:87-88: no self co-occurrences)
+ *      gs_walk_paths writes paths (ld_paths >= walk_len) and counts.  The caller forms offsets = the exclusive prefix sum of
+ *      counts (int64 [n_walks]); gs_walk_pairs then writes pairs[offsets[i] + k] = (paths[i][0], k-th position of walk i that
+ *      differs from it), rows at or beyond pairs_cap are not written.  One lane per walk in both launches, integers only, no
+ *      atomics: bitwise reproducible.  gs_walk_desc is 152 bytes on every target (checked at compile time and by the binding;
+ *      passed by pointer, not part of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_WALK_TAG 0xA700000000000000ull      /* domain tag of the walk stream (the sampler's tags: gs_sample_dev.h) */
+#define GS_WALK_ATTEMPTS 256
+#define GS_WALK_MAX_LEN 4096
+typedef struct gs_walk_desc {
+    const int64_t* rowptr;     /* device [n_nodes + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const int32_t* starts;     /* device [n_starts]: the whole job's start ids */
+    int32_t* paths;            /* device [n_walks][ld_paths] */
+    int32_t* counts;           /* device [n_walks]; gs_walk_paths only */
+    const int64_t* offsets;    /* device [n_walks]; gs_walk_pairs only */
+    int32_t* pairs;            /* device [pairs_cap][2]; gs_walk_pairs only */
+    int64_t n_nodes, nnz, n_starts, walk0, n_walks, ld_paths, pairs_cap;
+    uint64_t seed, thr_return, thr_common, thr_far;
+    int32_t num_walks, walk_len;
+} gs_walk_desc;
+int gs_walk_paths(const gs_walk_desc* desc_host, void* stream);
+int gs_walk_pairs(const gs_walk_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
