@@ -171,6 +171,9 @@ _PROTOS = {
                      _P, _P, _P, _P, _P, c_uint64, _P, c_uint64, _P],
     "gs_csr_reduce_ws_bytes": [c_int64, c_int32, POINTER(c_int64)],
     "gs_csr_reduce_fwd": [_P, _P],
+    "gs_csr_reduce_rows": [_P, _P],
+    "gs_frontier_ws_bytes": [c_int64, POINTER(c_int64)],
+    "gs_frontier_expand": [_P, _P],
     "gs_rank_ws_bytes": [c_int64, c_int64, POINTER(c_int64)],
     "gs_rank_count": [_P, _P],
     "gs_topk_ws_bytes": [c_int64, c_int64, c_int32, POINTER(c_int64)],
@@ -287,6 +290,28 @@ class CsrReduceDesc(ctypes.Structure):
 
 
 assert ctypes.sizeof(CsrReduceDesc) == 200      # static_assert in csrc/gs_csr_reduce.hip (passed by pointer, as LstmSeg)
+
+
+class CsrRowsDesc(ctypes.Structure):
+    """struct gs_csr_rows_desc (include/graphsage_amd.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("items", c_void_p), ("splits", c_void_p), ("x_pos", c_void_p),
+                ("out_pos", c_void_p), ("X", c_void_p), ("out", c_void_p), ("ws", c_void_p),
+                ("n_rows", c_int64), ("nnz", c_int64), ("n_items", c_int64), ("n_split", c_int64), ("n_slots", c_int64),
+                ("ldx", c_int64), ("x_rows", c_int64), ("ldo", c_int64), ("out_rows", c_int64), ("ws_bytes", c_int64),
+                ("d", c_int32), ("op", c_int32), ("act", c_int32), ("split_len", c_int32)]
+
+
+assert ctypes.sizeof(CsrRowsDesc) == 168      # static_assert in csrc/gs_csr_reduce.hip (passed by pointer, as CsrReduceDesc)
+
+
+class FrontierDesc(ctypes.Structure):
+    """struct gs_frontier_desc (include/graphsage_amd.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("rows_in", c_void_p), ("rows_out", c_void_p), ("pos", c_void_p),
+                ("count", c_void_p), ("ws", c_void_p),
+                ("n_rows", c_int64), ("nnz", c_int64), ("m", c_int64), ("rows_out_cap", c_int64), ("ws_bytes", c_int64)]
+
+
+assert ctypes.sizeof(FrontierDesc) == 96      # static_assert in csrc/gs_frontier.hip (passed by pointer, as CsrReduceDesc)
 
 
 class RankDesc(ctypes.Structure):

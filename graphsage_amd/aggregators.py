@@ -304,6 +304,20 @@ class _SageBase(Layer):
         e.sync()
         return out
 
+    def _infer_rows_sage(self, L, csr_op, table, x_pos, width, H):
+        """Tail of infer_rows: `table` (read through x_pos) reduced over the whole neighbor lists of the rows of L into a
+        compact [L.n, width] table, then the SAGE matmuls over [rows L.self_ids of H | reduced]."""
+        from . import inference as inf
+        e = self.engine
+        out = inf._table(e, L.n, self.output_dim * (2 if self.concat else 1))
+        reduced = inf._table(e, L.n, width, ld_multiple=32)
+        L.reduce(e, csr_op, table, reduced, x_pos)
+        b = self.vars['bias'].value.buf if self.bias else None
+        ops.sage_dense_fwd(H, L.self_ids, reduced, None, L.n, self.vars['self_weights'].value, self.vars['neigh_weights'].value,
+                           self.output_dim, self.concat, self.act_code, b, out, stream=e.stream)
+        e.sync()
+        return out
+
 
 class MeanAggregator(_SageBase):
     """Aggregates via mean followed by matmul and non-linearity (aggregators.py:6-64)."""
@@ -516,6 +530,23 @@ class MeanAggregator(_SageBase):
         e.sync()
         return out
 
+    def infer_rows(self, L, H):
+        """infer_full for the rows of L (inference.RowsLayer) only, into a compact [L.n, n_out] table: H is the table of the layer
+        below (the feature table by node id, or the compact table over the rows this layer may read).  The same two forms."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in = self.output_dim, H.d
+        if not (self.concat and not self.bias and o % 4 == 0 and o < d_in):
+            return self._infer_rows_sage(L, inf.CSR_MEAN, H, L.src_pos, d_in, H)
+        out = inf._table(e, L.n, 2 * o)
+        P = inf._table(e, L.prev_n, o)
+        ops.gemm(False, False, L.prev_n, o, d_in, H, self.vars['neigh_weights'].value, P, a_row_idx=L.prev_ids, stream=e.stream)
+        ops.gemm(False, False, L.n, o, d_in, H, self.vars['self_weights'].value, out.cols_slice(0, o), a_row_idx=L.self_ids,
+                 act=self.act_code, stream=e.stream)
+        L.reduce(e, inf.CSR_MEAN, P, out.cols_slice(o, 2 * o), L.prev_pos, act=self.act_code)
+        e.sync()
+        return out
+
 
 class GCNAggregator(_SageBase):
     """Same matmul parameters for self and neighbor vectors (aggregators.py:66-116).
@@ -640,6 +671,25 @@ class GCNAggregator(_SageBase):
                 graph.reduce(e, inf.CSR_MEAN_SELF, H, means, r0, n)
                 ops.sage_dense_fwd(None, None, means, None, n, None, W, o, False, self.act_code, b, out.rows_slice(r0, r0 + n),
                                    stream=e.stream)
+        e.sync()
+        return out
+
+    def infer_rows(self, L, H):
+        """infer_full for the rows of L (inference.RowsLayer) only, into a compact [L.n, output_dim] table."""
+        from . import inference as inf
+        e = self.engine
+        o, d_in = self.output_dim, H.d
+        out = inf._table(e, L.n, o)
+        W = self.vars['weights'].value
+        b = self.vars['bias'].value.buf if self.bias else None
+        if o % 4 == 0 and o <= d_in:
+            P = inf._table(e, L.prev_n, o)
+            ops.gemm(False, False, L.prev_n, o, d_in, H, W, P, a_row_idx=L.prev_ids, bias=b, stream=e.stream)
+            L.reduce(e, inf.CSR_MEAN_SELF, P, out, L.prev_pos, act=self.act_code)
+        else:
+            means = inf._table(e, L.n, d_in, ld_multiple=32)
+            L.reduce(e, inf.CSR_MEAN_SELF, H, means, L.src_pos)
+            ops.sage_dense_fwd(None, None, means, None, L.n, None, W, o, False, self.act_code, b, out, stream=e.stream)
         e.sync()
         return out
 
@@ -854,6 +904,17 @@ class _PoolingAggregator(_PoolBase):
         pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid)
         return self._infer_reduce_sage(graph, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, pooled, H, out)
 
+    def infer_rows(self, L, H):
+        """infer_full for the rows of L (inference.RowsLayer) only: the MLP once per row this layer may read, the reduce and the
+        SAGE matmuls over the rows of L."""
+        from . import inference as inf
+        e = self.engine
+        mlp = self.mlp_layers[0]
+        Hh = inf._table(e, L.prev_n, self.hidden_dim)
+        ops.gemm(False, False, L.prev_n, self.hidden_dim, H.d, H, mlp.vars['weights'].value, Hh, a_row_idx=L.prev_ids,
+                 bias=mlp.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
+        return self._infer_rows_sage(L, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, L.prev_pos, self.hidden_dim, H)
+
 
 class MaxPoolingAggregator(_PoolingAggregator):
     """Aggregates via max-pooling over MLP functions (aggregators.py:119-195)."""
@@ -951,6 +1012,9 @@ class SeqAggregator(_SageBase):
     def infer_full(self, graph, H):
         raise ops._lib.GraphsageAmdError("SeqAggregator has no full-neighborhood form: an LSTM over a random permutation of a "
                                          "SAMPLE of the neighbors has no meaning over the whole list (use eval_step)")
+
+    def infer_rows(self, L, H):
+        return self.infer_full(L.graph, H)
 
 
 class TwoMaxLayerPoolingAggregator(_PoolBase):
@@ -1098,3 +1162,17 @@ class TwoMaxLayerPoolingAggregator(_PoolBase):
                      bias=mlp2.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
         pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid2)
         return self._infer_reduce_sage(graph, inf.CSR_MAX, Hh2, pooled, H, out)
+
+    def infer_rows(self, L, H):
+        """infer_full for the rows of L (inference.RowsLayer) only: both Dense layers once per row this layer may read."""
+        from . import inference as inf
+        e = self.engine
+        mlp1, mlp2 = self.mlp_layers
+        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
+        Hh1 = inf._table(e, L.prev_n, hid1)
+        Hh2 = inf._table(e, L.prev_n, hid2)
+        ops.gemm(False, False, L.prev_n, hid1, H.d, H, mlp1.vars['weights'].value, Hh1, a_row_idx=L.prev_ids,
+                 bias=mlp1.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
+        ops.gemm(False, False, L.prev_n, hid2, hid1, Hh1, mlp2.vars['weights'].value, Hh2, bias=mlp2.vars['bias'].value.buf,
+                 act=ACT_RELU, stream=e.stream)
+        return self._infer_rows_sage(L, inf.CSR_MAX, Hh2, L.prev_pos, hid2, H)

@@ -21,6 +21,16 @@ The split rule.  One wave reduces one work item; a row longer than `split_len` (
 many, reduced by separate waves into a workspace and combined in segment order by a second small launch: a hub of thousands
 of neighbors does not outlive the launch, no float atomics, one fixed summation order.
 
+A node subset.  The same exact pass over only the rows a request depends on:
+
+    emb, stats = model.embed_nodes(graph, nodes)                # rows in request order; stats: rows [|S_K| .. |S_0|], edges
+    emb, preds, stats = sup_model.predict_nodes(graph, nodes)
+
+S_K = the distinct requested ids, S_{l-1} = S_l U N(S_l), found on the device (gs_frontier_expand, csrc/gs_frontier.hip);
+layer l is computed for the rows of S_l into a compact table, read and written through position maps (gs_csr_reduce_rows:
+the window kernel's own item loop, so every row comes out with the same bits).  When |S_0| reaches about half of the graph
+the whole-graph pass is the faster one (profiles/embed_nodes.md).
+
 Link ranking.  What the exact embeddings are for: where does the true partner of a held-out edge (u, v) stand among ALL nodes?
 
     res = model.rank_full(graph, edges)                         # ranks, ranks_optimistic, n_gt, n_eq, scores, mrr, hits
@@ -108,6 +118,7 @@ class FullGraph(object):
             self.col = np.ascontiguousarray(col, dtype=np.int32)
         self._check(rowptr_host)
         self.nnz = int(rowptr_host[-1])
+        self.rowptr_host = rowptr_host
         self.items, self.item_ptr, self.splits = plan_work_items(rowptr_host, self.split_len)
         self._dev = {}
         self._rank_filter = None
@@ -235,6 +246,53 @@ class FullGraph(object):
                            slot_r, ws=ws, act=act, stream=engine.stream)
         return out
 
+    # ------------------------------------------------------------------------------------------------ row subsets
+    def plan_rows(self, rows):
+        """(items, splits) of the row subset `rows` (ascending, duplicate-free, in [0, n_rows)), cut from the graph's own plan
+        (NumPy, no device needed): the items of those rows in the plan's order, with the partial slots re-based to
+        0 .. sum(splits[:, 2]) -- what gs_csr_reduce_rows takes."""
+        rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        if rows.size and (rows[0] < 0 or rows[-1] >= self.n_rows or (np.diff(rows) <= 0).any()):
+            raise GraphsageAmdError("FullGraph.plan_rows: rows must be ascending, duplicate-free ids in [0, %d)" % self.n_rows)
+        first = self.item_ptr[rows]
+        cnt = self.item_ptr[rows + 1] - first
+        start = np.zeros(rows.shape[0] + 1, np.int64)
+        np.cumsum(cnt, out=start[1:])
+        items = self.items[np.repeat(first - start[:-1], cnt) + np.arange(start[-1], dtype=np.int64)]
+        cut = items[:, 3] >= 0
+        items[cut, 3] = np.arange(int(cut.sum()), dtype=np.int64)          # consecutive within a row, rows ascending
+        splits = self.splits[np.isin(self.splits[:, 0], rows)] if self.splits.shape[0] else self.splits.copy()
+        splits[:, 1] = np.cumsum(splits[:, 2]) - splits[:, 2]
+        return items, splits
+
+    def reduce_rows(self, engine, op, X, out, rows, out_pos, x_pos=None, act=ops.ACT_IDENTITY, plan=None):
+        """out[out_pos[r]] = op over the whole neighbor list of every row r of `rows` (host ids: ascending, duplicate-free) of
+        the rows X[x_pos[col]] (x_pos None: X is indexed by node id, [>= n_rows, d]).  out_pos / x_pos: int32 device maps
+        [n_rows] (receptive_field makes them).  plan: the (items, splits) device tensors and slot count of plan_rows(rows), as
+        upload_plan returns them, when the caller reduces the same rows more than once."""
+        if x_pos is None and X.rows < self.n_rows:
+            raise GraphsageAmdError("FullGraph.reduce_rows: the table has %d rows, the graph %d" % (X.rows, self.n_rows))
+        rowptr, col, _, _ = self.on(engine.device)
+        items, splits, n_slots = plan if plan is not None else self.upload_plan(engine, rows)
+        ws = None
+        if n_slots:
+            words = ops.csr_reduce_ws_bytes(n_slots, X.d) // 4
+            ws = engine.ws_f32(("csr_reduce_ws",), max(1 << 16, 1 << (words - 1).bit_length()))
+        ops.csr_reduce_rows(rowptr, col, items, splits, self.n_rows, self.split_len, op, X, out, out_pos, x_pos=x_pos,
+                            n_slots=n_slots, ws=ws, act=act, stream=engine.stream)
+        return out
+
+    def upload_plan(self, engine, rows):
+        """plan_rows(rows) on the engine's device: (items, splits or None, slot count)."""
+        import torch
+        items, splits = self.plan_rows(rows)
+        n_slots = int(splits[:, 2].sum())
+        items_dev = torch.from_numpy(items).to(engine.device) if items.shape[0] else \
+            torch.zeros((1, 4), dtype=torch.int64, device=engine.device)[:0]
+        splits_dev = torch.from_numpy(splits).to(engine.device) if splits.shape[0] else None
+        torch.cuda.synchronize()          # the uploads ran on torch's stream; order them before the engine's
+        return items_dev, splits_dev, n_slots
+
 
 # ---------------------------------------------------------------------------------------------------- model passes
 WINDOW_ROWS = 32768      # rows per launch group: the per-window workspaces (means, pooled rows, partials) do not grow with N
@@ -263,6 +321,108 @@ def layers_full(model, graph):
     for agg in model.aggregators:
         H = agg.infer_full(graph, H)
     return H
+
+
+# ---------------------------------------------------------------------------------------------------- node subsets
+def receptive_field(engine, graph, nodes, n_layers):
+    """The rows a K-layer exact pass needs to answer `nodes`: S_K = the distinct requested ids, sorted, and
+    S_{l-1} = S_l U N(S_l), found on the device (gs_frontier_expand; the graph's CSR may only exist there).
+
+    Returns (sets, pos, edges), all ordered from the request down: sets[j] = S_{K-j} as an ascending int32 NumPy array
+    (|S| int32s and one count word come back per layer), pos[j] = its int32 device map [n_rows] (index in the set, -1 for a
+    non-member), edges[j] = the number of edges of the rows of S_{K-j}, j < K: what layer K - j visits."""
+    import torch
+    e = engine
+    ids = np.asarray(nodes).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= graph.n_rows):
+        raise GraphsageAmdError("node ids must lie in [0, %d]" % (graph.n_rows - 1))
+    S = np.unique(ids).astype(np.int32)
+    rowptr, col, _, _ = graph.on(e.device)
+    S_dev = torch.from_numpy(S).to(e.device)
+    pos = torch.full((graph.n_rows,), -1, dtype=torch.int32, device=e.device)
+    pos[S_dev.long()] = torch.arange(S.shape[0], dtype=torch.int32, device=e.device)
+    ws = e.ws_i32(("frontier_ws",), ops.frontier_ws_bytes(graph.n_rows) // 4)
+    count = torch.zeros(1, dtype=torch.int32, device=e.device)
+    sets, maps, edges = [S], [pos], []
+    deg = np.diff(graph.rowptr_host)
+    for _ in range(int(n_layers)):
+        n_edges = int(deg[S].sum())
+        cap = max(1, min(graph.n_rows, S.shape[0] + n_edges))
+        rows_out = torch.empty(cap, dtype=torch.int32, device=e.device)
+        pos = torch.empty(graph.n_rows, dtype=torch.int32, device=e.device)
+        torch.cuda.synchronize()          # uploads and fills ran on torch's stream; order them before the engine's
+        ops.frontier_expand(rowptr, col, graph.n_rows, S_dev if S.shape[0] else None, S.shape[0], rows_out, pos, count, ws,
+                            stream=e.stream)
+        e.sync()
+        S_dev = rows_out[:int(count.item())]
+        S = S_dev.cpu().numpy()
+        sets.append(S)
+        maps.append(pos)
+        edges.append(n_edges)
+    return sets, maps, edges
+
+
+class RowsLayer(object):
+    """What one layer of layers_nodes hands to an aggregator's infer_rows: compute the layer for the rows `rows` (S_l, n of
+    them) into a compact [n, d_out] table, from the table `src` of the layer below.
+
+      rows / rows_dev   S_l: ascending host ids / the same on the device (int32)
+      out_pos           device map id -> row of the output table (pos of S_l)
+      prev_n            |S_{l-1}|: the rows of the layer below that this layer may read
+      prev_ids          device ids that pick S_{l-1} out of `src`, in set order; None when src IS the compact table over S_{l-1}
+      prev_pos          device map id -> index in S_{l-1}: the x_pos of a compact table over S_{l-1}
+      src_pos           the x_pos of `src` itself (None: src is indexed by node id, the feature table)
+      self_ids          device ids that pick the rows of S_l out of `src`, in set order
+      plan              upload_plan(rows): shared by every reduce of the layer"""
+
+    def __init__(self, graph, engine, rows, rows_dev, out_pos, prev_rows_dev, prev_pos, by_id):
+        self.graph, self.rows, self.rows_dev, self.n, self.out_pos = graph, rows, rows_dev, int(rows.shape[0]), out_pos
+        self.prev_n, self.prev_pos = int(prev_rows_dev.numel()), prev_pos
+        self.prev_ids = prev_rows_dev if by_id else None
+        self.src_pos = None if by_id else prev_pos
+        self.self_ids = rows_dev if by_id else prev_pos[rows_dev.long()]
+        self.plan = graph.upload_plan(engine, rows)
+
+    def reduce(self, engine, op, X, out, x_pos, act=ops.ACT_IDENTITY):
+        return self.graph.reduce_rows(engine, op, X, out, self.rows, self.out_pos, x_pos=x_pos, act=act, plan=self.plan)
+
+
+def layers_nodes(model, graph, nodes):
+    """hidden[K] for the rows `nodes` depend on only: layer l is computed for the rows of S_l (receptive_field) into a compact
+    [|S_l|, d] table, layer 0 reading model.features by node id.  Returns (table over S_K Mat, S_K ids, pos of S_K, stats)
+    with stats = {"rows": [|S_K|, ..., |S_0|], "edges": [...], "n_rows": N + 1}."""
+    import torch
+    check_graph(model, graph)
+    e = model.engine
+    e.sync()
+    K = len(model.aggregators)
+    if np.asarray(nodes).size == 0:
+        raise GraphsageAmdError("receptive-field inference needs at least one node")
+    sets, maps, edges = receptive_field(e, graph, nodes, K)
+    devs = [torch.from_numpy(np.ascontiguousarray(S)).to(e.device) for S in sets]
+    torch.cuda.synchronize()
+    H = model.features
+    for l, agg in enumerate(model.aggregators):
+        j = K - 1 - l                          # sets[j] = S_{l+1}: the rows this layer computes; sets[j + 1] the rows it reads
+        H = agg.infer_rows(RowsLayer(graph, e, sets[j], devs[j], maps[j], devs[j + 1], maps[j + 1], by_id=(l == 0)), H)
+    e.sync()
+    return H, sets[0], maps[0], {"rows": [int(S.shape[0]) for S in sets], "edges": edges, "n_rows": graph.n_rows}
+
+
+def request_rows(model, table, S, nodes):
+    """(rows Mat [n, d], n): the rows of the compact table over the sorted distinct ids S in REQUEST order (a duplicate request
+    is answered twice)."""
+    import torch
+    e = model.engine
+    ids = np.asarray(nodes).reshape(-1)
+    idx = np.searchsorted(S, ids).astype(np.int32)
+    idx_dev = torch.from_numpy(idx).to(e.device)
+    torch.cuda.synchronize()
+    out = _table(e, max(ids.size, 1), table.d)
+    if ids.size:
+        ops.gather_rows(table, idx_dev, out=out, stream=e.stream)
+    e.sync()
+    return out, int(ids.size)
 
 
 def select_rows(model, table, nodes):

@@ -1000,6 +1000,21 @@ class SampleAndAggregate(object):
         e.sync()
         return y.numpy()[:n]
 
+    def embed_nodes(self, graph, nodes):
+        """(embeddings [n, d] (NumPy), stats): embed_full(graph, nodes) computed from the receptive field of `nodes` alone
+        (inference.layers_nodes): layer l only for the rows layer l + 1 of the request reads, found on the device.  Rows in
+        REQUEST order, a duplicate request answered twice.  stats = {"rows": [|S_K|, ..., |S_0|], "edges": [...], "n_rows":
+        N + 1}.  The values agree with embed_full to the float tolerance, not bitwise: the contractions may take another tile
+        form at another row count."""
+        from . import inference as inf
+        e = self.engine
+        H, S, _, stats = inf.layers_nodes(self, graph, nodes)
+        rows, n = inf.request_rows(self, H, S, nodes)
+        y = inf._table(e, max(n, 1), rows.d)
+        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
+        e.sync()
+        return y.numpy()[:n], stats
+
     def rank_full(self, graph, edges, filtered=True, hits=(1, 10, 50, 100)):
         """Rank the true partner of every edge (src, dst) among ALL N nodes with the exact embeddings of `graph` (the table of
         embed_full, kept on the device): inference.rank_full with n_cand = N (the pad row is never a candidate), the query

@@ -259,6 +259,45 @@ def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, ro
     return out
 
 
+def csr_reduce_rows(rowptr, col, items, splits, n_rows, split_len, op, X, out, out_pos, x_pos=None, n_slots=0, ws=None,
+                    act=ACT_IDENTITY, stream=None):
+    """gs_csr_reduce_rows: out[out_pos[r]] = mean | mean-with-self | max over the whole neighbor list of row r of the rows
+    X[x_pos[col[e]]], for the rows of a subset plan (inference.FullGraph.plan_rows: items / splits with slots 0 .. n_slots).
+    x_pos None: X is indexed by node id.  out_pos, x_pos: int32 device vectors [n_rows]."""
+    for name, m in (("out_pos", out_pos), ("x_pos", x_pos)):
+        if m is not None and (m.dtype != torch.int32 or m.numel() != n_rows):
+            raise _lib.GraphsageAmdError("csr_reduce_rows: %s must be an int32 vector of n_rows = %d entries" % (name, n_rows))
+    q = _lib.CsrRowsDesc()
+    q.rowptr, q.col, q.items, q.splits = ptr(rowptr), ptr(col), ptr(items), ptr(splits)
+    q.x_pos, q.out_pos = ptr(x_pos), ptr(out_pos)
+    q.X, q.out, q.ws = X.ptr, out.ptr, ptr(ws)
+    q.n_rows, q.nnz, q.n_items, q.n_split = n_rows, col.numel(), items.shape[0], (splits.shape[0] if splits is not None else 0)
+    q.n_slots = n_slots
+    q.ldx, q.x_rows, q.ldo, q.out_rows, q.ws_bytes = X.ld, X.rows, out.ld, out.rows, (4 * ws.numel() if ws is not None else 0)
+    q.d, q.op, q.act, q.split_len = X.d, op, act, split_len
+    call("gs_csr_reduce_rows", ctypes.addressof(q), _s(stream))
+    return out
+
+
+def frontier_ws_bytes(n_rows):
+    """Bytes of the int32 workspace gs_frontier_expand needs for a graph of n_rows rows (flags, zero on first use, + block sums)."""
+    out = ctypes.c_int64(0)
+    call("gs_frontier_ws_bytes", n_rows, ctypes.byref(out))
+    return out.value
+
+
+def frontier_expand(rowptr, col, n_rows, rows_in, m, rows_out, pos, count, ws, stream=None):
+    """gs_frontier_expand: rows_out = rows_in[:m] U their column ids (ascending, duplicate-free), pos[id] = index in rows_out or
+    -1, count[0] = members.  rows_in: ascending duplicate-free int32 device vector (None when m == 0); ws: int32 device vector
+    of frontier_ws_bytes(n_rows) bytes whose flag half is zero (every call leaves it zero)."""
+    q = _lib.FrontierDesc()
+    q.rowptr, q.col, q.rows_in, q.rows_out, q.pos, q.count, q.ws = (ptr(rowptr), ptr(col), ptr(rows_in), ptr(rows_out), ptr(pos),
+                                                                    ptr(count), ptr(ws))
+    q.n_rows, q.nnz, q.m, q.rows_out_cap, q.ws_bytes = n_rows, col.numel(), m, rows_out.numel(), 4 * ws.numel()
+    call("gs_frontier_expand", ctypes.addressof(q), _s(stream))
+    return rows_out, pos, count
+
+
 # ------------------------------------------------------------------------------------------ RANK
 RANK_CHUNK = 65536       # query rows per gs_rank_count call: the slab workspace does not grow with Q
 

@@ -348,9 +348,22 @@ class SupervisedGraphsage(SampleAndAggregate):
         `graph` (inference.FullGraph): l2_normalize, the prediction Dense and its softmax / sigmoid
         (supervised_models.py:85-93, :122-126)."""
         from . import inference as inf
+        rows, n = inf.select_rows(self, inf.layers_full(self, graph), nodes)
+        return self._head_rows(rows, n)
+
+    def predict_nodes(self, graph, nodes):
+        """(embeddings [n, d], preds [n, C], stats): predict_full(graph, nodes) computed from the receptive field of `nodes`
+        alone (SampleAndAggregate.embed_nodes): rows in REQUEST order, a duplicate request answered twice."""
+        from . import inference as inf
+        H, S, _, stats = inf.layers_nodes(self, graph, nodes)
+        rows, n = inf.request_rows(self, H, S, nodes)
+        return self._head_rows(rows, n) + (stats,)
+
+    def _head_rows(self, rows, n):
+        """l2_normalize, the prediction Dense and its softmax / sigmoid over the first n rows of `rows`."""
+        from . import inference as inf
         e = self.engine
         C = self.num_classes
-        rows, n = inf.select_rows(self, inf.layers_full(self, graph), nodes)
         y = inf._table(e, max(n, 1), rows.d)
         preds = inf._table(e, max(n, 1), C)
         ops.l2norm_fwd(rows, n, y, None, stream=e.stream)

@@ -65,7 +65,15 @@ def build_flags(argv=None):
     p.add_argument('--full_inference', type=b, nargs='?', const=True, default=False,
                    help='after training: exact layer-wise inference over every node\'s WHOLE neighbor list on the test graph '
                         '(predict_full) -> val_stats_full.txt / test_stats_full.txt; not for graphsage_seq')
+    add_embed_nodes_flag(p)
     return p.parse_args(argv)
+
+
+def add_embed_nodes_flag(p):
+    p.add_argument('--embed_nodes', default='',
+                   help='FILE with one ORIGINAL node id per line (the ids val.txt lists): after training, their exact embeddings '
+                        'from their receptive field alone on the test graph (embed_nodes) -> embed_nodes.npy / embed_nodes.txt '
+                        '(supervised: + embed_nodes_preds.npy); not for n2v / graphsage_seq')
 
 
 FLAGS = None
@@ -74,11 +82,66 @@ FLAGS = None
 def refuse_full_inference(flags):
     """--full_inference (and --rank_full / --topk_full, which rank the embed_full embeddings) has no meaning for the models
     without a full-neighborhood form: say so before any work is done."""
-    for flag in ("full_inference", "rank_full", "topk_full"):
+    for flag in ("full_inference", "rank_full", "topk_full", "embed_nodes"):
         if getattr(flags, flag, False) and flags.model in ('n2v', 'graphsage_seq'):
             raise SystemExit("--%s is not available with --model %s: %s" % (
                 flag, flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v'
                 else "an LSTM over a random permutation of a neighbor sample has no full-neighborhood form"))
+
+
+def read_embed_nodes(flags):
+    """The tokens of --embed_nodes FILE, one per non-empty line (None without the flag); a missing file is refused here, before
+    any work is done."""
+    path = getattr(flags, "embed_nodes", "")
+    if not path:
+        return None
+    if not os.path.isfile(path):
+        raise SystemExit("--embed_nodes %s: no such file" % path)
+    with open(path) as fp:
+        return [line.strip() for line in fp if line.strip()]
+
+
+def embed_nodes_rows(G, tokens, path):
+    """Rows of the ORIGINAL node ids `tokens` in G (through the id map, where the graph has one); an id that the graph does not
+    have is refused, before training."""
+    id_map = getattr(G, "id_map", None)
+    rows = []
+    for tok in tokens:
+        if id_map is not None:
+            row = id_map.get(tok)
+        else:
+            row = int(tok) if tok.lstrip("-").isdigit() and 0 <= int(tok) < G.n_nodes else None
+        if row is None:
+            raise SystemExit("--embed_nodes %s: the graph has no node %s" % (path, tok))
+        rows.append(row)
+    if not rows:
+        raise SystemExit("--embed_nodes %s: the file lists no node" % path)
+    return np.asarray(rows, dtype=np.int64)
+
+
+def embed_nodes_line(n, stats, duration):
+    """The line --embed_nodes prints."""
+    return "Receptive-field inference: nodes= %d rows= %s of %d edges= %d time= %.5f" % (
+        n, " / ".join(str(r) for r in stats["rows"]), stats["n_rows"], sum(stats["edges"]), duration)
+
+
+def save_embed_nodes(model, minibatch, n_nodes, rows, out_dir, supervised):
+    """embed_nodes.npy (+ embed_nodes_preds.npy): the exact embeddings of the rows `rows` from their receptive field on the test
+    graph, in the order of the file; embed_nodes.txt: their ORIGINAL ids, as val.txt lists them."""
+    graph = full_graph(minibatch, n_nodes)
+    t0 = time.time()
+    res = model.predict_nodes(graph, rows) if supervised else model.embed_nodes(graph, rows)
+    duration = time.time() - t0
+    print(embed_nodes_line(len(rows), res[-1], duration))
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    np.save(out_dir + "embed_nodes.npy", res[0])
+    if supervised:
+        np.save(out_dir + "embed_nodes_preds.npy", res[1])
+    ids = getattr(minibatch.G, "node_ids", None)
+    with open(out_dir + "embed_nodes.txt", "w") as fp:
+        fp.write("\n".join(str(ids[i] if ids is not None else i) for i in rows))
+    return res
 
 
 def refuse_dropout(flags):
@@ -217,7 +280,7 @@ def load_graph():
     return utils.load_data(FLAGS.train_prefix)
 
 
-def train(G):
+def train(G, embed_rows=None):
     from . import engine as eng
     from .minibatch import NodeMinibatchIterator
     from .models import SAGEInfo
@@ -379,6 +442,8 @@ def train(G):
         fp.write("loss={:.5f} f1_micro={:.5f} f1_macro={:.5f}".format(val_cost, val_f1_mic, val_f1_mac))
     if FLAGS.full_inference:
         full_inference_stats(model, minibatch, G.n_nodes)
+    if embed_rows is not None:
+        save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=True)
     return val_f1_mic
 
 
@@ -387,10 +452,11 @@ def main(argv=None):
     FLAGS = build_flags(argv)
     refuse_full_inference(FLAGS)
     refuse_dropout(FLAGS)
+    tokens = read_embed_nodes(FLAGS)
     print("Loading training data..")
     G = load_graph()
     print("Done loading training data..")
-    return train(G)
+    return train(G, embed_nodes_rows(G, tokens, FLAGS.embed_nodes) if tokens is not None else None)
 
 
 if __name__ == '__main__':

@@ -71,6 +71,8 @@ def build_flags(argv=None):
                    help='K > 0: after val.npy, the K best-scoring partners of every node among ALL nodes with the exact '
                         'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
                         'topk_full_scores.npy; not for n2v / graphsage_seq')
+    from .supervised_train import add_embed_nodes_flag
+    add_embed_nodes_flag(p)
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     p.add_argument('--walk_p', type=float, default=1.0,
                    help='return parameter p of node2vec\'s second-order walk (a step back to the previous node weighs 1/p)')
@@ -250,7 +252,7 @@ def construct_placeholders():
             'dropout': Placeholder('dropout', 0.), 'batch_size': Placeholder('batch_size')}
 
 
-def train(G, context_pairs):
+def train(G, context_pairs, embed_rows=None):
     from . import engine as eng
     from .minibatch import EdgeMinibatchIterator
     from .models import Node2VecModel, SAGEInfo, SampleAndAggregate
@@ -355,6 +357,9 @@ def train(G, context_pairs):
             save_full_topk(model, minibatch, log_dir(), FLAGS.topk_full)
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
+    if embed_rows is not None:
+        from .supervised_train import save_embed_nodes
+        save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=False)
     return shadow_mrr
 
 
@@ -408,6 +413,7 @@ def main(argv=None):
     st.refuse_full_inference(FLAGS)
     st.refuse_dropout(FLAGS)
     refuse_walk_flags(FLAGS)
+    tokens = st.read_embed_nodes(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)
     G = st.load_graph()
@@ -425,7 +431,7 @@ def main(argv=None):
                 pairs = utils.run_random_walks(rp, col, train_nodes, num_walks=FLAGS.num_walks, walk_len=FLAGS.walk_len,
                                                max_pairs=FLAGS.max_walk_pairs)
     print("Done loading training data..")
-    return train(G, pairs)
+    return train(G, pairs, st.embed_nodes_rows(G, tokens, FLAGS.embed_nodes) if tokens is not None else None)
 
 
 if __name__ == '__main__':

@@ -1053,6 +1053,58 @@ int gs_csr_reduce_ws_bytes(int64_t n_slots, int32_t d, int64_t* bytes_out_host);
 int gs_csr_reduce_fwd(const gs_csr_reduce_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * INF-ROWS  exact inference for a node SUBSET: the receptive field on the device, and the reduce over a row list.
+ *
+ *      gs_frontier_expand: rows_in is an ascending, duplicate-free int32 list [m] of rows in [0, n_rows) of the CSR;
+ *        rows_out = the ascending, duplicate-free list of rows_in U {col[e] : e in a row of rows_in}   (at most rows_out_cap)
+ *        pos[id]  = index of id in rows_out, -1 for every id in [0, n_rows) that is no member           (int32 [n_rows])
+ *        count[0] = the number of members                                                             (device word)
+ *      A flag array written with plain stores of one value, then a block count and a rank pass (the method of
+ *      gs_unique_ids): no atomics, no sort, a deterministic result.  One wave walks one input row, its edges spread over the
+ *      lanes.  ws = int32 [n_rows + 256] (gs_frontier_ws_bytes), 16-byte aligned; its first n_rows words must be ZERO on first
+ *      use and every call leaves them zero.  Entries of rows_in or col outside [0, n_rows) are skipped.
+ *
+ *      gs_csr_reduce_rows: the ops and the optional relu of gs_csr_reduce_fwd over the rows of a plan that covers a row subset
+ *      (items / splits as above, cut from the graph's plan in its order, partial slots re-based to 0 .. n_slots):
+ *        out[out_pos[r]] = reduce over e of X[x_pos[col[e]]]        (GS_CSR_MEAN_SELF: the self row is X[x_pos[r]])
+ *      x_pos, out_pos: int32 [n_rows] maps from node id to table row; x_pos == NULL means X is indexed by node id (then
+ *      x_rows >= n_rows).  The item loop and the combine are the code of gs_csr_reduce_fwd, so a row gets bit for bit the value
+ *      the window form gives it.  An id outside [0, n_rows) or a mapped position outside [0, x_rows) / [0, out_rows) makes the
+ *      wave give its item up: an uncut row is then not written (a cut row combines what its partial slot held), and nothing
+ *      outside the tables is touched.
+ *      gs_frontier_desc is 96 and gs_csr_rows_desc 168 bytes on every target (checked at compile time and by the binding;
+ *      passed by pointer, not part of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gs_frontier_desc {
+    const int64_t* rowptr;     /* device [n_rows + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const int32_t* rows_in;    /* device [m]; nullable when m == 0 */
+    int32_t* rows_out;         /* device [rows_out_cap] */
+    int32_t* pos;              /* device [n_rows] */
+    int32_t* count;            /* device [1] */
+    int32_t* ws;               /* device [n_rows + 256] */
+    int64_t n_rows, nnz, m, rows_out_cap, ws_bytes;
+} gs_frontier_desc;
+int gs_frontier_ws_bytes(int64_t n_rows, int64_t* bytes_out_host);
+int gs_frontier_expand(const gs_frontier_desc* desc_host, void* stream);
+
+typedef struct gs_csr_rows_desc {
+    const int64_t* rowptr;     /* device [n_rows + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const int64_t* items;      /* device [n_items][4] */
+    const int64_t* splits;     /* device [n_split][3]; nullable when n_split == 0 */
+    const int32_t* x_pos;      /* device [n_rows]; NULL: X is indexed by node id */
+    const int32_t* out_pos;    /* device [n_rows] */
+    const float* X;            /* [x_rows, ldx] */
+    float* out;                /* [out_rows, ldo] */
+    float* ws;                 /* partials of the list's long rows; nullable when it has none */
+    int64_t n_rows, nnz, n_items, n_split, n_slots;
+    int64_t ldx, x_rows, ldo, out_rows, ws_bytes;
+    int32_t d, op, act, split_len;
+} gs_csr_rows_desc;
+int gs_csr_reduce_rows(const gs_csr_rows_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * RANK link ranking against every node: a contraction with a compare-and-count epilogue; no score is written to memory.
  *        t[q]    = <Xq[q], Zc[dst[q]]>                                   (fp32 on the matrix cores, fp32 operands)
  *        n_gt[q] = #{w in C_q : <Xq[q], Zc[w]> >  t[q]}
