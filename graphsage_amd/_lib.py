@@ -180,6 +180,8 @@ _PROTOS = {
     "gs_topk_select": [_P, _P],
     "gs_walk_paths": [_P, _P],
     "gs_walk_pairs": [_P, _P],
+    "gs_logreg_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
+    "gs_logreg_eval": [_P, _P],
 }
 
 
@@ -354,6 +356,21 @@ WALK_TAG = 0xA7 << 56                       # GS_WALK_TAG
 WALK_ATTEMPTS = 256                         # GS_WALK_ATTEMPTS
 WALK_MAX_LEN = 4096                         # GS_WALK_MAX_LEN
 assert ctypes.sizeof(WalkDesc) == 152      # static_assert in csrc/gs_walk.hip (passed by pointer, as RankDesc)
+
+
+class LogregDesc(ctypes.Structure):
+    """struct gs_logreg_desc (include/graphsage_amd.h)"""
+    _fields_ = [("X", c_void_p), ("rows", c_void_p), ("W", c_void_p), ("b", c_void_p), ("y_class", c_void_p),
+                ("y_multi", c_void_p), ("loss", c_void_p), ("gW", c_void_p), ("gb", c_void_p), ("pred_class", c_void_p),
+                ("pred_multi", c_void_p), ("ws", c_void_p),
+                ("n", c_int64), ("n_rows", c_int64), ("ldx", c_int64), ("ldw", c_int64), ("ldy", c_int64), ("ldp", c_int64),
+                ("ws_bytes", c_int64),
+                ("d", c_int32), ("c", c_int32), ("mode", c_int32), ("flags", c_int32)]
+
+
+LOGREG_FIT, LOGREG_PREDICT = 0, 1           # GS_LOGREG_FIT, GS_LOGREG_PREDICT (gs_logreg_desc.mode)
+LOGREG_MAX_D, LOGREG_MAX_C = 512, 128       # GS_LOGREG_MAX_D, GS_LOGREG_MAX_C
+assert ctypes.sizeof(LogregDesc) == 168    # static_assert in csrc/gs_logreg.hip (passed by pointer, as RankDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -1056,6 +1056,61 @@ def sumsq_scaled(x, count, scale, out, accumulate=False, stream=None):
     call("gs_sumsq_scaled", ptr(x), count, scale, ptr(out), 1 if accumulate else 0, _s(stream))
 
 
+# ------------------------------------------------------------------------------------------ LOGREG (gs_logreg.hip)
+LOGREG_FIT, LOGREG_PREDICT = _lib.LOGREG_FIT, _lib.LOGREG_PREDICT
+LOGREG_MAX_D, LOGREG_MAX_C = _lib.LOGREG_MAX_D, _lib.LOGREG_MAX_C
+
+
+def logreg_ws_bytes(n, d, c):
+    """Bytes of the fp32 workspace gs_logreg_eval needs for n rows of width d and c classes."""
+    out = ctypes.c_int64(0)
+    call("gs_logreg_ws_bytes", n, d, c, ctypes.byref(out))
+    return out.value
+
+
+def logreg_eval(X, W, b, n=None, rows=None, y_class=None, y_multi=None, mode=LOGREG_FIT, loss=None, gW=None, gb=None,
+                pred_class=None, pred_multi=None, ws=None, stream=None):
+    """gs_logreg_eval: one evaluation of the one-vs-rest logistic regression z = X[rows] W + b on the device.
+    X: Mat [n_rows, d]; W: Mat [d, c]; b: float32 [c]; rows: int32 [n] with entries in [0, X.rows) (checked by the caller) or
+    None (rows 0 .. n-1); y_class: int32 [n] in [0, c) or y_multi: uint8 [n, >= c].
+    LOGREG_FIT returns (loss [c], gW [d, c], gb [c]) as float64 SUMS over the rows (no mean, no regulariser).
+    LOGREG_PREDICT writes the given pred_class (int32 [n]) / pred_multi (uint8 [n, >= c]) and, with labels and `loss`, loss."""
+    d, c = X.d, W.d
+    n = (rows.numel() if rows is not None else X.rows) if n is None else int(n)
+    if W.rows != d or b.numel() != c or b.dtype != torch.float32:
+        raise _lib.GraphsageAmdError("logreg_eval: X is [%d, %d], W [%d, %d], b has %d entries" % (X.rows, d, W.rows, c, b.numel()))
+    if rows is not None and (rows.dtype != torch.int32 or rows.numel() != n):
+        raise _lib.GraphsageAmdError("logreg_eval: rows must be an int32 vector of n=%d entries" % n)
+    if y_class is not None and (y_class.dtype != torch.int32 or y_class.numel() != n):
+        raise _lib.GraphsageAmdError("logreg_eval: y_class must be an int32 vector of n=%d entries" % n)
+    for name, m in (("y_multi", y_multi), ("pred_multi", pred_multi)):
+        if m is not None and (m.dtype != torch.uint8 or m.dim() != 2 or m.shape[0] != n or m.shape[1] < c or m.stride(1) != 1):
+            raise _lib.GraphsageAmdError("logreg_eval: %s must be a uint8 matrix [n=%d, >= c=%d]" % (name, n, c))
+    if pred_class is not None and (pred_class.dtype != torch.int32 or pred_class.numel() != n):
+        raise _lib.GraphsageAmdError("logreg_eval: pred_class must be an int32 vector of n=%d entries" % n)
+    dev = X.buf.device
+    fit = mode == LOGREG_FIT
+    if fit:
+        loss = torch.empty(c, dtype=torch.float64, device=dev) if loss is None else loss
+        gW = torch.empty((d, c), dtype=torch.float64, device=dev) if gW is None else gW
+        gb = torch.empty(c, dtype=torch.float64, device=dev) if gb is None else gb
+    for name, t, numel in (("loss", loss, c), ("gW", gW, d * c), ("gb", gb, c)):
+        if t is not None and (t.dtype != torch.float64 or t.numel() != numel or not t.is_contiguous()):
+            raise _lib.GraphsageAmdError("logreg_eval: %s must be a dense float64 array of %d entries" % (name, numel))
+    if loss is not None and ws is None:
+        ws = torch.empty(max(logreg_ws_bytes(n, d, c) // 4, 2), dtype=torch.float32, device=dev)
+    q = _lib.LogregDesc()
+    q.X, q.rows, q.W, q.b, q.y_class, q.y_multi = X.ptr, ptr(rows), W.ptr, ptr(b), ptr(y_class), ptr(y_multi)
+    q.loss, q.gW, q.gb, q.pred_class, q.pred_multi, q.ws = ptr(loss), ptr(gW), ptr(gb), ptr(pred_class), ptr(pred_multi), ptr(ws)
+    q.n, q.n_rows, q.ldx, q.ldw = n, X.rows, X.ld, W.ld
+    q.ldy = y_multi.stride(0) if y_multi is not None else 0
+    q.ldp = pred_multi.stride(0) if pred_multi is not None else 0
+    q.ws_bytes = 4 * ws.numel() if ws is not None else 0
+    q.d, q.c, q.mode, q.flags = d, c, mode, 0
+    call("gs_logreg_eval", ctypes.addressof(q), _s(stream))
+    return (loss, gW, gb) if fit else (pred_class, pred_multi, loss)
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

@@ -73,6 +73,10 @@ def build_flags(argv=None):
                         'topk_full_scores.npy; not for n2v / graphsage_seq')
     from .supervised_train import add_embed_nodes_flag
     add_embed_nodes_flag(p)
+    p.add_argument('--eval_classifier', default='', choices=['', 'val', 'test'],
+                   help='val | test: after val.npy, fit a logistic regression on the train nodes\' embeddings on the device and '
+                        'score it on that split (the reference\'s eval_scripts; with --full_inference on val_full.npy, with '
+                        '--model n2v the scored rows come from val-test.npy) -> eval_classifier.txt')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     p.add_argument('--walk_p', type=float, default=1.0,
                    help='return parameter p of node2vec\'s second-order walk (a step back to the previous node weighs 1/p)')
@@ -103,6 +107,35 @@ def refuse_walk_flags(flags):
         walk_thresholds(flags.walk_p, flags.walk_q)
     except ValueError as e:
         raise SystemExit("--walk_p / --walk_q: %s" % e)
+
+
+def embedding_width(flags):
+    """Columns of val.npy: 2 * dim_2 (concat; gcn doubles its dims instead), 2 * dim_1 for the node2vec table."""
+    return 2 * (flags.dim_1 if flags.model == 'n2v' else flags.dim_2)
+
+
+def refuse_eval_classifier(flags, G=None):
+    """--eval_classifier needs the saved embeddings, a width the classifier kernel takes and (once the graph is loaded) class
+    labels in its range: anything else is refused before training, with the rule in the message."""
+    if not getattr(flags, "eval_classifier", ""):
+        return
+    from . import evaluation
+    if not flags.save_embeddings:
+        raise SystemExit("--eval_classifier reads val.npy: it needs --save_embeddings true")
+    try:
+        evaluation.refuse(embedding_width(flags), n_classes=1)
+    except ValueError as e:
+        raise SystemExit("--eval_classifier: %s" % e)
+    if G is not None:
+        evaluation.refuse_graph(G)
+
+
+def save_eval_classifier(G, out_dir):
+    """eval_classifier.txt: the `Downstream classifier:` line for the table that was just written."""
+    from . import engine as eng
+    from . import evaluation
+    return evaluation.evaluate_embedding_dir(eng.get_engine(), G, out_dir, FLAGS.eval_classifier,
+                                             base="val_full" if FLAGS.full_inference else "val")
 
 
 def device_walks(rowptr, col, nodes, max_pairs=None):
@@ -357,6 +390,8 @@ def train(G, context_pairs, embed_rows=None):
             save_full_topk(model, minibatch, log_dir(), FLAGS.topk_full)
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
+        if FLAGS.eval_classifier:
+            save_eval_classifier(G, log_dir())
     if embed_rows is not None:
         from .supervised_train import save_embed_nodes
         save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=False)
@@ -413,10 +448,12 @@ def main(argv=None):
     st.refuse_full_inference(FLAGS)
     st.refuse_dropout(FLAGS)
     refuse_walk_flags(FLAGS)
+    refuse_eval_classifier(FLAGS)
     tokens = st.read_embed_nodes(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)
     G = st.load_graph()
+    refuse_eval_classifier(FLAGS, G)
     pairs = None
     if FLAGS.random_context:
         walks = FLAGS.train_prefix + "-walks.txt"

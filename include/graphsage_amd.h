@@ -38,7 +38,7 @@ extern "C" {
 #define GS_ACT_IDENTITY 0
 #define GS_ACT_RELU 1
 
-/* bumped when a struct layout or an existing signature changes; added entry points alone (gs_pool2_*) leave it as it is */
+/* bumped when a struct layout or an existing signature changes; added entry points alone (gs_pool2_*, gs_logreg_*) leave it as it is */
 #define GS_ABI_VERSION 12
 
 const char* gs_last_error(void);
@@ -1219,6 +1219,53 @@ typedef struct gs_walk_desc {
 } gs_walk_desc;
 int gs_walk_paths(const gs_walk_desc* desc_host, void* stream);
 int gs_walk_pairs(const gs_walk_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * LOGREG one loss-and-gradient evaluation of a one-vs-rest logistic regression on rows of an embedding table (the downstream
+ *      node classification of eval_scripts/: SGDClassifier(loss="log") per class; csrc/gs_logreg.hip).  With
+ *        z[i][k] = <X[rows[i]], W[:, k]> + b[k]   (fp32 on the matrix cores),   s[i][k] = +1 / -1,   m = s z
+ *      where s comes from y_class (int32 [n] in [0, c): +1 for the row's class, -1 for every other class) or from y_multi
+ *      (uint8 [n][ldy]: +1 where the entry is non-zero):
+ *      GS_LOGREG_FIT writes three fp64 arrays -- sums over the rows, NOT means, and without any regulariser:
+ *        loss[k]  = sum_i max(-m, 0) + log1p(exp(-|m|))            (= log(1 + exp(-m)), safe at both ends)
+ *        gb[k]    = sum_i r[i][k],   r = -s sigma(-m)
+ *        gW[j][k] = sum_i X[rows[i]][j] r[i][k]                    (dense [d][c])
+ *      GS_LOGREG_PREDICT forms the logits only and writes, where the pointer is given, pred_class[i] = argmax_k z[i][k]
+ *      (int32 [n], the lowest class id on an exact tie), pred_multi[i][k] = z[i][k] > 0 (uint8 [n][ldp]) and, if labels are
+ *      given too, loss.  gW, gb (PREDICT) and pred_* (FIT) must be null.
+ *      rows is nullable (rows 0 .. n-1 of X); entries may repeat and must lie in [0, n_rows) (the caller checks them once).
+ *      Exactly one label form in FIT mode; none or one in PREDICT mode.  d % 4 == 0, 4 <= d <= GS_LOGREG_MAX_D,
+ *      1 <= c <= GS_LOGREG_MAX_C, n >= 1, ldx >= d (ldx % 4 == 0, X 16-byte aligned), ldw, ldy, ldp >= c; anything else is
+ *      refused with a message and no launch.
+ *      A workgroup owns a contiguous run of 32-row tiles, keeps the gathered tile in LDS for both contractions and writes one
+ *      fp32 partial; a second launch adds the partials in workgroup order in fp64.  No n x c array exists in memory, no
+ *      atomics: bitwise repeatable.  gs_logreg_ws_bytes(n, d, c) = wgs * (2 c + d c) * 4 with tiles = ceil(n / 32),
+ *      wgs = ceil(tiles / ceil(tiles / 512)); the workspace is needed whenever loss is written.
+ *      gs_logreg_desc is 168 bytes on every target (checked at compile time and by the binding; passed by pointer, not part
+ *      of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_LOGREG_FIT 0
+#define GS_LOGREG_PREDICT 1
+#define GS_LOGREG_MAX_D 512
+#define GS_LOGREG_MAX_C 128
+typedef struct gs_logreg_desc {
+    const float* X;            /* device [n_rows][ldx] embedding table */
+    const int32_t* rows;       /* device [n] rows of X; nullable (0 .. n-1) */
+    const float* W;            /* device [d][ldw] */
+    const float* b;            /* device [c] */
+    const int32_t* y_class;    /* device [n]; nullable */
+    const uint8_t* y_multi;    /* device [n][ldy]; nullable */
+    double* loss;              /* device [c]; FIT: required, PREDICT: nullable (needs labels) */
+    double* gW;                /* device [d][c]; FIT only */
+    double* gb;                /* device [c]; FIT only */
+    int32_t* pred_class;       /* device [n]; PREDICT only, nullable */
+    uint8_t* pred_multi;       /* device [n][ldp]; PREDICT only, nullable */
+    void* ws;                  /* device, 8-byte aligned, ws_bytes >= gs_logreg_ws_bytes(n, d, c); needed with loss */
+    int64_t n, n_rows, ldx, ldw, ldy, ldp, ws_bytes;
+    int32_t d, c, mode, flags; /* mode: GS_LOGREG_FIT | GS_LOGREG_PREDICT; flags: 0 */
+} gs_logreg_desc;
+int gs_logreg_ws_bytes(int64_t n, int32_t d, int32_t c, int64_t* bytes_out_host);
+int gs_logreg_eval(const gs_logreg_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
