@@ -15,6 +15,13 @@ linear model.  Prints one JSON line (and writes it to --out):
   * "fit": evaluation.fit_classifier on the whole shape: evaluations, stop reason, seconds.
   * "sklearn": SGDClassifier(loss="log_loss") (one-vs-rest; MultiOutputClassifier for multi-label) on the first --fit_rows
     train rows on the CPU, and fit_classifier on the same rows, when scikit-learn imports; else null.
+
+    python benchmarks/bench_eval.py --joined all [--chunked_lib benchmarks/variants/_lib/libgs_logreg_chunked.so]
+
+measures the joined inputs instead (gs_logreg_eval_joined, profiles/eval_classifier_features.md), all at the Reddit shape:
+d256 = the embeddings alone through gs_logreg_eval and gs_logreg_eval_joined in one process (alternating regions),
+features = 604 standardised feature columns, both = 604 + 256, d1024 = 604 + 420; each next to the eager restatement
+(materialised hstack, standardise, two matmuls), gs_col_moments, and with --chunked_lib the column-chunked form of the kernel.
 """
 import argparse
 import json
@@ -132,16 +139,140 @@ def bench_shape(name, shape, args, dev):
     return res
 
 
+# (da, db) of the joined inputs at the Reddit shape: the embeddings alone through both entry points, the 602 feature columns
+# (604 padded), features + embeddings, and the widest row the kernel takes
+JOINED = {"d256": (256, 0), "features": (604, 0), "both": (604, 256), "d1024": (604, 420)}
+
+
+def bench_joined(name, da, db, args, dev, chunked=None):
+    """One FIT evaluation of gs_logreg_eval_joined on standardised [A | B] rows at the Reddit shape (153,431 of 232,965 rows,
+    41 classes), next to gs_logreg_eval where the shape allows it (d256: one table, no scaler -- the same arithmetic), the
+    column-chunked build (--chunked_lib) and an eager restatement (materialised hstack, standardise, two matmuls)."""
+    import ctypes
+    from graphsage_amd import _lib, ops
+    shape = SHAPES["reddit"]
+    N, n, c = shape["N"], shape["n"], shape["c"]
+    d = da + db
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    A = torch.randn(N, da, device=dev, generator=g)
+    plain = db == 0 and d <= ops.LOGREG_MAX_D
+    if plain:
+        A /= A.norm(dim=1, keepdim=True)                        # an embedding table: unit rows, no scaler
+    else:
+        A = A * torch.exp(torch.rand(da, device=dev, generator=g) * 5.0 - 1.6) + (torch.rand(da, device=dev, generator=g) - 0.5) * 100
+    B = None
+    if db:
+        B = torch.randn(N, db, device=dev, generator=g)
+        B /= B.norm(dim=1, keepdim=True)
+    Xa, Xb = ops.Mat(A, da), (ops.Mat(B, db) if db else None)
+    rows_a = torch.randperm(N, device=dev, generator=g)[:n].to(torch.int32)
+    rows_b = torch.randperm(N, device=dev, generator=g)[:n].to(torch.int32) if db else None
+    y = torch.randint(0, c, (n,), device=dev, generator=g).to(torch.int32)
+    W = ops.Mat(torch.randn(d, ops.round_up(c, 4), device=dev, generator=g) / d ** 0.5, c)
+    b = torch.zeros(c, device=dev)
+    mu = inv = None
+    res = {"n": n, "da": da, "db": db, "c": c}
+    if not plain:
+        t0 = time.time()
+        mean, var = ops.col_moments(Xa, Xb=Xb, n=n, rows_a=rows_a, rows_b=rows_b)
+        torch.cuda.synchronize()
+        res["col_moments_first_call_s"] = time.time() - t0
+        res["col_moments"] = regions(lambda: ops.col_moments(Xa, Xb=Xb, n=n, rows_a=rows_a, rows_b=rows_b, mean=mean, var=var), 2)
+        scale = torch.where(var == 0, torch.ones_like(var), var.sqrt())
+        mu, inv = mean.float().contiguous(), (1.0 / scale).float().contiguous()
+    loss = torch.zeros(c, dtype=torch.float64, device=dev)
+    gW = torch.zeros((d, c), dtype=torch.float64, device=dev)
+    gb = torch.zeros(c, dtype=torch.float64, device=dev)
+    ws = torch.empty(ops.logreg_joined_ws_bytes(n, d, c) // 4, dtype=torch.float32, device=dev)
+
+    def joined():
+        ops.logreg_eval_joined(Xa, W, b, Xb=Xb, n=n, rows_a=rows_a, rows_b=rows_b, mu=mu, inv=inv, y_class=y, loss=loss, gW=gW,
+                               gb=gb, ws=ws)
+
+    joined()
+    torch.cuda.synchronize()
+    want = [t.clone() for t in (loss, gW, gb)]
+    res["joined"] = regions(joined, args.reps)
+    res["joined"]["tflops"] = 4.0 * n * d * c / (res["joined"]["ms"] * 1e-3) / 1e12
+    res["joined"]["row_gbytes_per_s"] = 4.0 * n * d / (res["joined"]["ms"] * 1e-3) / 1e9
+    if plain:
+        def single():
+            ops.logreg_eval(Xa, W, b, n=n, rows=rows_a, y_class=y, loss=loss, gW=gW, gb=gb, ws=ws)
+        single()
+        torch.cuda.synchronize()
+        res["bit_equal_to_logreg_eval"] = all(torch.equal(a, b_) for a, b_ in zip(want, (loss, gW, gb)))
+        # alternate the two entry points: the run-to-run spread of each is visible next to their difference
+        res["logreg_eval"], res["joined_again"] = regions(single, args.reps), regions(joined, args.reps)
+        res["logreg_eval_again"] = regions(single, args.reps)
+    if chunked is not None:
+        q = _lib.LogregJoinedDesc()
+        q.Xa, q.rows_a, q.lda, q.n_rows_a, q.da = Xa.ptr, rows_a.data_ptr(), Xa.ld, Xa.rows, da
+        if db:
+            q.Xb, q.rows_b, q.ldb, q.n_rows_b, q.db = Xb.ptr, rows_b.data_ptr(), Xb.ld, Xb.rows, db
+        if mu is not None:
+            q.mu, q.inv = mu.data_ptr(), inv.data_ptr()
+        q.W, q.b, q.y_class, q.loss, q.gW, q.gb, q.ws = W.ptr, b.data_ptr(), y.data_ptr(), loss.data_ptr(), gW.data_ptr(), \
+            gb.data_ptr(), ws.data_ptr()
+        q.n, q.ldw, q.ws_bytes, q.c, q.mode = n, W.ld, 4 * ws.numel(), c, ops.LOGREG_FIT
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+        def chunk():
+            rc = chunked.gs_logreg_eval_joined_chunked(ctypes.addressof(q), stream)
+            assert rc == 0, rc
+
+        for t in (loss, gW, gb):
+            t.zero_()
+        chunk()
+        torch.cuda.synchronize()
+        res["chunked_bit_equal"] = all(torch.equal(a, b_) for a, b_ in zip(want, (loss, gW, gb)))
+        res["chunked"], res["joined_after_chunked"] = regions(chunk, args.reps), regions(joined, args.reps)
+    S = torch.nn.functional.one_hot(y.long(), c).float() * 2 - 1
+    ra, rb, Wv = rows_a.long(), (rows_b.long() if db else None), W.view()
+    out = {}
+
+    def eager():
+        Xg = torch.hstack([A[ra], B[rb]]) if db else A[ra]
+        if mu is not None:
+            Xg = (Xg - mu) * inv
+        M = S * (Xg @ Wv + b)
+        out["loss"] = torch.nn.functional.softplus(-M).sum(0)
+        R = -S * torch.sigmoid(-M)
+        out["gW"], out["gb"] = Xg.t() @ R, R.sum(0)
+
+    eager()
+    torch.cuda.synchronize()
+    res["max_rel_diff_gW"] = float((want[1].float() - out["gW"]).abs().max() / max(1.0, float(want[1].abs().max())))
+    res["torch"] = regions(eager, max(2, args.reps // 2))
+    res["speedup_vs_torch"] = res["torch"]["ms"] / res["joined"]["ms"]
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="reddit,ppi")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--fit_rows", type=int, default=20000)
     ap.add_argument("--out", default="")
+    ap.add_argument("--joined", default="", help="comma list of %s (or 'all'): the joined-input measurements instead of --shapes"
+                    % ",".join(JOINED))
+    ap.add_argument("--chunked_lib", default="", help="library built by benchmarks/variants/build_logreg_chunked.sh: the "
+                    "column-chunked form of the joined kernel is timed next to the library's")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "bench_eval.py needs the GPU"
     dev = torch.device("cuda:0")
-    res = {name: bench_shape(name, SHAPES[name], args, dev) for name in args.shapes.split(",")}
+    if args.joined:
+        import ctypes
+        from graphsage_amd import _lib
+        _lib.load()                                  # torch's HIP runtime first, then the product library, then the variant
+        chunked = ctypes.CDLL(args.chunked_lib) if args.chunked_lib else None
+        if chunked is not None:                      # without argtypes ctypes passes a Python int as a C int: half an address
+            chunked.gs_logreg_eval_joined_chunked.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            chunked.gs_logreg_eval_joined_chunked.restype = ctypes.c_int
+        names = list(JOINED) if args.joined == "all" else args.joined.split(",")
+        res = {name: bench_joined(name, JOINED[name][0], JOINED[name][1], args, dev, chunked) for name in names}
+    else:
+        res = {name: bench_shape(name, SHAPES[name], args, dev) for name in args.shapes.split(",")}
     line = json.dumps(res)
     print(line)
     if args.out:

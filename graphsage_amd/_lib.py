@@ -182,6 +182,9 @@ _PROTOS = {
     "gs_walk_pairs": [_P, _P],
     "gs_logreg_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
     "gs_logreg_eval": [_P, _P],
+    "gs_logreg_joined_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
+    "gs_logreg_eval_joined": [_P, _P],
+    "gs_col_moments": [_P, _P, c_int64, c_int32, c_int64, _P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P, c_int64, _P],
 }
 
 
@@ -371,6 +374,22 @@ class LogregDesc(ctypes.Structure):
 LOGREG_FIT, LOGREG_PREDICT = 0, 1           # GS_LOGREG_FIT, GS_LOGREG_PREDICT (gs_logreg_desc.mode)
 LOGREG_MAX_D, LOGREG_MAX_C = 512, 128       # GS_LOGREG_MAX_D, GS_LOGREG_MAX_C
 assert ctypes.sizeof(LogregDesc) == 168    # static_assert in csrc/gs_logreg.hip (passed by pointer, as RankDesc)
+
+
+class LogregJoinedDesc(ctypes.Structure):
+    """struct gs_logreg_joined_desc (include/graphsage_amd.h)"""
+    _fields_ = [("Xa", c_void_p), ("rows_a", c_void_p), ("Xb", c_void_p), ("rows_b", c_void_p), ("mu", c_void_p),
+                ("inv", c_void_p), ("W", c_void_p), ("b", c_void_p), ("y_class", c_void_p), ("y_multi", c_void_p),
+                ("loss", c_void_p), ("gW", c_void_p), ("gb", c_void_p), ("pred_class", c_void_p), ("pred_multi", c_void_p),
+                ("ws", c_void_p),
+                ("n", c_int64), ("n_rows_a", c_int64), ("lda", c_int64), ("n_rows_b", c_int64), ("ldb", c_int64),
+                ("ldw", c_int64), ("ldy", c_int64), ("ldp", c_int64), ("ws_bytes", c_int64),
+                ("da", c_int32), ("db", c_int32), ("c", c_int32), ("mode", c_int32), ("flags", c_int32), ("reserved_", c_int32)]
+
+
+LOGREG_JOINED_MAX_D = 1024                  # GS_LOGREG_JOINED_MAX_D
+COL_MOMENTS_MAX_CHUNKS = 256                # GS_COL_MOMENTS_MAX_CHUNKS
+assert ctypes.sizeof(LogregJoinedDesc) == 224    # static_assert in csrc/gs_logreg.hip (passed by pointer, as LogregDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -1111,6 +1111,92 @@ def logreg_eval(X, W, b, n=None, rows=None, y_class=None, y_multi=None, mode=LOG
     return (loss, gW, gb) if fit else (pred_class, pred_multi, loss)
 
 
+LOGREG_JOINED_MAX_D = _lib.LOGREG_JOINED_MAX_D
+
+
+def logreg_joined_ws_bytes(n, d, c):
+    """Bytes of the fp32 workspace gs_logreg_eval_joined needs for n rows of joined width d and c classes."""
+    out = ctypes.c_int64(0)
+    call("gs_logreg_joined_ws_bytes", n, d, c, ctypes.byref(out))
+    return out.value
+
+
+def _joined_sources(who, Xa, rows_a, Xb, rows_b, n):
+    """(n, da, db) of a joined problem after the checks a pointer cannot carry."""
+    n = (rows_a.numel() if rows_a is not None else (rows_b.numel() if rows_b is not None else Xa.rows)) if n is None else int(n)
+    if Xb is None and rows_b is not None:
+        raise _lib.GraphsageAmdError("%s: rows_b without Xb" % who)
+    for name, r in (("rows_a", rows_a), ("rows_b", rows_b)):
+        if r is not None and (r.dtype != torch.int32 or r.numel() != n):
+            raise _lib.GraphsageAmdError("%s: %s must be an int32 vector of n=%d entries" % (who, name, n))
+    return n, Xa.d, (Xb.d if Xb is not None else 0)
+
+
+def logreg_eval_joined(Xa, W, b, Xb=None, n=None, rows_a=None, rows_b=None, mu=None, inv=None, y_class=None, y_multi=None,
+                       mode=LOGREG_FIT, loss=None, gW=None, gb=None, pred_class=None, pred_multi=None, ws=None, stream=None):
+    """gs_logreg_eval_joined: logreg_eval on rows joined from two tables and standardised while they are staged,
+    x[i] = ([Xa[rows_a[i]] | Xb[rows_b[i]]] - mu) * inv.  Xa: Mat [*, da]; Xb: Mat [*, db] or None; W: Mat [da + db, c];
+    mu, inv: float32 [da + db], both or neither; the rest as logreg_eval.  da + db <= LOGREG_JOINED_MAX_D."""
+    n, da, db = _joined_sources("logreg_eval_joined", Xa, rows_a, Xb, rows_b, n)
+    d, c = da + db, W.d
+    if W.rows != d or b.numel() != c or b.dtype != torch.float32:
+        raise _lib.GraphsageAmdError("logreg_eval_joined: the joined width is %d + %d, W [%d, %d], b has %d entries" % (
+            da, db, W.rows, c, b.numel()))
+    for name, t in (("mu", mu), ("inv", inv)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != d or not t.is_contiguous()):
+            raise _lib.GraphsageAmdError("logreg_eval_joined: %s must be a dense float32 vector of d=%d entries" % (name, d))
+    if y_class is not None and (y_class.dtype != torch.int32 or y_class.numel() != n):
+        raise _lib.GraphsageAmdError("logreg_eval_joined: y_class must be an int32 vector of n=%d entries" % n)
+    for name, m in (("y_multi", y_multi), ("pred_multi", pred_multi)):
+        if m is not None and (m.dtype != torch.uint8 or m.dim() != 2 or m.shape[0] != n or m.shape[1] < c or m.stride(1) != 1):
+            raise _lib.GraphsageAmdError("logreg_eval_joined: %s must be a uint8 matrix [n=%d, >= c=%d]" % (name, n, c))
+    if pred_class is not None and (pred_class.dtype != torch.int32 or pred_class.numel() != n):
+        raise _lib.GraphsageAmdError("logreg_eval_joined: pred_class must be an int32 vector of n=%d entries" % n)
+    dev = Xa.buf.device
+    fit = mode == LOGREG_FIT
+    if fit:
+        loss = torch.empty(c, dtype=torch.float64, device=dev) if loss is None else loss
+        gW = torch.empty((d, c), dtype=torch.float64, device=dev) if gW is None else gW
+        gb = torch.empty(c, dtype=torch.float64, device=dev) if gb is None else gb
+    for name, t, numel in (("loss", loss, c), ("gW", gW, d * c), ("gb", gb, c)):
+        if t is not None and (t.dtype != torch.float64 or t.numel() != numel or not t.is_contiguous()):
+            raise _lib.GraphsageAmdError("logreg_eval_joined: %s must be a dense float64 array of %d entries" % (name, numel))
+    if loss is not None and ws is None:
+        ws = torch.empty(max(logreg_joined_ws_bytes(n, d, c) // 4, 2), dtype=torch.float32, device=dev)
+    q = _lib.LogregJoinedDesc()
+    q.Xa, q.rows_a, q.lda, q.n_rows_a, q.da = Xa.ptr, ptr(rows_a), Xa.ld, Xa.rows, da
+    if Xb is not None:
+        q.Xb, q.rows_b, q.ldb, q.n_rows_b, q.db = Xb.ptr, ptr(rows_b), Xb.ld, Xb.rows, db
+    q.mu, q.inv, q.W, q.b, q.y_class, q.y_multi = ptr(mu), ptr(inv), W.ptr, ptr(b), ptr(y_class), ptr(y_multi)
+    q.loss, q.gW, q.gb, q.pred_class, q.pred_multi, q.ws = ptr(loss), ptr(gW), ptr(gb), ptr(pred_class), ptr(pred_multi), ptr(ws)
+    q.n, q.ldw = n, W.ld
+    q.ldy = y_multi.stride(0) if y_multi is not None else 0
+    q.ldp = pred_multi.stride(0) if pred_multi is not None else 0
+    q.ws_bytes = 4 * ws.numel() if ws is not None else 0
+    q.c, q.mode, q.flags = c, mode, 0
+    call("gs_logreg_eval_joined", ctypes.addressof(q), _s(stream))
+    return (loss, gW, gb) if fit else (pred_class, pred_multi, loss)
+
+
+def col_moments(Xa, Xb=None, n=None, rows_a=None, rows_b=None, mean=None, var=None, ws=None, stream=None):
+    """gs_col_moments: (mean, var) float64 [da + db] of the joined rows [Xa[rows_a[i]] | Xb[rows_b[i]]], i < n: the column
+    means and the POPULATION variances, centred, in a fixed order (bitwise repeatable; a constant column has var == 0.0)."""
+    n, da, db = _joined_sources("col_moments", Xa, rows_a, Xb, rows_b, n)
+    d = da + db
+    dev = Xa.buf.device
+    mean = torch.empty(d, dtype=torch.float64, device=dev) if mean is None else mean
+    var = torch.empty(d, dtype=torch.float64, device=dev) if var is None else var
+    for name, t in (("mean", mean), ("var", var)):
+        if t.dtype != torch.float64 or t.numel() != d or not t.is_contiguous():
+            raise _lib.GraphsageAmdError("col_moments: %s must be a dense float64 vector of d=%d entries" % (name, d))
+    if ws is None:
+        ws = torch.empty(_lib.COL_MOMENTS_MAX_CHUNKS * d, dtype=torch.float64, device=dev)
+    call("gs_col_moments", Xa.ptr, ptr(rows_a), Xa.ld, da, Xa.rows, Xb.ptr if Xb is not None else None, ptr(rows_b),
+         Xb.ld if Xb is not None else 0, db, Xb.rows if Xb is not None else 0, n, ptr(mean), ptr(var), ptr(ws),
+         ws.numel() * ws.element_size(), _s(stream))
+    return mean, var
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

@@ -77,6 +77,10 @@ def build_flags(argv=None):
                    help='val | test: after val.npy, fit a logistic regression on the train nodes\' embeddings on the device and '
                         'score it on that split (the reference\'s eval_scripts; with --full_inference on val_full.npy, with '
                         '--model n2v the scored rows come from val-test.npy) -> eval_classifier.txt')
+    p.add_argument('--eval_classifier_inputs', default='embeddings', choices=['embeddings', 'features', 'both', 'all'],
+                   help='with --eval_classifier: besides the embeddings line, the same classifier on the feature table the model '
+                        'trained on (features -> eval_classifier_features.txt), on [features | embeddings] (both -> '
+                        'eval_classifier_both.txt), or the two of them (all); these rows are standardised on the train nodes')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     p.add_argument('--walk_p', type=float, default=1.0,
                    help='return parameter p of node2vec\'s second-order walk (a step back to the previous node weighs 1/p)')
@@ -117,7 +121,10 @@ def embedding_width(flags):
 def refuse_eval_classifier(flags, G=None):
     """--eval_classifier needs the saved embeddings, a width the classifier kernel takes and (once the graph is loaded) class
     labels in its range: anything else is refused before training, with the rule in the message."""
+    kinds = eval_classifier_kinds(flags)
     if not getattr(flags, "eval_classifier", ""):
+        if kinds:
+            raise SystemExit("--eval_classifier_inputs %s needs --eval_classifier val or test" % flags.eval_classifier_inputs)
         return
     from . import evaluation
     if not flags.save_embeddings:
@@ -126,16 +133,45 @@ def refuse_eval_classifier(flags, G=None):
         evaluation.refuse(embedding_width(flags), n_classes=1)
     except ValueError as e:
         raise SystemExit("--eval_classifier: %s" % e)
+    if kinds:
+        width = G.feats.shape[1] if G is not None and G.feats is not None else (None if G is not None else feature_width(flags))
+        for kind in kinds:
+            evaluation.refuse_inputs(kind, width, embedding_width(flags), width is not None)
     if G is not None:
         evaluation.refuse_graph(G)
 
 
+def eval_classifier_kinds(flags):
+    """The inputs --eval_classifier_inputs adds to the embeddings line."""
+    return {"embeddings": (), "features": ("features",), "both": ("both",),
+            "all": ("features", "both")}[getattr(flags, "eval_classifier_inputs", "embeddings")]
+
+
+def feature_width(flags):
+    """Columns of the feature table the run will load, read without loading it; None: the dataset has none."""
+    if flags.synthetic:
+        return 602 if flags.synthetic == 'reddit' else 50          # supervised_train.load_graph
+    path = flags.train_prefix + "-feats.npy"
+    if not os.path.exists(path):
+        return None
+    shape = np.load(path, mmap_mode="r").shape
+    return int(shape[1]) if len(shape) == 2 else None
+
+
 def save_eval_classifier(G, out_dir):
-    """eval_classifier.txt: the `Downstream classifier:` line for the table that was just written."""
+    """eval_classifier.txt: the `Downstream classifier:` line for the table that was just written; then the lines and files
+    of --eval_classifier_inputs, on the feature table the model trained on (one upload)."""
     from . import engine as eng
     from . import evaluation
-    return evaluation.evaluate_embedding_dir(eng.get_engine(), G, out_dir, FLAGS.eval_classifier,
-                                             base="val_full" if FLAGS.full_inference else "val")
+    base = "val_full" if FLAGS.full_inference else "val"
+    res = evaluation.evaluate_embedding_dir(eng.get_engine(), G, out_dir, FLAGS.eval_classifier, base=base)
+    kinds = eval_classifier_kinds(FLAGS)
+    if kinds:
+        features = evaluation.as_mat(eng.get_engine(), G.feats)
+        for kind in kinds:
+            evaluation.evaluate_embedding_dir(eng.get_engine(), G, out_dir, FLAGS.eval_classifier, base=base, inputs=kind,
+                                              features=features)
+    return res
 
 
 def device_walks(rowptr, col, nodes, max_pairs=None):

@@ -1268,6 +1268,56 @@ int gs_logreg_ws_bytes(int64_t n, int32_t d, int32_t c, int64_t* bytes_out_host)
 int gs_logreg_eval(const gs_logreg_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LOGREG, joined  the same evaluation on rows that are formed from TWO tables and standardised while they are staged (the
+ *      `feat` and features + embeddings inputs of eval_scripts/: hstack, StandardScaler, then the regression).  Row i is
+ *        x[i][j] = ((j < da ? Xa[rows_a[i]][j] : Xb[rows_b[i]][j - da]) - mu[j]) * inv[j],    0 <= j < d = da + db
+ *      one fp32 subtract, then one fp32 multiply (the scaler is NOT folded into W and b: that cancels for a column whose mean
+ *      is large against its spread).  mu and inv (fp32 [d], 16-byte aligned) are given together or both null (no affine).
+ *      Source B is absent when Xb, rows_b, ldb, db and n_rows_b are all null / zero.  rows_a and rows_b are independent, each
+ *      nullable (rows 0 .. n-1 of its table), entries may repeat and must lie in [0, n_rows_a) / [0, n_rows_b).
+ *      da % 4 == 0, db % 4 == 0, da >= 4, 4 <= d <= GS_LOGREG_JOINED_MAX_D, lda >= da, ldb >= db; W is [d][ldw], gW [d][c].
+ *      Everything else -- modes, labels, outputs, the arithmetic after staging, the order of every sum -- is gs_logreg_eval's
+ *      (the two kernels share their device code, csrc/gs_logreg_dev.h): with B absent, mu null and d <= GS_LOGREG_MAX_D every
+ *      output is bit-equal to gs_logreg_eval on the same inputs.  gs_logreg_joined_ws_bytes is gs_logreg_ws_bytes' formula
+ *      with d up to GS_LOGREG_JOINED_MAX_D.  Anything else is refused with a message and no launch.
+ *      gs_logreg_joined_desc is 224 bytes on every target (checked at compile time and by the binding; passed by pointer, not
+ *      part of gs_abi_struct_sizes).
+ *
+ *      gs_col_moments writes the column means and POPULATION variances of the same joined rows, without any affine, as fp64
+ *      mean[d] and var[d]: centred (the means first, then the squares of x - mean), no atomics, a fixed summation order,
+ *      bitwise repeatable; a column whose selected entries are all equal has var == 0.0 exactly.  ws: device, 8-byte aligned,
+ *      ws_bytes >= GS_COL_MOMENTS_MAX_CHUNKS * d * 8.  (StandardScaler: scale = sqrt(var), 1 where var == 0; the caller
+ *      uploads mu = mean and inv = 1 / scale as fp32.)
+ * ------------------------------------------------------------------------------------------- */
+#define GS_LOGREG_JOINED_MAX_D 1024
+#define GS_COL_MOMENTS_MAX_CHUNKS 256
+typedef struct gs_logreg_joined_desc {
+    const float* Xa;           /* device [n_rows_a][lda] source A: columns [0, da) */
+    const int32_t* rows_a;     /* device [n] rows of Xa; nullable (0 .. n-1) */
+    const float* Xb;           /* device [n_rows_b][ldb] source B: columns [da, da + db); NULL: absent */
+    const int32_t* rows_b;     /* device [n] rows of Xb; nullable (0 .. n-1) */
+    const float* mu;           /* device [d]; nullable (with inv) */
+    const float* inv;          /* device [d]; nullable (with mu) */
+    const float* W;            /* device [d][ldw] */
+    const float* b;            /* device [c] */
+    const int32_t* y_class;    /* device [n]; nullable */
+    const uint8_t* y_multi;    /* device [n][ldy]; nullable */
+    double* loss;              /* device [c]; FIT: required, PREDICT: nullable (needs labels) */
+    double* gW;                /* device [d][c]; FIT only */
+    double* gb;                /* device [c]; FIT only */
+    int32_t* pred_class;       /* device [n]; PREDICT only, nullable */
+    uint8_t* pred_multi;       /* device [n][ldp]; PREDICT only, nullable */
+    void* ws;                  /* device, 8-byte aligned, ws_bytes >= gs_logreg_joined_ws_bytes(n, d, c); needed with loss */
+    int64_t n, n_rows_a, lda, n_rows_b, ldb, ldw, ldy, ldp, ws_bytes;
+    int32_t da, db, c, mode, flags, reserved_; /* mode: GS_LOGREG_FIT | GS_LOGREG_PREDICT; flags, reserved_: 0 */
+} gs_logreg_joined_desc;
+int gs_logreg_joined_ws_bytes(int64_t n, int32_t d, int32_t c, int64_t* bytes_out_host);
+int gs_logreg_eval_joined(const gs_logreg_joined_desc* desc_host, void* stream);
+int gs_col_moments(const float* Xa, const int32_t* rows_a, int64_t lda, int32_t da, int64_t n_rows_a,
+                   const float* Xb, const int32_t* rows_b, int64_t ldb, int32_t db, int64_t n_rows_b, int64_t n,
+                   double* mean, double* var, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
