@@ -180,6 +180,7 @@ _PROTOS = {
     "gs_topk_select": [_P, _P],
     "gs_walk_paths": [_P, _P],
     "gs_walk_pairs": [_P, _P],
+    "gs_importance_table": [_P, _P],
     "gs_logreg_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
     "gs_logreg_eval": [_P, _P],
     "gs_logreg_joined_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
@@ -359,6 +360,20 @@ WALK_TAG = 0xA7 << 56                       # GS_WALK_TAG
 WALK_ATTEMPTS = 256                         # GS_WALK_ATTEMPTS
 WALK_MAX_LEN = 4096                         # GS_WALK_MAX_LEN
 assert ctypes.sizeof(WalkDesc) == 152      # static_assert in csrc/gs_walk.hip (passed by pointer, as RankDesc)
+
+
+class ImportanceDesc(ctypes.Structure):
+    """struct gs_importance_desc (include/graphsage_amd.h)"""
+    _fields_ = [("paths", c_void_p), ("table", c_void_p), ("stats", c_void_p),
+                ("n_starts", c_int64), ("n_nodes", c_int64), ("ld_paths", c_int64),
+                ("num_walks", c_int32), ("walk_len", c_int32), ("top", c_int32), ("slots", c_int32), ("pad_id", c_int32),
+                ("reserved_", c_int32)]
+
+
+IMPORTANCE_MAX_VISITS = 4096                # GS_IMPORTANCE_MAX_VISITS
+IMPORTANCE_MAX_TOP = 4096                   # GS_IMPORTANCE_MAX_TOP
+IMPORTANCE_MAX_SLOTS = 1024                 # GS_IMPORTANCE_MAX_SLOTS
+assert ctypes.sizeof(ImportanceDesc) == 72  # static_assert in csrc/gs_importance.hip (passed by pointer, as WalkDesc)
 
 
 class LogregDesc(ctypes.Structure):

@@ -23,8 +23,11 @@ from .layers import Layer
 
 class PaddedAdjacency(object):
     def __init__(self, adj, device):
-        adj = np.ascontiguousarray(adj, dtype=np.int32)
-        self.table = torch.from_numpy(adj).to(device)
+        if torch.is_tensor(adj):             # a table that already lives on a device (utils.importance_neighbors)
+            self.table = adj.to(device=device, dtype=torch.int32).contiguous()
+        else:
+            adj = np.ascontiguousarray(adj, dtype=np.int32)
+            self.table = torch.from_numpy(adj).to(device)
         self.n_nodes = adj.shape[0] - 1
         self.max_degree = adj.shape[1]
 
@@ -45,6 +48,24 @@ class CSRAdjacency(object):
         self = cls.__new__(cls)
         self.rowptr, self.col, self.n_nodes = rowptr.contiguous(), col.contiguous(), int(n_nodes)
         return self
+
+    @classmethod
+    def from_table(cls, table):
+        """The CSR of an [N + 1, slots] int32 table whose pad id is N (utils.importance_neighbors), built where the table lives:
+        rows 0 .. N - 1, a row that is all pad becomes a row of degree 0, every other row keeps its `slots` entries verbatim,
+        repeats included.  Under the reference law with max_degree == slots such a row is used as it stands, and a repeated
+        entry is drawn as often as it is stored."""
+        if not torch.is_tensor(table) or table.dim() != 2 or table.shape[0] < 1 or table.dtype != torch.int32:
+            raise ops._lib.GraphsageAmdError("CSRAdjacency.from_table: table must be an int32 [N + 1, slots] tensor")
+        n, slots = table.shape[0] - 1, table.shape[1]
+        rows = table[:n]
+        full = (rows != n).any(dim=1)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=table.device)
+        rowptr[1:] = torch.cumsum(full.to(torch.int64) * slots, 0)
+        col = rows[full].reshape(-1)
+        if col.numel() == 0:
+            col = torch.zeros(1, dtype=torch.int32, device=table.device)
+        return cls.from_device(rowptr, col, n)
 
 
 class AdjInfo(object):

@@ -485,6 +485,36 @@ def walk_pairs(paths, offsets, total, pairs=None, stream=None):
     return pairs[:int(total)]
 
 
+def importance_table(paths, num_walks, walk_len, n_nodes, top, slots, pad_id, table=None, stats=None, stream=None):
+    """gs_importance_table: the importance neighborhoods of the starts whose walks `paths` holds (walk_paths: int32
+    [n_starts * num_walks, >= walk_len], unit column stride; the walks of start i in rows i * num_walks ..).  The `top` most
+    visited nodes of each start share `slots` table entries by largest remainder (include/graphsage_amd.h, section
+    IMPORTANCE).  Returns (table int32 [n_starts, slots], stats int32 [n_starts, 2] = (distinct visited, nodes with a slot))."""
+    num_walks, walk_len, top, slots = int(num_walks), int(walk_len), int(top), int(slots)
+    if paths.dtype != torch.int32 or paths.dim() != 2 or (paths.shape[0] and paths.stride(1) != 1) or num_walks < 1 \
+            or paths.shape[0] % num_walks:
+        raise _lib.GraphsageAmdError("importance_table: paths must be int32 [n_starts * num_walks, >= walk_len] with unit column "
+                                     "stride")
+    n_starts = paths.shape[0] // num_walks
+    dev = paths.device
+    table = torch.empty((n_starts, max(slots, 0)), dtype=torch.int32, device=dev) if table is None else table
+    stats = torch.empty((n_starts, 2), dtype=torch.int32, device=dev) if stats is None else stats
+    if table.dtype != torch.int32 or tuple(table.shape) != (n_starts, slots) or not table.is_contiguous() \
+            or stats.dtype != torch.int32 or tuple(stats.shape) != (n_starts, 2) or not stats.is_contiguous() \
+            or table.device != dev or stats.device != dev:
+        raise _lib.GraphsageAmdError("importance_table: table must be a dense int32 [n_starts, slots] and stats a dense int32 "
+                                     "[n_starts, 2], both on the device of paths")
+    d = _lib.ImportanceDesc()
+    d.paths, d.table, d.stats = (ptr(paths) if paths.numel() else None), (ptr(table) if table.numel() else None), \
+        (ptr(stats) if stats.numel() else None)
+    d.n_starts, d.n_nodes = n_starts, int(n_nodes)
+    # (a view narrower than walk_len is refused by the library whatever its row stride)
+    d.ld_paths = paths.stride(0) if paths.shape[0] > 1 and paths.shape[1] >= walk_len else max(paths.shape[1], 1)
+    d.num_walks, d.walk_len, d.top, d.slots, d.pad_id = num_walks, walk_len, top, slots, int(pad_id)
+    call("gs_importance_table", ctypes.addressof(d), _s(stream))
+    return table, stats
+
+
 # ------------------------------------------------------------------------------------------ K3
 def sage_dense_fwd(self_m, self_idx, agg, agg_idx, n, W_self, W_neigh, out_dim, concat, act, bias, out,
                    stream=None):

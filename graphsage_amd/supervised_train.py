@@ -66,6 +66,7 @@ def build_flags(argv=None):
                    help='after training: exact layer-wise inference over every node\'s WHOLE neighbor list on the test graph '
                         '(predict_full) -> val_stats_full.txt / test_stats_full.txt; not for graphsage_seq')
     add_embed_nodes_flag(p)
+    add_importance_flags(p)
     return p.parse_args(argv)
 
 
@@ -76,7 +77,88 @@ def add_embed_nodes_flag(p):
                         '(supervised: + embed_nodes_preds.npy); not for n2v / graphsage_seq')
 
 
+def add_importance_flags(p):
+    p.add_argument('--importance_neighbors', type=int, default=0,
+                   help='T > 0: importance neighborhoods (PinSage) in place of adjacency rows: a node\'s neighbors are the T '
+                        'nodes that short random walks from it visit most often, stored in the --max_degree slots of its table '
+                        'row in proportion to their visits (gs_importance_table); sampling, validation, --full_inference, '
+                        '--embed_nodes and --eval_classifier then run over that graph; 0: off')
+    p.add_argument('--importance_walks', type=int, default=50, help='random walks per node for --importance_neighbors')
+    p.add_argument('--importance_walk_len', type=int, default=3,
+                   help='nodes per walk for --importance_neighbors, the start included')
+    p.add_argument('--importance_p', type=float, default=1.0, help='return parameter p of the walks for --importance_neighbors')
+    p.add_argument('--importance_q', type=float, default=1.0, help='in-out parameter q of the walks for --importance_neighbors')
+
+
 FLAGS = None
+
+
+def refuse_importance(flags):
+    """--importance_neighbors with a model, a follow-up flag or sizes it does not cover is refused before any work is done, with
+    the rule in the message."""
+    top = getattr(flags, "importance_neighbors", 0)
+    if not top:
+        return
+    from . import _lib
+    if flags.model == 'n2v':
+        raise SystemExit("--importance_neighbors is not available with --model n2v: node2vec has no aggregation layers (it "
+                         "samples no neighborhoods)")
+    for flag in ("rank_full", "topk_full"):
+        if getattr(flags, flag, False):
+            raise SystemExit("--importance_neighbors cannot be combined with --%s: its filter is the known edges of the graph it "
+                             "is given, and that must stay the true graph, not the importance neighborhoods" % flag)
+    walks, length, slots = flags.importance_walks, flags.importance_walk_len, flags.max_degree
+    if not 1 <= top <= _lib.IMPORTANCE_MAX_TOP:
+        raise SystemExit("--importance_neighbors %d: must lie in 1 .. %d" % (top, _lib.IMPORTANCE_MAX_TOP))
+    if walks < 1 or length < 2:
+        raise SystemExit("--importance_walks must be at least 1 and --importance_walk_len at least 2")
+    if walks * (length - 1) > _lib.IMPORTANCE_MAX_VISITS:
+        raise SystemExit("--importance_walks %d x (--importance_walk_len %d - 1) = %d visits per node; at most %d"
+                         % (walks, length, walks * (length - 1), _lib.IMPORTANCE_MAX_VISITS))
+    if not 1 <= slots <= _lib.IMPORTANCE_MAX_SLOTS:
+        raise SystemExit("--importance_neighbors fills --max_degree %d slots per node; it must lie in 1 .. %d"
+                         % (slots, _lib.IMPORTANCE_MAX_SLOTS))
+    from .ops import walk_thresholds
+    try:
+        walk_thresholds(flags.importance_p, flags.importance_q)
+    except ValueError as e:
+        raise SystemExit("--importance_p / --importance_q: %s" % e)
+
+
+def importance_line(flags, graph, n_rows, stats, duration):
+    """The line --importance_neighbors prints per graph; stats: int [n_rows, 2] = (distinct nodes visited, nodes with a slot)."""
+    stats = np.asarray(stats).reshape(-1, 2)
+    return ("Importance neighborhoods: graph= %s top= %d slots= %d walks= %d len= %d p= %g q= %g rows= %d distinct_mean= %.5f "
+            "kept_mean= %.5f empty= %d time= %.5f" % (
+                graph, flags.importance_neighbors, flags.max_degree, flags.importance_walks, flags.importance_walk_len,
+                flags.importance_p, flags.importance_q, n_rows, stats[:, 0].mean() if n_rows else 0.0,
+                stats[:, 1].mean() if n_rows else 0.0, int((stats[:, 0] == 0).sum()), duration))
+
+
+def importance_adjacencies(flags, minibatch, n_nodes, device):
+    """The importance tables of the train and the test graph (utils.importance_neighbors over minibatch.train_csr / .test_csr),
+    one printed line each, as the adjacencies the sampler sees: padded tables under --sampler padded, else their CSR.  The test
+    table is kept on the iterator for full_graph().  The true graph stays what it was everywhere else (minibatch.deg, the
+    negative-sampling law, the context pairs, val_edges)."""
+    import torch
+    from . import utils
+    from .neigh_samplers import CSRAdjacency, PaddedAdjacency
+    out = []
+    for graph, (rowptr, col) in (("train", minibatch.train_csr), ("test", minibatch.test_csr)):
+        t0 = time.time()
+        table, stats = utils.importance_neighbors(
+            torch.from_numpy(np.ascontiguousarray(rowptr, dtype=np.int64)).to(device),
+            torch.from_numpy(np.ascontiguousarray(col, dtype=np.int32)).to(device), n_nodes, flags.importance_neighbors,
+            flags.max_degree, num_walks=flags.importance_walks, walk_len=flags.importance_walk_len, p=flags.importance_p,
+            q=flags.importance_q, seed=seed)
+        stats = stats.cpu().numpy()                          # (the copy ends the timed work)
+        print(importance_line(flags, graph, n_nodes, stats, time.time() - t0))
+        out.append(PaddedAdjacency(table, device) if flags.sampler == 'padded' else CSRAdjacency.from_table(table))
+        if graph == "test":
+            minibatch.importance_test = table
+    # the tables and their CSRs were made on torch's current stream; the engine's stream does not wait for it by itself
+    torch.cuda.current_stream().synchronize()
+    return out
 
 
 def refuse_full_inference(flags):
@@ -155,6 +237,8 @@ def refuse_dropout(flags):
 def full_graph(minibatch, n_nodes):
     """The test graph for full-neighborhood inference: the padded test table verbatim under --sampler padded, else the CSR."""
     from .inference import FullGraph
+    if getattr(minibatch, "importance_test", None) is not None:      # --importance_neighbors: that table verbatim
+        return FullGraph.from_padded(minibatch.importance_test)
     if minibatch.test_adj is not None:
         return FullGraph.from_padded(minibatch.test_adj)
     return FullGraph.from_csr(minibatch.test_csr[0], minibatch.test_csr[1], n_nodes)
@@ -293,7 +377,9 @@ def train(G, embed_rows=None):
     minibatch = NodeMinibatchIterator(G, None, placeholders, None, num_classes, batch_size=FLAGS.batch_size,
                                       max_degree=FLAGS.max_degree, build_padded=(FLAGS.sampler == 'padded'))
     e = eng.get_engine()
-    if FLAGS.sampler == 'padded':
+    if getattr(FLAGS, "importance_neighbors", 0):
+        train_adj, test_adj = importance_adjacencies(FLAGS, minibatch, G.n_nodes, e.device)
+    elif FLAGS.sampler == 'padded':
         train_adj = PaddedAdjacency(minibatch.adj, e.device)
         test_adj = PaddedAdjacency(minibatch.test_adj, e.device)
     else:
@@ -452,6 +538,7 @@ def main(argv=None):
     FLAGS = build_flags(argv)
     refuse_full_inference(FLAGS)
     refuse_dropout(FLAGS)
+    refuse_importance(FLAGS)
     tokens = read_embed_nodes(FLAGS)
     print("Loading training data..")
     G = load_graph()

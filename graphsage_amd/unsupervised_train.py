@@ -71,8 +71,9 @@ def build_flags(argv=None):
                    help='K > 0: after val.npy, the K best-scoring partners of every node among ALL nodes with the exact '
                         'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
                         'topk_full_scores.npy; not for n2v / graphsage_seq')
-    from .supervised_train import add_embed_nodes_flag
+    from .supervised_train import add_embed_nodes_flag, add_importance_flags
     add_embed_nodes_flag(p)
+    add_importance_flags(p)
     p.add_argument('--eval_classifier', default='', choices=['', 'val', 'test'],
                    help='val | test: after val.npy, fit a logistic regression on the train nodes\' embeddings on the device and '
                         'score it on that split (the reference\'s eval_scripts; with --full_inference on val_full.npy, with '
@@ -333,7 +334,10 @@ def train(G, context_pairs, embed_rows=None):
                                       context_pairs=context_pairs if FLAGS.random_context else None,
                                       build_padded=(FLAGS.sampler == 'padded'))
     e = eng.get_engine()
-    if FLAGS.sampler == 'padded':
+    if getattr(FLAGS, "importance_neighbors", 0):
+        from .supervised_train import importance_adjacencies
+        train_adj, test_adj = importance_adjacencies(FLAGS, minibatch, G.n_nodes, e.device)
+    elif FLAGS.sampler == 'padded':
         train_adj, test_adj = PaddedAdjacency(minibatch.adj, e.device), PaddedAdjacency(minibatch.test_adj, e.device)
     else:
         train_adj = CSRAdjacency(minibatch.train_csr[0], minibatch.train_csr[1], G.n_nodes, e.device)
@@ -483,6 +487,7 @@ def main(argv=None):
     from . import supervised_train as st
     st.refuse_full_inference(FLAGS)
     st.refuse_dropout(FLAGS)
+    st.refuse_importance(FLAGS)
     refuse_walk_flags(FLAGS)
     refuse_eval_classifier(FLAGS)
     tokens = st.read_embed_nodes(FLAGS)

@@ -556,3 +556,35 @@ def device_walk_pairs(rowptr, col, nodes, num_walks=N_WALKS, walk_len=WALK_LEN, 
     if max_pairs is not None and pairs.shape[0] > max_pairs:
         pairs = pairs[torch.randperm(pairs.shape[0], device=device, generator=g)[:max_pairs]]
     return (pairs, all_paths) if return_paths else pairs
+
+
+def importance_neighbors(rowptr, col, n_nodes, top, slots, num_walks=50, walk_len=3, p=1.0, q=1.0, seed=123, chunk_starts=None):
+    """Importance neighborhoods (PinSage) as the sampler's table: num_walks (p, q) walks of walk_len nodes from EVERY node
+    0 .. n_nodes - 1 of the CSR in HBM (gs_walk_paths; rowptr int64 [n_nodes + 1], col int32, rows ascending for (p, q) !=
+    (1, 1)), and per node its `top` most visited nodes spread over `slots` entries in proportion to their visits
+    (gs_importance_table).  A node without neighbors stays where it is and gets an all-pad row, as does the pad row n_nodes.
+    The job runs in chunks of chunk_starts whole starts; walk g depends on (seed, g) only, so the table does not depend on the
+    chunking.  Returns (table int32 [n_nodes + 1, slots] on the device, stats int32 [n_nodes, 2] on the device: the distinct
+    nodes visited and the nodes that got a slot)."""
+    import torch
+    from . import ops
+    thr = ops.walk_thresholds(p, q)
+    n_nodes, num_walks, walk_len, top, slots = int(n_nodes), int(num_walks), int(walk_len), int(top), int(slots)
+    if rowptr.numel() != n_nodes + 1:
+        raise ValueError("importance_neighbors: rowptr must have n_nodes + 1 = %d entries" % (n_nodes + 1))
+    if num_walks < 1 or walk_len < 2 or slots < 1:
+        raise ValueError("importance_neighbors: num_walks=%d must be at least 1, walk_len=%d at least 2 and slots=%d at least 1"
+                         % (num_walks, walk_len, slots))
+    device = rowptr.device
+    if len(set(thr)) > 1:
+        check_rows_ascending(rowptr, col)
+    table = torch.full((n_nodes + 1, slots), n_nodes, dtype=torch.int32, device=device)
+    stats = torch.zeros((n_nodes, 2), dtype=torch.int32, device=device)
+    starts = torch.arange(n_nodes, dtype=torch.int32, device=device)
+    chunk = max(1, int(chunk_starts or max(1, WALK_CHUNK // num_walks)))
+    for s0 in range(0, n_nodes, chunk):
+        n = min(chunk, n_nodes - s0)
+        paths, _ = ops.walk_paths(rowptr, col, starts, num_walks, walk_len, thr, seed, walk0=s0 * num_walks, n_walks=n * num_walks)
+        ops.importance_table(paths, num_walks, walk_len, n_nodes, top, slots, n_nodes, table=table[s0:s0 + n],
+                             stats=stats[s0:s0 + n])
+    return table, stats

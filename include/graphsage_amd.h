@@ -1221,6 +1221,44 @@ int gs_walk_paths(const gs_walk_desc* desc_host, void* stream);
 int gs_walk_pairs(const gs_walk_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * IMPORTANCE importance neighborhoods (PinSage): the neighborhood of a start u is the set of nodes that short random walks
+ *      from u visit most often, and the table row of u stores each of them as often as its share of the visits asks.  Input
+ *      is what gs_walk_paths wrote: paths int32 [n_starts * num_walks][ld_paths], the walks of start i in rows
+ *      i * num_walks .. (i + 1) * num_walks - 1.  Output: table int32 [n_starts][slots] (dense) and stats int32 [n_starts][2].
+ *      The rule for start i, integers only:
+ *        1. u = paths[i * num_walks][0].  u outside [0, n_nodes) (the walker's row of -1): the row is all pad_id, stats (0, 0).
+ *        2. A visit is x = paths[i * num_walks + r][j], 0 <= r < num_walks, 1 <= j < walk_len; it is KEPT iff 0 <= x < n_nodes
+ *           and x != u (a stored pad id, -1 and the start itself never become neighbors).
+ *        3. c(x) = the kept visits of x, m = the distinct x.  m == 0: the row is all pad_id, stats (0, 0).
+ *        4. The selected set: the first min(m, top) nodes in the order (c descending, id ascending).
+ *        5. Largest remainder over the selected set: C = sum c; q_k = floor(c_k * slots / C), r_k = c_k * slots - q_k * C;
+ *           rest = slots - sum q_k; the first `rest` selected nodes in the order (r descending, id ascending) get one more
+ *           slot.  (c * slots <= 2^22; rest is smaller than the number of non-zero remainders, so the rule is total.)
+ *        6. Row i holds the selected ids ascending, id k repeated n_k times: exactly `slots` entries, ids with n_k == 0 absent.
+ *           stats[i] = (m, #{k : n_k > 0}).
+ *      A CSR whose non-empty rows hold exactly max_degree = slots entries is used as it stands by GS_LAW_REFERENCE and a
+ *      repeated entry is drawn as often as it is stored, so an entry stored n times weighs n / slots in the sampled mean and
+ *      in the exact one (csr_reduce over the table): importance pooling by multiplicity, no other kernel involved.
+ *      Limits, checked before any launch (else GS_EINVAL): num_walks >= 1, walk_len >= 2, V = num_walks * (walk_len - 1) <=
+ *      GS_IMPORTANCE_MAX_VISITS, 1 <= top <= GS_IMPORTANCE_MAX_TOP, 1 <= slots <= GS_IMPORTANCE_MAX_SLOTS, ld_paths >= walk_len,
+ *      0 <= n_nodes <= 2^31 - 1, reserved_ == 0; n_starts == 0 is a no-op.  pad_id is any int32.
+ *      One wave per start, sorts in LDS, ONE kernel form for every V (no switch point); no atomics, no floats: bitwise
+ *      reproducible (csrc/gs_importance.hip).  gs_importance_desc is 72 bytes on every target (checked at compile time and
+ *      by the binding; passed by pointer, not part of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_IMPORTANCE_MAX_VISITS 4096
+#define GS_IMPORTANCE_MAX_TOP 4096
+#define GS_IMPORTANCE_MAX_SLOTS 1024
+typedef struct gs_importance_desc {
+    const int32_t* paths;      /* device [n_starts * num_walks][ld_paths] */
+    int32_t* table;            /* device [n_starts][slots] */
+    int32_t* stats;            /* device [n_starts][2]: (distinct kept nodes, nodes with a slot) */
+    int64_t n_starts, n_nodes, ld_paths;
+    int32_t num_walks, walk_len, top, slots, pad_id, reserved_;   /* reserved_: 0 */
+} gs_importance_desc;
+int gs_importance_table(const gs_importance_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * LOGREG one loss-and-gradient evaluation of a one-vs-rest logistic regression on rows of an embedding table (the downstream
  *      node classification of eval_scripts/: SGDClassifier(loss="log") per class; csrc/gs_logreg.hip).  With
  *        z[i][k] = <X[rows[i]], W[:, k]> + b[k]   (fp32 on the matrix cores),   s[i][k] = +1 / -1,   m = s z
