@@ -290,33 +290,31 @@ class _SageBase(Layer):
         ops.input_grad_pull(d_prev, d_prev.rows, d_prev.d, d_self=d_self_all, n_self=n_total, segments=segs,
                             mask_y=prev_mask, stream=e.stream)
 
-    def _infer_reduce_sage(self, graph, csr_op, table, reduced, H, out):
-        """Tail of infer_full, per window of rows: `table` reduced over every row's whole neighbor list into `reduced`, then the
-        SAGE matmuls over [H rows | reduced].  Returns `out` once the stream has drained."""
+    # ---- exact full-neighborhood inference (inference.py): ONE recipe per aggregator, written on a scope's primitives ----
+    def infer(self, scope, H):
+        """The layer for the rows `scope` computes, every row from ALL its neighbors, no dropout: H is the table of the layer
+        below, the result a table over the computed rows.  scope: inference.GraphLayer (every row of the graph, the pad row
+        computed like any other, in row windows) or inference.RowsLayer (a row subset, compact tables)."""
+        raise NotImplementedError
+
+    def infer_full(self, graph, H):
+        """infer for EVERY row of `graph` (inference.FullGraph): H [N + 1, d_in] -> [N + 1, n_out], once the stream has drained."""
         from . import inference as inf
-        e = self.engine
-        b = self.vars['bias'].value.buf if self.bias else None
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            graph.reduce(e, csr_op, table, reduced, r0, n)
-            ops.sage_dense_fwd(H.rows_slice(r0, r0 + n), None, reduced, None, n, self.vars['self_weights'].value,
-                               self.vars['neigh_weights'].value, self.output_dim, self.concat, self.act_code, b,
-                               out.rows_slice(r0, r0 + n), stream=e.stream)
-        e.sync()
+        return self._drained(self.infer(inf.GraphLayer(graph), H))
+
+    def infer_rows(self, L, H):
+        """infer for the rows of L (inference.RowsLayer) only, into a compact [L.n, n_out] table: H is the feature table by node
+        id, or the compact table over the rows this layer may read."""
+        return self._drained(self.infer(L, H))
+
+    def _drained(self, out):
+        self.engine.sync()
         return out
 
-    def _infer_rows_sage(self, L, csr_op, table, x_pos, width, H):
-        """Tail of infer_rows: `table` (read through x_pos) reduced over the whole neighbor lists of the rows of L into a
-        compact [L.n, width] table, then the SAGE matmuls over [rows L.self_ids of H | reduced]."""
-        from . import inference as inf
-        e = self.engine
-        out = inf._table(e, L.n, self.output_dim * (2 if self.concat else 1))
-        reduced = inf._table(e, L.n, width, ld_multiple=32)
-        L.reduce(e, csr_op, table, reduced, x_pos)
-        b = self.vars['bias'].value.buf if self.bias else None
-        ops.sage_dense_fwd(H, L.self_ids, reduced, None, L.n, self.vars['self_weights'].value, self.vars['neigh_weights'].value,
-                           self.output_dim, self.concat, self.act_code, b, out, stream=e.stream)
-        e.sync()
-        return out
+    def _infer_sage(self, scope, csr_op, X, of_src, H):
+        """Tail of the wide forms: X reduced over the whole neighbor lists, then the SAGE matmuls over [self rows of H | reduced]."""
+        return scope.reduce_sage(self, csr_op, X, of_src, H, self.vars['self_weights'].value, self.vars['neigh_weights'].value,
+                                 self.output_dim, self.concat, self.act_code, self.vars['bias'].value.buf if self.bias else None)
 
 
 class MeanAggregator(_SageBase):
@@ -507,44 +505,17 @@ class MeanAggregator(_SageBase):
             self._bwd_dropped(d_means_all.rows_slice(r, r + n), n, s, 1.0 / s, rate, SITE_NEIGH, k, hr, dst, mask,
                               (h + 1 < len(neighs)), ("n", h))
 
-    def infer_full(self, graph, H):
-        """The layer for EVERY row of `graph` (inference.FullGraph) from ALL its neighbors: H [N + 1, d_in] -> [N + 1, n_out],
-        the pad row computed like any other; no dropout.  The mean is linear, so the narrower side is reduced: with concat and
-        output_dim < d_in the rows of H . W_neigh are averaged (602 -> 128 at Reddit's layer 0: 4.7 x fewer gathered bytes)."""
-        from . import inference as inf
-        e = self.engine
-        o, d_in = self.output_dim, H.d
-        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
-        if not (self.concat and not self.bias and o % 4 == 0 and o < d_in):
-            means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
-            return self._infer_reduce_sage(graph, inf.CSR_MEAN, H, means, H, out)
-        W_self, W_neigh = self.vars['self_weights'].value, self.vars['neigh_weights'].value
-        P = inf._table(e, graph.n_rows, o)
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_neigh, P.rows_slice(r0, r0 + n), stream=e.stream)
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            rows = out.rows_slice(r0, r0 + n)
-            ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W_self, rows.cols_slice(0, o), act=self.act_code,
-                     stream=e.stream)
-            graph.reduce(e, inf.CSR_MEAN, P, rows.cols_slice(o, 2 * o), r0, n, act=self.act_code)
-        e.sync()
-        return out
-
-    def infer_rows(self, L, H):
-        """infer_full for the rows of L (inference.RowsLayer) only, into a compact [L.n, n_out] table: H is the table of the layer
-        below (the feature table by node id, or the compact table over the rows this layer may read).  The same two forms."""
-        from . import inference as inf
-        e = self.engine
+    def infer(self, scope, H):
+        """The mean is linear, so the narrower side is reduced: with concat and output_dim < d_in the rows of H . W_neigh are
+        averaged (602 -> 128 at Reddit's layer 0: 4.7 x fewer gathered bytes)."""
+        from .inference import CSR_MEAN
         o, d_in = self.output_dim, H.d
         if not (self.concat and not self.bias and o % 4 == 0 and o < d_in):
-            return self._infer_rows_sage(L, inf.CSR_MEAN, H, L.src_pos, d_in, H)
-        out = inf._table(e, L.n, 2 * o)
-        P = inf._table(e, L.prev_n, o)
-        ops.gemm(False, False, L.prev_n, o, d_in, H, self.vars['neigh_weights'].value, P, a_row_idx=L.prev_ids, stream=e.stream)
-        ops.gemm(False, False, L.n, o, d_in, H, self.vars['self_weights'].value, out.cols_slice(0, o), a_row_idx=L.self_ids,
-                 act=self.act_code, stream=e.stream)
-        L.reduce(e, inf.CSR_MEAN, P, out.cols_slice(o, 2 * o), L.prev_pos, act=self.act_code)
-        e.sync()
+            return self._infer_sage(scope, CSR_MEAN, H, True, H)
+        P = scope.dense(self, H, [(self.vars['neigh_weights'].value, None, o, ACT_IDENTITY)])
+        out = scope.table(self, 2 * o)
+        scope.self_gemm(self, H, self.vars['self_weights'].value, o, out.cols_slice(0, o), self.act_code)
+        scope.reduce(self, CSR_MEAN, P, False, out.cols_slice(o, 2 * o), self.act_code)
         return out
 
 
@@ -649,49 +620,17 @@ class GCNAggregator(_SageBase):
             self._bwd_dropped(d_means.rows_slice(r, r + n), n, s, 1.0 / (s + 1), rate, SITE_NEIGH, k, hr, dst, mask,
                               (h + 1 < len(neighs)), ("n", h))
 
-    def infer_full(self, graph, H):
-        """MeanAggregator.infer_full for the GCN layer: act(mean over {all neighbors} U {self} . W [+ b]) (aggregators.py:96-116).
-        The mean's weights sum to one, so when output_dim <= d_in the rows of H . W + b are averaged instead."""
-        from . import inference as inf
-        e = self.engine
+    def infer(self, scope, H):
+        """act(mean over {all neighbors} U {self} . W [+ b]) (aggregators.py:96-116).  The mean's weights sum to one, so when
+        output_dim <= d_in the rows of H . W + b are averaged instead."""
+        from .inference import CSR_MEAN_SELF
         o, d_in = self.output_dim, H.d
-        out = inf._table(e, graph.n_rows, o)
         W = self.vars['weights'].value
         b = self.vars['bias'].value.buf if self.bias else None
-        if o % 4 == 0 and o <= d_in:
-            P = inf._table(e, graph.n_rows, o)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                ops.gemm(False, False, n, o, d_in, H.rows_slice(r0, r0 + n), W, P.rows_slice(r0, r0 + n), bias=b, stream=e.stream)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                graph.reduce(e, inf.CSR_MEAN_SELF, P, out.rows_slice(r0, r0 + n), r0, n, act=self.act_code)
-        else:
-            # (not _infer_reduce_sage: one matrix and no self operand)
-            means = e.ws_mat((self.name, "full_mean"), min(inf.WINDOW_ROWS, graph.n_rows), d_in, ld_multiple=32)
-            for r0, n in graph.windows(inf.WINDOW_ROWS):
-                graph.reduce(e, inf.CSR_MEAN_SELF, H, means, r0, n)
-                ops.sage_dense_fwd(None, None, means, None, n, None, W, o, False, self.act_code, b, out.rows_slice(r0, r0 + n),
-                                   stream=e.stream)
-        e.sync()
-        return out
-
-    def infer_rows(self, L, H):
-        """infer_full for the rows of L (inference.RowsLayer) only, into a compact [L.n, output_dim] table."""
-        from . import inference as inf
-        e = self.engine
-        o, d_in = self.output_dim, H.d
-        out = inf._table(e, L.n, o)
-        W = self.vars['weights'].value
-        b = self.vars['bias'].value.buf if self.bias else None
-        if o % 4 == 0 and o <= d_in:
-            P = inf._table(e, L.prev_n, o)
-            ops.gemm(False, False, L.prev_n, o, d_in, H, W, P, a_row_idx=L.prev_ids, bias=b, stream=e.stream)
-            L.reduce(e, inf.CSR_MEAN_SELF, P, out, L.prev_pos, act=self.act_code)
-        else:
-            means = inf._table(e, L.n, d_in, ld_multiple=32)
-            L.reduce(e, inf.CSR_MEAN_SELF, H, means, L.src_pos)
-            ops.sage_dense_fwd(None, None, means, None, L.n, None, W, o, False, self.act_code, b, out, stream=e.stream)
-        e.sync()
-        return out
+        if not (o % 4 == 0 and o <= d_in):
+            return scope.reduce_sage(self, CSR_MEAN_SELF, H, True, None, None, W, o, False, self.act_code, b)   # one matrix, no self
+        P = scope.dense(self, H, [(W, b, o, ACT_IDENTITY)])
+        return scope.reduce(self, CSR_MEAN_SELF, P, False, scope.table(self, o), self.act_code)
 
 
 class _PoolBase(_SageBase):
@@ -889,31 +828,13 @@ class _PoolingAggregator(_PoolBase):
         self._row_input_grads(saved, k, dz, dH, self.hidden_dim, mlp.vars['weights'].value, embed_sink, d_prev, prev_mask,
                               prev_offsets, drop=(lambda: self._drop(rate, SITE_MLP, k)) if rate > 0 else None)
 
-    def infer_full(self, graph, H):
-        """MeanAggregator.infer_full for the pooling layers: the MLP (aggregators.py:176-179) runs once per NODE, then the hidden
-        table is max- / mean-reduced over every node's whole neighbor list, then the SAGE matmuls."""
+    def infer(self, scope, H):
+        """The MLP (aggregators.py:176-179) runs once per row the layer may read, then the hidden table is max- / mean-reduced
+        over every computed row's whole neighbor list, then the SAGE matmuls."""
         from . import inference as inf
-        e = self.engine
-        o, d_in, hid = self.output_dim, H.d, self.hidden_dim
         mlp = self.mlp_layers[0]
-        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
-        Hh = inf._table(e, graph.n_rows, hid)
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            ops.gemm(False, False, n, hid, d_in, H.rows_slice(r0, r0 + n), mlp.vars['weights'].value, Hh.rows_slice(r0, r0 + n),
-                     bias=mlp.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
-        pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid)
-        return self._infer_reduce_sage(graph, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, pooled, H, out)
-
-    def infer_rows(self, L, H):
-        """infer_full for the rows of L (inference.RowsLayer) only: the MLP once per row this layer may read, the reduce and the
-        SAGE matmuls over the rows of L."""
-        from . import inference as inf
-        e = self.engine
-        mlp = self.mlp_layers[0]
-        Hh = inf._table(e, L.prev_n, self.hidden_dim)
-        ops.gemm(False, False, L.prev_n, self.hidden_dim, H.d, H, mlp.vars['weights'].value, Hh, a_row_idx=L.prev_ids,
-                 bias=mlp.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
-        return self._infer_rows_sage(L, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, L.prev_pos, self.hidden_dim, H)
+        Hh = scope.dense(self, H, [(mlp.vars['weights'].value, mlp.vars['bias'].value.buf, self.hidden_dim, ACT_RELU)])
+        return self._infer_sage(scope, inf.CSR_MAX if self.POOL == "max" else inf.CSR_MEAN, Hh, False, H)
 
 
 class MaxPoolingAggregator(_PoolingAggregator):
@@ -1009,12 +930,9 @@ class SeqAggregator(_SageBase):
         _pieces_wgrad(e, self.lstm_wx, pieces, dG)
         self._row_input_grads(saved, k, dz, dG, 4 * H, self.lstm_wx.value, None, d_prev, prev_mask, prev_offsets)
 
-    def infer_full(self, graph, H):
+    def infer(self, scope, H):
         raise ops._lib.GraphsageAmdError("SeqAggregator has no full-neighborhood form: an LSTM over a random permutation of a "
                                          "SAMPLE of the neighbors has no meaning over the whole list (use eval_step)")
-
-    def infer_rows(self, L, H):
-        return self.infer_full(L.graph, H)
 
 
 class TwoMaxLayerPoolingAggregator(_PoolBase):
@@ -1144,35 +1062,10 @@ class TwoMaxLayerPoolingAggregator(_PoolBase):
         _pieces_wgrad(e, W1, pieces, dH1)
         self._row_input_grads(saved, k, dz, dH1, hid1, W1.value, embed_sink, d_prev, prev_mask, prev_offsets)
 
-    def infer_full(self, graph, H):
-        """_PoolingAggregator.infer_full with both Dense layers run once per NODE, then the hid2-wide table is max-reduced over
-        every node's whole neighbor list, then the SAGE matmuls."""
-        from . import inference as inf
-        e = self.engine
-        o, d_in = self.output_dim, H.d
-        mlp1, mlp2 = self.mlp_layers
-        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
-        out = inf._table(e, graph.n_rows, o * (2 if self.concat else 1))
-        Hh2 = inf._table(e, graph.n_rows, hid2)
-        Hh1 = e.ws_mat((self.name, "full_h1"), min(inf.WINDOW_ROWS, graph.n_rows), hid1)
-        for r0, n in graph.windows(inf.WINDOW_ROWS):
-            ops.gemm(False, False, n, hid1, d_in, H.rows_slice(r0, r0 + n), mlp1.vars['weights'].value, Hh1.rows_slice(0, n),
-                     bias=mlp1.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
-            ops.gemm(False, False, n, hid2, hid1, Hh1.rows_slice(0, n), mlp2.vars['weights'].value, Hh2.rows_slice(r0, r0 + n),
-                     bias=mlp2.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
-        pooled = e.ws_mat((self.name, "full_pooled"), min(inf.WINDOW_ROWS, graph.n_rows), hid2)
-        return self._infer_reduce_sage(graph, inf.CSR_MAX, Hh2, pooled, H, out)
-
-    def infer_rows(self, L, H):
-        """infer_full for the rows of L (inference.RowsLayer) only: both Dense layers once per row this layer may read."""
-        from . import inference as inf
-        e = self.engine
-        mlp1, mlp2 = self.mlp_layers
-        hid1, hid2 = self.hidden_dim_1, self.hidden_dim_2
-        Hh1 = inf._table(e, L.prev_n, hid1)
-        Hh2 = inf._table(e, L.prev_n, hid2)
-        ops.gemm(False, False, L.prev_n, hid1, H.d, H, mlp1.vars['weights'].value, Hh1, a_row_idx=L.prev_ids,
-                 bias=mlp1.vars['bias'].value.buf, act=ACT_RELU, stream=e.stream)
-        ops.gemm(False, False, L.prev_n, hid2, hid1, Hh1, mlp2.vars['weights'].value, Hh2, bias=mlp2.vars['bias'].value.buf,
-                 act=ACT_RELU, stream=e.stream)
-        return self._infer_rows_sage(L, inf.CSR_MAX, Hh2, L.prev_pos, hid2, H)
+    def infer(self, scope, H):
+        """_PoolingAggregator.infer with both Dense layers run once per row the layer may read, then the hid2-wide table is
+        max-reduced."""
+        from .inference import CSR_MAX
+        stack = [(m.vars['weights'].value, m.vars['bias'].value.buf, width, ACT_RELU)
+                 for m, width in zip(self.mlp_layers, (self.hidden_dim_1, self.hidden_dim_2))]
+        return self._infer_sage(scope, CSR_MAX, scope.dense(self, H, stack), False, H)

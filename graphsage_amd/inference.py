@@ -362,9 +362,74 @@ def receptive_field(engine, graph, nodes, n_layers):
     return sets, maps, edges
 
 
+def _sage(e, H, self_ids, reduced, n, W_self, W_neigh, o, concat, act, bias, out):
+    """The SAGE matmuls over [rows self_ids of H | reduced] (H None: the one-matrix GCN call, no self operand)."""
+    ops.sage_dense_fwd(H, self_ids if H is not None else None, reduced, None, n, W_self, W_neigh, o, concat, act, bias, out,
+                       stream=e.stream)
+
+
+class GraphLayer(object):
+    """The scope of a layer computed for EVERY row of `graph` in row windows of WINDOW_ROWS (read at call time): it computes
+    and may read all n_rows rows, and every table is indexed by node id.  An aggregator's infer(scope, H) is written on the
+    output-table allocator `table` and the four primitives below it; RowsLayer offers the same five for a row subset.  `agg`
+    names the engine and the workspaces.  `of_src` (is X the layer's source table, or a `dense` table over the readable rows?)
+    only matters where the two are indexed differently, in RowsLayer's compact tables: here both are indexed by node id."""
+
+    def __init__(self, graph):
+        self.graph = graph
+
+    def _windows(self):
+        return self.graph.windows(WINDOW_ROWS)
+
+    def table(self, agg, d):
+        """A zeroed [computed rows, d] output table."""
+        return _table(agg.engine, self.graph.n_rows, d)
+
+    def dense(self, agg, H, stack):
+        """The Dense stack [(W, bias, width, act), ...] over every row the layer may read: a table indexed like those rows.
+        The intermediate of a two-layer stack lives in a per-window workspace."""
+        e = agg.engine
+        T = self.table(agg, stack[-1][2])
+        mid = e.ws_mat((agg.name, "full_h1"), min(WINDOW_ROWS, self.graph.n_rows), stack[0][2]) if len(stack) > 1 else None
+        for r0, n in self._windows():
+            X, k = H.rows_slice(r0, r0 + n), H.d
+            for i, (W, bias, width, act) in enumerate(stack):
+                Y = T.rows_slice(r0, r0 + n) if i + 1 == len(stack) else mid.rows_slice(0, n)
+                ops.gemm(False, False, n, width, k, X, W, Y, bias=bias, act=act, stream=e.stream)
+                X, k = Y, width
+        return T
+
+    def self_gemm(self, agg, H, W, width, dst, act):
+        """dst = act(computed rows of H . W): the self term into the output table or a column slice of it."""
+        for r0, n in self._windows():
+            ops.gemm(False, False, n, width, H.d, H.rows_slice(r0, r0 + n), W, dst.rows_slice(r0, r0 + n), act=act,
+                     stream=agg.engine.stream)
+
+    def reduce(self, agg, op, X, of_src, dst, act=ops.ACT_IDENTITY):
+        """dst = act(op over every computed row's whole neighbor list of the rows of X).  X is the layer's source table
+        (of_src) or a table over the readable rows (dense); dst the output table or a column slice of it."""
+        for r0, n in self._windows():
+            self.graph.reduce(agg.engine, op, X, dst.rows_slice(r0, r0 + n), r0, n, act=act)
+        return dst
+
+    def reduce_sage(self, agg, op, X, of_src, H, W_self, W_neigh, o, concat, act, bias):
+        """reduce X into a workspace of whole 128-byte lines per row, then the SAGE matmuls over [computed rows of H | reduced]
+        (H None: one matrix, no self operand).  Returns the output table."""
+        e = agg.engine
+        out = self.table(agg, o * (2 if concat else 1))
+        # ld_multiple=32 for every aggregator: the mean forms always had it; the pooling forms' hidden widths (256, 512, 1024:
+        # _PoolBase._WIDTHS) are multiples of 32, so their workspace keeps the leading dimension the default of 4 gave it
+        reduced = e.ws_mat((agg.name, "full_reduced"), min(WINDOW_ROWS, self.graph.n_rows), X.d, ld_multiple=32)
+        for r0, n in self._windows():
+            self.graph.reduce(e, op, X, reduced, r0, n)
+            _sage(e, H.rows_slice(r0, r0 + n) if H is not None else None, None, reduced, n, W_self, W_neigh, o, concat, act, bias,
+                  out.rows_slice(r0, r0 + n))
+        return out
+
+
 class RowsLayer(object):
-    """What one layer of layers_nodes hands to an aggregator's infer_rows: compute the layer for the rows `rows` (S_l, n of
-    them) into a compact [n, d_out] table, from the table `src` of the layer below.
+    """The scope of a layer of layers_nodes: compute the layer for the rows `rows` (S_l, n of them) into a compact [n, d_out]
+    table, from the table `src` of the layer below.  The same `table` and four primitives as GraphLayer.
 
       rows / rows_dev   S_l: ascending host ids / the same on the device (int32)
       out_pos           device map id -> row of the output table (pos of S_l)
@@ -383,8 +448,31 @@ class RowsLayer(object):
         self.self_ids = rows_dev if by_id else prev_pos[rows_dev.long()]
         self.plan = graph.upload_plan(engine, rows)
 
-    def reduce(self, engine, op, X, out, x_pos, act=ops.ACT_IDENTITY):
-        return self.graph.reduce_rows(engine, op, X, out, self.rows, self.out_pos, x_pos=x_pos, act=act, plan=self.plan)
+    def table(self, agg, d):
+        return _table(agg.engine, self.n, d)
+
+    def dense(self, agg, H, stack):
+        e = agg.engine
+        tables = [_table(e, self.prev_n, width) for _, _, width, _ in stack]
+        X, idx, k = H, self.prev_ids, H.d
+        for (W, bias, width, act), Y in zip(stack, tables):
+            ops.gemm(False, False, self.prev_n, width, k, X, W, Y, a_row_idx=idx, bias=bias, act=act, stream=e.stream)
+            X, idx, k = Y, None, width
+        return X
+
+    def self_gemm(self, agg, H, W, width, dst, act):
+        ops.gemm(False, False, self.n, width, H.d, H, W, dst, a_row_idx=self.self_ids, act=act, stream=agg.engine.stream)
+
+    def reduce(self, agg, op, X, of_src, dst, act=ops.ACT_IDENTITY):
+        return self.graph.reduce_rows(agg.engine, op, X, dst, self.rows, self.out_pos,
+                                      x_pos=self.src_pos if of_src else self.prev_pos, act=act, plan=self.plan)
+
+    def reduce_sage(self, agg, op, X, of_src, H, W_self, W_neigh, o, concat, act, bias):
+        out = self.table(agg, o * (2 if concat else 1))
+        reduced = _table(agg.engine, self.n, X.d, ld_multiple=32)
+        self.reduce(agg, op, X, of_src, reduced)
+        _sage(agg.engine, H, self.self_ids, reduced, self.n, W_self, W_neigh, o, concat, act, bias, out)
+        return out
 
 
 def layers_nodes(model, graph, nodes):
@@ -409,37 +497,41 @@ def layers_nodes(model, graph, nodes):
     return H, sets[0], maps[0], {"rows": [int(S.shape[0]) for S in sets], "edges": edges, "n_rows": graph.n_rows}
 
 
+def _gather(model, table, idx):
+    """(rows Mat [n, d], n): rows `idx` (host indices) of `table` on the device, at least one row allocated."""
+    import torch
+    e = model.engine
+    idx_dev = torch.from_numpy(idx.astype(np.int32)).to(e.device)
+    torch.cuda.synchronize()
+    out = _table(e, max(idx.size, 1), table.d)
+    if idx.size:
+        ops.gather_rows(table, idx_dev, out=out, stream=e.stream)
+    e.sync()
+    return out, int(idx.size)
+
+
 def request_rows(model, table, S, nodes):
     """(rows Mat [n, d], n): the rows of the compact table over the sorted distinct ids S in REQUEST order (a duplicate request
     is answered twice)."""
-    import torch
-    e = model.engine
-    ids = np.asarray(nodes).reshape(-1)
-    idx = np.searchsorted(S, ids).astype(np.int32)
-    idx_dev = torch.from_numpy(idx).to(e.device)
-    torch.cuda.synchronize()
-    out = _table(e, max(ids.size, 1), table.d)
-    if ids.size:
-        ops.gather_rows(table, idx_dev, out=out, stream=e.stream)
-    e.sync()
-    return out, int(ids.size)
+    return _gather(model, table, np.searchsorted(S, np.asarray(nodes).reshape(-1)))
 
 
 def select_rows(model, table, nodes):
     """(rows Mat [n, d], n): the rows `nodes` of a layer table (default: the N real nodes, in id order)."""
-    import torch
-    e = model.engine
     if nodes is None:
         return table.rows_slice(0, table.rows - 1), table.rows - 1
     ids = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int64)
     if ids.size and (ids.min() < 0 or ids.max() >= table.rows):
         raise GraphsageAmdError("node ids must lie in [0, %d]" % (table.rows - 1))
-    ids_dev = torch.from_numpy(ids.astype(np.int32)).to(e.device)
-    torch.cuda.synchronize()
-    out = _table(e, max(ids.size, 1), table.d)
-    ops.gather_rows(table, ids_dev, out=out, stream=e.stream)
-    e.sync()
-    return out, int(ids.size)
+    return _gather(model, table, ids)
+
+
+def l2_rows(engine, rows, n):
+    """The first n rows of `rows` l2-normalised (models.py:368-370) into a new table of at least one row; the launch is left on
+    the engine's stream."""
+    y = _table(engine, max(n, 1), rows.d)
+    ops.l2norm_fwd(rows, n, y, None, stream=engine.stream)
+    return y
 
 
 # ---------------------------------------------------------------------------------------------------- link ranking
@@ -514,6 +606,25 @@ def rank_metrics(n_gt, n_eq, hits=(1, 10, 50, 100)):
             "hits": {int(k): (float(np.mean(ranks <= k)) if ranks.size else 0.0) for k in hits}}
 
 
+def _queries(engine, Z, ids, filt, weights, who):
+    """What rank_full and topk_full do before their launch: (src, Xq, f_rowptr, f_col) = the query ids on the device, their rows
+    of Z (times the bilinear weights, if any) and the filter's device CSR.  Ends with everything torch's stream did in order."""
+    import torch
+    e = engine
+    if weights is not None and (weights.rows != Z.d or weights.d != Z.d):
+        raise GraphsageAmdError("%s: bilinear weights must be [%d, %d]" % (who, Z.d, Z.d))
+    src = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(e.device)
+    f_rowptr, f_col = filt.on(e.device, Z.rows) if filt is not None else (None, None)
+    Xq = _table(e, src.numel(), Z.d)
+    U = _table(e, src.numel(), Z.d) if weights is not None else None
+    torch.cuda.synchronize()              # uploads and zero-fills ran on torch's stream; order them before the engine's
+    ops.gather_rows(Z, src, out=Xq, stream=e.stream)
+    if weights is not None:
+        ops.gemm(False, False, src.numel(), Z.d, Z.d, Xq, weights, U, stream=e.stream)
+        Xq = U
+    return src, Xq, f_rowptr, f_col
+
+
 def rank_full(engine, Z, edges, *, n_cand=None, filt=None, exclude_self=True, weights=None, hits=(1, 10, 50, 100)):
     """Rank the true partner of every edge (src, dst) among the rows 0 .. n_cand - 1 of the device table Z ([n_rows, d] Mat): the
     score of a candidate w is <Z[src], Z[w]>, or <Z[src] . A, Z[w]> with the bilinear weights A ([d, d] Mat, prediction.py:68-92,
@@ -533,24 +644,12 @@ def rank_full(engine, Z, edges, *, n_cand=None, filt=None, exclude_self=True, we
         res["scores"] = np.zeros(0, np.float32)
         return res
     e = engine
-    src = torch.from_numpy(np.ascontiguousarray(edges[:, 0], dtype=np.int32)).to(e.device)
     dst = torch.from_numpy(np.ascontiguousarray(edges[:, 1], dtype=np.int32)).to(e.device)
-    f_rowptr = f_col = None
-    if filt is not None:
-        f_rowptr, f_col = filt.on(e.device, Z.rows)
-    Xq = _table(e, Q, Z.d)
     out = (torch.zeros(Q, dtype=torch.float32, device=e.device), torch.zeros(Q, dtype=torch.int32, device=e.device),
            torch.zeros(Q, dtype=torch.int32, device=e.device))
     ws = torch.zeros(max(2, max(ops.rank_ws_bytes(n, n_cand) for n in {min(Q, ops.RANK_CHUNK), Q % ops.RANK_CHUNK}) // 4),
                      dtype=torch.int32, device=e.device)
-    torch.cuda.synchronize()              # uploads and zero-fills ran on torch's stream; order them before the engine's
-    ops.gather_rows(Z, src, out=Xq, stream=e.stream)
-    if weights is not None:
-        if weights.rows != Z.d or weights.d != Z.d:
-            raise GraphsageAmdError("rank_full: bilinear weights must be [%d, %d]" % (Z.d, Z.d))
-        U = _table(e, Q, Z.d)
-        ops.gemm(False, False, Q, Z.d, Z.d, Xq, weights, U, stream=e.stream)
-        Xq = U
+    src, Xq, f_rowptr, f_col = _queries(e, Z, edges[:, 0], filt, weights, "rank_full")
     ops.rank_count(Xq, Z, dst, n_cand=n_cand, src=src if (exclude_self or filt is not None) else None,
                    keep_src=not exclude_self, f_rowptr=f_rowptr,
                    f_col=f_col, t=out[0], n_gt=out[1], n_eq=out[2], ws=ws, stream=e.stream)
@@ -582,23 +681,11 @@ def topk_full(engine, Z, nodes, k, *, n_cand=None, filt=None, exclude_self=True,
     if Q == 0:
         return {"ids": np.zeros((0, k), np.int32), "scores": np.zeros((0, k), np.float32), "count": np.zeros(0, np.int32)}
     e = engine
-    src = torch.from_numpy(nodes.astype(np.int32)).to(e.device)
-    f_rowptr = f_col = None
-    if filt is not None:
-        f_rowptr, f_col = filt.on(e.device, Z.rows)
-    Xq = _table(e, Q, Z.d)
     out = (torch.zeros((Q, k), dtype=torch.int32, device=e.device), torch.zeros((Q, k), dtype=torch.float32, device=e.device),
            torch.zeros(Q, dtype=torch.int32, device=e.device))
     need = max(ops.topk_ws_bytes(n, n_cand, k) for n in {min(Q, ops.RANK_CHUNK), Q % ops.RANK_CHUNK})
     ws = torch.zeros(max(1, (need + 7) // 8), dtype=torch.int64, device=e.device)
-    torch.cuda.synchronize()              # uploads and zero-fills ran on torch's stream; order them before the engine's
-    ops.gather_rows(Z, src, out=Xq, stream=e.stream)
-    if weights is not None:
-        if weights.rows != Z.d or weights.d != Z.d:
-            raise GraphsageAmdError("topk_full: bilinear weights must be [%d, %d]" % (Z.d, Z.d))
-        U = _table(e, Q, Z.d)
-        ops.gemm(False, False, Q, Z.d, Z.d, Xq, weights, U, stream=e.stream)
-        Xq = U
+    src, Xq, f_rowptr, f_col = _queries(e, Z, nodes, filt, weights, "topk_full")
     ops.topk_select(Xq, Z, k, n_cand=n_cand, src=src if (exclude_self or filt is not None) else None,
                     keep_src=not exclude_self, f_rowptr=f_rowptr, f_col=f_col, ids=out[0], scores=out[1], count=out[2], ws=ws,
                     stream=e.stream)

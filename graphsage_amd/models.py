@@ -993,11 +993,12 @@ class SampleAndAggregate(object):
         """l2-normalised embeddings (models.py:368-370) [n, d] (NumPy) of `nodes` (default: all N real nodes in id order) from
         the exact layer-wise pass over `graph` (inference.FullGraph): every layer for every node from ALL its neighbors."""
         from . import inference as inf
-        e = self.engine
-        rows, n = inf.select_rows(self, inf.layers_full(self, graph), nodes)
-        y = inf._table(e, max(n, 1), rows.d)
-        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
-        e.sync()
+        return self._l2_numpy(*inf.select_rows(self, inf.layers_full(self, graph), nodes))
+
+    def _l2_numpy(self, rows, n):
+        from . import inference as inf
+        y = inf.l2_rows(self.engine, rows, n)
+        self.engine.sync()
         return y.numpy()[:n]
 
     def embed_nodes(self, graph, nodes):
@@ -1007,26 +1008,23 @@ class SampleAndAggregate(object):
         N + 1}.  The values agree with embed_full to the float tolerance, not bitwise: the contractions may take another tile
         form at another row count."""
         from . import inference as inf
-        e = self.engine
         H, S, _, stats = inf.layers_nodes(self, graph, nodes)
-        rows, n = inf.request_rows(self, H, S, nodes)
-        y = inf._table(e, max(n, 1), rows.d)
-        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
-        e.sync()
-        return y.numpy()[:n], stats
+        return self._l2_numpy(*inf.request_rows(self, H, S, nodes)), stats
+
+    def _exact_table(self, graph):
+        """The l2-normalised exact table of `graph` [N + 1, d], pad row included, kept on the device (Mat)."""
+        from . import inference as inf
+        H = inf.layers_full(self, graph)
+        return inf.l2_rows(self.engine, H, H.rows)
 
     def rank_full(self, graph, edges, filtered=True, hits=(1, 10, 50, 100)):
         """Rank the true partner of every edge (src, dst) among ALL N nodes with the exact embeddings of `graph` (the table of
         embed_full, kept on the device): inference.rank_full with n_cand = N (the pad row is never a candidate), the query
         node left out, the edges of `graph` filtered (filtered=True) and the head's bilinear weights if it has them."""
         from . import inference as inf
-        e = self.engine
-        H = inf.layers_full(self, graph)
-        Z = inf._table(e, H.rows, H.d)
-        ops.l2norm_fwd(H, H.rows, Z, None, stream=e.stream)
-        filt = graph.rank_filter() if filtered else None
         W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
-        return inf.rank_full(e, Z, edges, n_cand=graph.n_nodes, filt=filt, weights=W, hits=hits)
+        return inf.rank_full(self.engine, self._exact_table(graph), edges, n_cand=graph.n_nodes,
+                             filt=graph.rank_filter() if filtered else None, weights=W, hits=hits)
 
     def topk_full(self, graph, nodes=None, k=10, filtered=True):
         """The k best-scoring partners of `nodes` (default: all N real nodes in id order) among ALL N nodes with the exact
@@ -1034,15 +1032,9 @@ class SampleAndAggregate(object):
         never a candidate), the query node left out, the edges of `graph` filtered (filtered=True) and the head's bilinear weights
         if it has them.  Returns {"ids": int32 [n, k], "scores": float32 [n, k], "count": int32 [n]}."""
         from . import inference as inf
-        e = self.engine
-        H = inf.layers_full(self, graph)
-        Z = inf._table(e, H.rows, H.d)
-        ops.l2norm_fwd(H, H.rows, Z, None, stream=e.stream)
-        filt = graph.rank_filter() if filtered else None
         W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
-        if nodes is None:
-            nodes = np.arange(graph.n_nodes)
-        return inf.topk_full(e, Z, nodes, k, n_cand=graph.n_nodes, filt=filt, weights=W)
+        return inf.topk_full(self.engine, self._exact_table(graph), np.arange(graph.n_nodes) if nodes is None else nodes, k,
+                             n_cand=graph.n_nodes, filt=graph.rank_filter() if filtered else None, weights=W)
 
     # ------------------------------------------------------------------------------ step machinery (shared)
     def _samplers(self):

@@ -243,18 +243,23 @@ def csr_reduce_ws_bytes(n_slots, d):
     return out.value
 
 
-def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, row0, n, item_range, split_range, slot_range,
-                   ws=None, act=ACT_IDENTITY, stream=None):
-    """gs_csr_reduce_fwd: out[r - row0] = mean | mean-with-self | max over the whole neighbor list of row r of X's rows, for the
-    window [row0, row0 + n) of a planned CSR graph (inference.FullGraph owns the plan and has checked the column ids)."""
-    q = _lib.CsrReduceDesc()
+def _csr_desc(q, rowptr, col, items, splits, n_rows, split_len, op, X, out, ws, act):
+    """The fields CsrReduceDesc and CsrRowsDesc have in common."""
     q.rowptr, q.col, q.items, q.splits = ptr(rowptr), ptr(col), ptr(items), ptr(splits)
     q.X, q.out, q.ws = X.ptr, out.ptr, ptr(ws)
     q.n_rows, q.nnz, q.n_items, q.n_split = n_rows, col.numel(), items.shape[0], (splits.shape[0] if splits is not None else 0)
     q.ldx, q.x_rows, q.ldo, q.ws_bytes = X.ld, X.rows, out.ld, (4 * ws.numel() if ws is not None else 0)
+    q.d, q.op, q.act, q.split_len = X.d, op, act, split_len
+    return q
+
+
+def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, row0, n, item_range, split_range, slot_range,
+                   ws=None, act=ACT_IDENTITY, stream=None):
+    """gs_csr_reduce_fwd: out[r - row0] = mean | mean-with-self | max over the whole neighbor list of row r of X's rows, for the
+    window [row0, row0 + n) of a planned CSR graph (inference.FullGraph owns the plan and has checked the column ids)."""
+    q = _csr_desc(_lib.CsrReduceDesc(), rowptr, col, items, splits, n_rows, split_len, op, X, out, ws, act)
     q.row0, q.n = row0, n
     (q.item0, q.item1), (q.split0, q.split1), (q.slot0, q.slot1) = item_range, split_range, slot_range
-    q.d, q.op, q.act, q.split_len = X.d, op, act, split_len
     call("gs_csr_reduce_fwd", ctypes.addressof(q), _s(stream))
     return out
 
@@ -267,14 +272,8 @@ def csr_reduce_rows(rowptr, col, items, splits, n_rows, split_len, op, X, out, o
     for name, m in (("out_pos", out_pos), ("x_pos", x_pos)):
         if m is not None and (m.dtype != torch.int32 or m.numel() != n_rows):
             raise _lib.GraphsageAmdError("csr_reduce_rows: %s must be an int32 vector of n_rows = %d entries" % (name, n_rows))
-    q = _lib.CsrRowsDesc()
-    q.rowptr, q.col, q.items, q.splits = ptr(rowptr), ptr(col), ptr(items), ptr(splits)
-    q.x_pos, q.out_pos = ptr(x_pos), ptr(out_pos)
-    q.X, q.out, q.ws = X.ptr, out.ptr, ptr(ws)
-    q.n_rows, q.nnz, q.n_items, q.n_split = n_rows, col.numel(), items.shape[0], (splits.shape[0] if splits is not None else 0)
-    q.n_slots = n_slots
-    q.ldx, q.x_rows, q.ldo, q.out_rows, q.ws_bytes = X.ld, X.rows, out.ld, out.rows, (4 * ws.numel() if ws is not None else 0)
-    q.d, q.op, q.act, q.split_len = X.d, op, act, split_len
+    q = _csr_desc(_lib.CsrRowsDesc(), rowptr, col, items, splits, n_rows, split_len, op, X, out, ws, act)
+    q.x_pos, q.out_pos, q.n_slots, q.out_rows = ptr(x_pos), ptr(out_pos), n_slots, out.rows
     call("gs_csr_reduce_rows", ctypes.addressof(q), _s(stream))
     return out
 
@@ -309,6 +308,27 @@ def rank_ws_bytes(Q, n_cand):
     return out.value
 
 
+def _query_desc(q, who, Xq, Zc, Q, n_cand, f_rowptr, f_col, keep_src):
+    """The width and filter checks of rank_count and topk_select (`who`: the message prefix and what follows the shapes), made
+    before anything is allocated or asked of the library, and the fields RankDesc and TopkDesc have in common but for the
+    workspace."""
+    if Xq.d != Zc.d or Xq.rows < Q:
+        raise _lib.GraphsageAmdError("%s: Xq is [%d, %d], Zc [%d, %d]%s" % (who[0], Xq.rows, Xq.d, Zc.rows, Zc.d, who[1]))
+    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
+            f_rowptr.dtype != torch.int64 or f_col.dtype != torch.int32 or f_rowptr.numel() != Zc.rows + 1)):
+        raise _lib.GraphsageAmdError("%s: the filter is an int64 rowptr [n_rows + 1] with an int32 col" % who[0])
+    q.Zc, q.f_rowptr, q.f_col = Zc.ptr, ptr(f_rowptr), ptr(f_col)
+    q.n_rows, q.n_cand, q.ldz, q.ldq = Zc.rows, n_cand, Zc.ld, Xq.ld
+    q.f_nnz, q.d, q.flags = (f_col.numel() if f_col is not None else 0), Xq.d, (_lib.RANK_KEEP_SRC if keep_src else 0)
+    return q
+
+
+def _query_chunks(Q):
+    """(q0, n) of every RANK_CHUNK of Q queries (one empty chunk when Q == 0)."""
+    for q0 in range(0, max(Q, 1), RANK_CHUNK):
+        yield q0, min(RANK_CHUNK, Q - q0)
+
+
 def rank_count(Xq, Zc, dst, n_cand=None, src=None, f_rowptr=None, f_col=None, t=None, n_gt=None, n_eq=None, ws=None,
                keep_src=False, stream=None):
     """gs_rank_count: t[q] = <Xq[q], Zc[dst[q]]> and the numbers of candidates w < n_cand (dst[q], src[q] and the filter row
@@ -317,13 +337,9 @@ def rank_count(Xq, Zc, dst, n_cand=None, src=None, f_rowptr=None, f_col=None, t=
     keep_src: src[q] stays a candidate and only names the filter row (GS_RANK_KEEP_SRC).  Returns (t, n_gt, n_eq)."""
     Q = dst.numel()
     n_cand = Zc.rows if n_cand is None else int(n_cand)
-    if Xq.d != Zc.d or Xq.rows < Q:
-        raise _lib.GraphsageAmdError("rank_count: Xq is [%d, %d], Zc [%d, %d], %d queries" % (Xq.rows, Xq.d, Zc.rows, Zc.d, Q))
+    q = _query_desc(_lib.RankDesc(), ("rank_count", ", %d queries" % Q), Xq, Zc, Q, n_cand, f_rowptr, f_col, keep_src)
     if dst.dtype != torch.int32 or (src is not None and (src.dtype != torch.int32 or src.numel() != Q)):
         raise _lib.GraphsageAmdError("rank_count: dst and src must be int32 vectors of the same length")
-    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
-            f_rowptr.dtype != torch.int64 or f_col.dtype != torch.int32 or f_rowptr.numel() != Zc.rows + 1)):
-        raise _lib.GraphsageAmdError("rank_count: the filter is an int64 rowptr [n_rows + 1] with an int32 col")
     dev = dst.device
     t = torch.empty(Q, dtype=torch.float32, device=dev) if t is None else t
     n_gt = torch.empty(Q, dtype=torch.int32, device=dev) if n_gt is None else n_gt
@@ -331,15 +347,9 @@ def rank_count(Xq, Zc, dst, n_cand=None, src=None, f_rowptr=None, f_col=None, t=
     need = max(rank_ws_bytes(n, n_cand) for n in {min(Q, RANK_CHUNK), Q % RANK_CHUNK})      # the two chunk sizes that occur
     if ws is None:
         ws = torch.empty(max(need // 4, 2), dtype=torch.int32, device=dev)
-    q = _lib.RankDesc()
-    q.Zc, q.f_rowptr, q.f_col, q.ws = Zc.ptr, ptr(f_rowptr), ptr(f_col), ptr(ws)
-    q.n_rows, q.n_cand, q.ldz, q.ldq = Zc.rows, n_cand, Zc.ld, Xq.ld
-    q.f_nnz, q.ws_bytes, q.d = (f_col.numel() if f_col is not None else 0), 4 * ws.numel(), Xq.d
-    q.flags = _lib.RANK_KEEP_SRC if keep_src else 0
-    for q0 in range(0, max(Q, 1), RANK_CHUNK):
-        n = min(RANK_CHUNK, Q - q0)
-        q.Q = n
-        q.Xq = Xq.ptr + 4 * q0 * Xq.ld
+    q.ws, q.ws_bytes = ptr(ws), 4 * ws.numel()
+    for q0, n in _query_chunks(Q):
+        q.Q, q.Xq = n, Xq.ptr + 4 * q0 * Xq.ld
         q.dst, q.src = ptr(dst[q0:q0 + n]), (ptr(src[q0:q0 + n]) if src is not None else None)
         q.t, q.n_gt, q.n_eq = ptr(t[q0:q0 + n]), ptr(n_gt[q0:q0 + n]), ptr(n_eq[q0:q0 + n])
         call("gs_rank_count", ctypes.addressof(q), _s(stream))
@@ -366,15 +376,11 @@ def topk_select(Xq, Zc, k, n_cand=None, src=None, f_rowptr=None, f_col=None, kee
     float32 [Q, k], count int32 [Q]); entries at and beyond count[q] = min(k, candidates of q) are -1 / -inf."""
     Q, k = Xq.rows, int(k)
     n_cand = Zc.rows if n_cand is None else int(n_cand)
-    if Xq.d != Zc.d:
-        raise _lib.GraphsageAmdError("topk_select: Xq is [%d, %d], Zc [%d, %d]" % (Xq.rows, Xq.d, Zc.rows, Zc.d))
+    q = _query_desc(_lib.TopkDesc(), ("topk_select", ""), Xq, Zc, Q, n_cand, f_rowptr, f_col, keep_src)
     if not 1 <= k <= TOPK_MAX:
         raise _lib.GraphsageAmdError("topk_select: k=%d must lie in [1, %d]" % (k, TOPK_MAX))
     if src is not None and (src.dtype != torch.int32 or src.numel() != Q):
         raise _lib.GraphsageAmdError("topk_select: src must be an int32 vector with one entry per query")
-    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
-            f_rowptr.dtype != torch.int64 or f_col.dtype != torch.int32 or f_rowptr.numel() != Zc.rows + 1)):
-        raise _lib.GraphsageAmdError("topk_select: the filter is an int64 rowptr [n_rows + 1] with an int32 col")
     dev = Xq.buf.device
     ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if ids is None else ids
     scores = torch.empty((Q, k), dtype=torch.float32, device=dev) if scores is None else scores
@@ -386,15 +392,9 @@ def topk_select(Xq, Zc, k, n_cand=None, src=None, f_rowptr=None, f_col=None, kee
     need = max(topk_ws_bytes(n, n_cand, k) for n in {min(Q, RANK_CHUNK), Q % RANK_CHUNK})     # the two chunk sizes that occur
     if ws is None:
         ws = torch.empty(max((need + 7) // 8, 1), dtype=torch.int64, device=dev)
-    q = _lib.TopkDesc()
-    q.Zc, q.f_rowptr, q.f_col, q.ws = Zc.ptr, ptr(f_rowptr), ptr(f_col), ptr(ws)
-    q.n_rows, q.n_cand, q.ldz, q.ldq = Zc.rows, n_cand, Zc.ld, Xq.ld
-    q.f_nnz, q.ws_bytes = (f_col.numel() if f_col is not None else 0), ws.element_size() * ws.numel()
-    q.d, q.k, q.flags = Xq.d, k, (_lib.RANK_KEEP_SRC if keep_src else 0)
-    for q0 in range(0, max(Q, 1), RANK_CHUNK):
-        n = min(RANK_CHUNK, Q - q0)
-        q.Q = n
-        q.Xq = Xq.ptr + 4 * q0 * Xq.ld
+    q.ws, q.ws_bytes, q.k = ptr(ws), ws.element_size() * ws.numel(), k
+    for q0, n in _query_chunks(Q):
+        q.Q, q.Xq = n, Xq.ptr + 4 * q0 * Xq.ld
         q.src = ptr(src[q0:q0 + n]) if src is not None else None
         q.ids, q.scores, q.count = ptr(ids[q0:q0 + n]), ptr(scores[q0:q0 + n]), ptr(count[q0:q0 + n])
         call("gs_topk_select", ctypes.addressof(q), _s(stream))

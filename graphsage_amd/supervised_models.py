@@ -364,9 +364,8 @@ class SupervisedGraphsage(SampleAndAggregate):
         from . import inference as inf
         e = self.engine
         C = self.num_classes
-        y = inf._table(e, max(n, 1), rows.d)
         preds = inf._table(e, max(n, 1), C)
-        ops.l2norm_fwd(rows, n, y, None, stream=e.stream)
+        y = inf.l2_rows(e, rows, n)
         w = min(inf.WINDOW_ROWS, max(n, 1))
         logits = e.ws_mat((self.name, "full_logits"), w, C)
         no_labels = e.ws_mat((self.name, "full_no_labels"), w, C)          # gs_class_loss also forms the loss: unused here
