@@ -148,6 +148,9 @@ _PROTOS = {
     "gs_unique_ids": [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P],
     "gs_dense_fwd_rows_dev": [_P, c_int64, _P, c_int32, c_int64, _P, _P, c_int64, c_int32, c_int, _P, _P, c_int64, _P],
     "gs_segment_max_gather_fwd": [_P, c_int64, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
+    "gs_segment_attn_fwd": [_P, c_int64, _P, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, _P],
+    "gs_segment_attn_bwd": [_P, c_int64, _P, c_int64, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, c_int32, _P],
+    "gs_attn_scores": [_P, c_int64, c_int64, c_int32, _P, _P],
     "gs_sample_fanout_desc": [_P, _P],
     "gs_build_padded_table": [_P, _P, c_int64, c_int32, c_int32, c_uint64, _P, _P],
     "gs_finalize_step2": [_P, c_int64, c_float, _P, c_int, _P, c_float, _P, _P, c_uint64, _P, c_uint64, _P, c_uint64, _P],
@@ -280,7 +283,7 @@ class LstmSeg(ctypes.Structure):
 
 assert ctypes.sizeof(LstmSeg) == 56      # static_assert in csrc/gs_lstm.hip (passed by pointer, not in gs_abi_struct_sizes)
 
-CSR_MEAN, CSR_MEAN_SELF, CSR_MAX = 0, 1, 2          # GS_CSR_* (ops of gs_csr_reduce_fwd)
+CSR_MEAN, CSR_MEAN_SELF, CSR_MAX, CSR_SOFTMAX = 0, 1, 2, 3          # GS_CSR_* (ops of gs_csr_reduce_fwd)
 
 
 class CsrReduceDesc(ctypes.Structure):

@@ -1,5 +1,5 @@
 """Mean / GCN / MaxPooling / MeanPooling / Seq (LSTM) aggregators with the constructor and call signatures of
-graphsage/aggregators.py, executing on the gfx950 kernels.
+graphsage/aggregators.py, executing on the gfx950 kernels; AttentionPoolingAggregator, which the reference does not have, shares them.
 
     agg = MeanAggregator(input_dim, output_dim, act=..., dropout=..., name=..., concat=..., model_size=...)
     out = agg((self_vecs, neigh_vecs))        # models.py:326-327
@@ -18,6 +18,7 @@ from collections import namedtuple
 import torch
 
 from . import ops
+from .engine import MAX_SLABS
 from .inits import glorot, zeros
 from .layers import SITE_MLP, SITE_NEIGH, SITE_SELF, Dense, Layer, Rows, _act_code, _rate, relu
 from .ops import ACT_IDENTITY, ACT_RELU, Mat
@@ -26,6 +27,7 @@ from .ops import ACT_IDENTITY, ACT_RELU, Mat
 _MeanSaved = namedtuple("_MeanSaved", "self_all neighs means out rate self_in h0", defaults=(None, None))   # Mean and GCN
 _PoolSaved = namedtuple("_PoolSaved", "self_all neighs pieces rows_total H pooled argmax out rate")
 _Pool2Saved = namedtuple("_Pool2Saved", "self_all neighs pieces rows_total H1 inv pooled argmax out")
+_AttnSaved = namedtuple("_AttnSaved", "self_all neighs pieces rows_total H inv alpha pooled out rate")
 _SeqSaved = namedtuple("_SeqSaved", "self_all neighs pieces rows_total segs lengths gates C Hp h_last out")
 
 
@@ -845,6 +847,113 @@ class MaxPoolingAggregator(_PoolingAggregator):
 class MeanPoolingAggregator(_PoolingAggregator):
     """Aggregates via mean-pooling over MLP functions (aggregators.py:197-273)."""
     POOL = "mean"
+
+
+class AttentionPoolingAggregator(_PoolBase):
+    """Aggregates via attention pooling over an MLP function: the pooling aggregators' relu-Dense over every neighbor row, then a
+    LEARNED weighting of the s rows instead of their max or mean, then the SAGE matmuls (DESIGN "Attention pooling"):
+
+        V_j = relu(x_j . W_mlp + b_mlp);  t_j = <V_j, a>;  alpha = softmax_j(t_j);  pooled = sum_j alpha_j V_j
+
+    hidden = 512 ("small") or 1024 ("big").  The gate `a` [hidden] (glorot as a [hidden, 1] matrix), like the Dense, is not in
+    aggregator.vars (no weight decay; still clipped and updated by Adam).  The gate does not depend on the node that asks, so the
+    Dense runs once per DISTINCT sampled id where _dedup_wanted says so and the attention reads through the index
+    (gs_segment_attn_fwd / _bwd, csrc/gs_attn.hip).  Dropout applies to the Dense's input rows, as in _PoolingAggregator."""
+    _WIDTHS = {"small": (512,), "big": (1024,)}
+    hidden_dim = property(lambda self: self._widths[0])
+
+    def __init__(self, input_dim, output_dim, model_size="small", **kwargs):
+        super(AttentionPoolingAggregator, self).__init__(input_dim, output_dim, model_size=model_size, **kwargs)
+        if not ops.segment_attn_supported(1, self.hidden_dim):
+            raise ops._lib.GraphsageAmdError("AttentionPoolingAggregator: hidden width %d outside the kernels' range" % self.hidden_dim)
+        self.attn_a = self.engine.add_variable(self.name + '/attn_vars/a', glorot((self.hidden_dim, 1)).reshape(-1), decay=False)
+
+    @staticmethod
+    def check_samples(num_samples):
+        """Refuse a fan-out outside the range of gs_segment_attn_fwd / _bwd (the drivers call this before training)."""
+        for s in num_samples:
+            if not 1 <= int(s) <= ops.ATTN_MAX_S:
+                raise ops._lib.GraphsageAmdError("graphsage_attn takes 1 <= samples <= %d per layer (got %d)" % (ops.ATTN_MAX_S, s))
+
+    def call_hops(self, self_all, neighs, means=None, side_jobs=None):
+        e = self.engine
+        _run_jobs(e, side_jobs)
+        self.check_samples([nv.shape3[1] for nv in neighs])
+        n_total = self_all.n
+        k = len(self._saved)
+        rate = _rate(self.dropout)
+        mlp = self.mlp_layers[0]
+        hid = self.hidden_dim
+        a = self.attn_a.value.buf
+        _, x_all, pieces, rows_total = _flatten(neighs)
+        pooled = e.ws_mat((self.name, "pooled", k), n_total, hid)
+        alpha = e.ws_f32((self.name, "alpha", k), rows_total)
+        self.last_pool_kernel = self.last_unique = None
+        inv = None
+        if rate == 0 and self._dedup_wanted(x_all, rows_total):
+            # the Dense once per DISTINCT id of the step; the attention picks its rows through `inv`
+            H, inv, cnt = self._mlp_distinct(mlp, hid, x_all, rows_total, k)
+            self.last_unique = (cnt, rows_total)
+        else:
+            H = e.ws_mat((self.name, "H", k), rows_total, hid)
+            if rate > 0:
+                # the Dense's x = tf.nn.dropout(x, 1 - dropout) over every gathered neighbor row (as _PoolingAggregator)
+                dropped, r = [], 0
+                for i, x in enumerate(pieces):
+                    xd = e.ws_mat((self.name, "x_drop", k, i), x.n, x.src.d)
+                    ops.dropout_rows(x.src, x.ids, x.n, self._drop(rate, SITE_MLP, k, r), xd, stream=e.stream)
+                    dropped.append(Rows(xd, None, x.n, x.requires_grad))
+                    r += x.n
+                pieces = dropped
+            _pieces_fwd(e, pieces, mlp.vars['weights'].value, mlp.vars['bias'].value.buf, hid, ACT_RELU, H)
+        for h, nv, n, s, r, hr in _hops(neighs):
+            ops.segment_attn_fwd(H if inv is not None else H.rows_slice(hr, hr + n * s), inv[hr:hr + n * s] if inv is not None else None,
+                                 a, n, s, pooled.rows_slice(r, r + n), alpha[hr:hr + n * s], stream=e.stream)
+        out = self._sage_out(self_all, pooled, n_total, k)
+        self._push(_AttnSaved(self_all, neighs, pieces, rows_total, H, inv, alpha, pooled, out, rate))
+        return out
+
+    def backward_hops(self, d_out, pre_masked=False, d_prev=None, prev_mask=None, prev_offsets=None, embed_sink=None):
+        e = self.engine
+        saved = self._saved.pop()
+        self_all, neighs, pieces, rows_total, H, inv, alpha, pooled, out, rate = saved
+        n_total = self_all.n
+        k = len(self._saved)
+        hid = self.hidden_dim
+        mlp = self.mlp_layers[0]
+        var_a = self.attn_a
+        dz, col_n = self._sage_bwd(d_out, out, n_total, pre_masked, self_all.src, self_all.ids, pooled)
+        d_pooled = e.ws_mat((self.name, "d_pooled", k), n_total, hid)
+        ops.dense_dgrad(dz, col_n, self.output_dim, n_total, self.vars['neigh_weights'].value, d_pooled, stream=e.stream)
+        # softmax and gate gradients, then the Dense's relu: dV per SAMPLED row; da as slabs of the gate's arena, one per workgroup
+        dV = e.ws_mat((self.name, "dV", k), rows_total, hid)
+        # a slab is a workgroup, and the hops' launches follow each other: the sum of rows_h / slabs_h is least where the gate's
+        # free slabs go to the hops by the SQUARE ROOT of their sampled rows (Reddit's layer 0: 11 for the 512 groups of 10, 52
+        # for the 5120 groups of 25); at least one each and no more than a hop has groups of 16
+        free = MAX_SLABS - var_a.n_slabs - len(neighs)
+        roots = [(nv.shape3[0] * nv.shape3[1]) ** 0.5 for nv in neighs]
+        for h, nv, n, s, r, hr in _hops(neighs):
+            n_slabs = int(max(1, min(1 + int(max(free, 0) * roots[h] / sum(roots)), (n + 15) // 16)))
+            if var_a.n_slabs + n_slabs > MAX_SLABS:
+                raise ops._lib.GraphsageAmdError("slab arena of %s exhausted" % var_a.name)
+            ops.segment_attn_bwd(d_pooled.rows_slice(r, r + n), H if inv is not None else H.rows_slice(hr, hr + n * s),
+                                 inv[hr:hr + n * s] if inv is not None else None, var_a.value.buf, alpha[hr:hr + n * s], n, s,
+                                 dV.rows_slice(hr, hr + n * s), n_slabs, var_a.slab_ptr(var_a.n_slabs), stream=e.stream)
+            var_a.n_slabs += n_slabs
+        e.bgrad(mlp.vars['bias'], dV, rows_total, hid)
+        _pieces_wgrad(e, mlp.vars['weights'], pieces, dV)
+        self._row_input_grads(saved, k, dz, dV, hid, mlp.vars['weights'].value, embed_sink, d_prev, prev_mask, prev_offsets,
+                              drop=(lambda: self._drop(rate, SITE_MLP, k)) if rate > 0 else None)
+
+    def infer(self, scope, H):
+        """The Dense once per row the layer may read, into a table with one spare column; the gate's score of every such row into
+        that column (gs_attn_scores); then the softmax-weighted sum over every computed row's WHOLE neighbor list (a duplicate
+        entry counts as often as it occurs) and the SAGE matmuls."""
+        from .inference import CSR_SOFTMAX
+        mlp = self.mlp_layers[0]
+        Hh = scope.dense(self, H, [(mlp.vars['weights'].value, mlp.vars['bias'].value.buf, self.hidden_dim, ACT_RELU)], spare=4)
+        ops.attn_scores(Hh, self.attn_a.value.buf, stream=self.engine.stream)
+        return self._infer_sage(scope, CSR_SOFTMAX, Hh, False, H)
 
 
 class SeqAggregator(_SageBase):

@@ -19,7 +19,8 @@ single neighbor N (a mean or max of identical entries is that entry).
 
 The split rule.  One wave reduces one work item; a row longer than `split_len` (512) edges is cut into items of at most that
 many, reduced by separate waves into a workspace and combined in segment order by a second small launch: a hub of thousands
-of neighbors does not outlive the launch, no float atomics, one fixed summation order.
+of neighbors does not outlive the launch, no float atomics, one fixed summation order.  (CSR_SOFTMAX, the attention pooling
+over the whole list: a partial carries its maximum and weight sum, and the combine rescales the partials to their common maximum.)
 
 A node subset.  The same exact pass over only the rows a request depends on:
 
@@ -50,7 +51,7 @@ bit-equal to those rank_full reports for the same pair.
 import numpy as np
 
 from . import ops
-from ._lib import CSR_MAX, CSR_MEAN, CSR_MEAN_SELF, GraphsageAmdError  # noqa: F401
+from ._lib import CSR_MAX, CSR_MEAN, CSR_MEAN_SELF, CSR_SOFTMAX, GraphsageAmdError  # noqa: F401
 
 SPLIT_LEN = 512          # longest run of edges one wave reduces (rows beyond it are cut)
 
@@ -92,6 +93,11 @@ def plan_work_items(rowptr, split_len=SPLIT_LEN):
 
 def _is_torch(a):
     return type(a).__module__.startswith("torch")
+
+
+def _partial_width(op, d):
+    """Width of a cut row's partial: CSR_SOFTMAX carries its (max, sum) pair behind the accumulator."""
+    return d + 4 if op == CSR_SOFTMAX else d
 
 
 class FullGraph(object):
@@ -240,7 +246,7 @@ class FullGraph(object):
         item_r, split_r, slot_r = self.window(row0, n)
         ws = None
         if slot_r[1] > slot_r[0]:
-            words = ops.csr_reduce_ws_bytes(slot_r[1] - slot_r[0], X.d) // 4
+            words = ops.csr_reduce_ws_bytes(slot_r[1] - slot_r[0], _partial_width(op, X.d)) // 4
             ws = engine.ws_f32(("csr_reduce_ws",), max(1 << 16, 1 << (words - 1).bit_length()))     # few sizes, few buffers
         ops.csr_reduce_fwd(rowptr, col, items, splits, self.n_rows, self.split_len, op, X, out, row0, n, item_r, split_r,
                            slot_r, ws=ws, act=act, stream=engine.stream)
@@ -276,7 +282,7 @@ class FullGraph(object):
         items, splits, n_slots = plan if plan is not None else self.upload_plan(engine, rows)
         ws = None
         if n_slots:
-            words = ops.csr_reduce_ws_bytes(n_slots, X.d) // 4
+            words = ops.csr_reduce_ws_bytes(n_slots, _partial_width(op, X.d)) // 4
             ws = engine.ws_f32(("csr_reduce_ws",), max(1 << 16, 1 << (words - 1).bit_length()))
         ops.csr_reduce_rows(rowptr, col, items, splits, self.n_rows, self.split_len, op, X, out, out_pos, x_pos=x_pos,
                             n_slots=n_slots, ws=ws, act=act, stream=engine.stream)
@@ -385,11 +391,12 @@ class GraphLayer(object):
         """A zeroed [computed rows, d] output table."""
         return _table(agg.engine, self.graph.n_rows, d)
 
-    def dense(self, agg, H, stack):
+    def dense(self, agg, H, stack, spare=0):
         """The Dense stack [(W, bias, width, act), ...] over every row the layer may read: a table indexed like those rows.
-        The intermediate of a two-layer stack lives in a per-window workspace."""
+        The intermediate of a two-layer stack lives in a per-window workspace.  spare: zeroed columns kept behind the table's
+        own (the logit column of CSR_SOFTMAX), inside its leading dimension."""
         e = agg.engine
-        T = self.table(agg, stack[-1][2])
+        T = self.table(agg, stack[-1][2] + spare).cols_slice(0, stack[-1][2])
         mid = e.ws_mat((agg.name, "full_h1"), min(WINDOW_ROWS, self.graph.n_rows), stack[0][2]) if len(stack) > 1 else None
         for r0, n in self._windows():
             X, k = H.rows_slice(r0, r0 + n), H.d
@@ -451,9 +458,10 @@ class RowsLayer(object):
     def table(self, agg, d):
         return _table(agg.engine, self.n, d)
 
-    def dense(self, agg, H, stack):
+    def dense(self, agg, H, stack, spare=0):
         e = agg.engine
-        tables = [_table(e, self.prev_n, width) for _, _, width, _ in stack]
+        tables = [_table(e, self.prev_n, width) for _, _, width, _ in stack[:-1]]
+        tables.append(_table(e, self.prev_n, stack[-1][2] + spare).cols_slice(0, stack[-1][2]))
         X, idx, k = H, self.prev_ids, H.d
         for (W, bias, width, act), Y in zip(stack, tables):
             ops.gemm(False, False, self.prev_n, width, k, X, W, Y, a_row_idx=idx, bias=bias, act=act, stream=e.stream)

@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .aggregators import (GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator, SeqAggregator,
-                          TwoMaxLayerPoolingAggregator, contiguous_rows)
+from .aggregators import (AttentionPoolingAggregator, GCNAggregator, MaxPoolingAggregator, MeanAggregator, MeanPoolingAggregator,
+                          SeqAggregator, TwoMaxLayerPoolingAggregator, contiguous_rows)
 from .engine import get_engine
 from .inits import glorot
 from .layers import Rows, identity
@@ -40,6 +40,7 @@ _AGGREGATORS = {
     "gcn": GCNAggregator,
     "seq": SeqAggregator,
     "twomaxpool": TwoMaxLayerPoolingAggregator,
+    "attn": AttentionPoolingAggregator,
 }
 
 

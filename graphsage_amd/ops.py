@@ -237,7 +237,8 @@ def mean_bwd(d_mean, n, s, scale, d_neigh, mask_y=None, accumulate=False, stream
 
 # ------------------------------------------------------------------------------------------ INF
 def csr_reduce_ws_bytes(n_slots, d):
-    """Bytes of the partials workspace gs_csr_reduce_fwd needs for n_slots segments of long rows at width d."""
+    """Bytes of the partials workspace gs_csr_reduce_fwd needs for n_slots segments of long rows at width d (CSR_SOFTMAX: the
+    table's d + 4, its partial carries the (max, sum) pair)."""
     out = ctypes.c_int64(0)
     call("gs_csr_reduce_ws_bytes", n_slots, d, ctypes.byref(out))
     return out.value
@@ -255,8 +256,9 @@ def _csr_desc(q, rowptr, col, items, splits, n_rows, split_len, op, X, out, ws, 
 
 def csr_reduce_fwd(rowptr, col, items, splits, n_rows, split_len, op, X, out, row0, n, item_range, split_range, slot_range,
                    ws=None, act=ACT_IDENTITY, stream=None):
-    """gs_csr_reduce_fwd: out[r - row0] = mean | mean-with-self | max over the whole neighbor list of row r of X's rows, for the
-    window [row0, row0 + n) of a planned CSR graph (inference.FullGraph owns the plan and has checked the column ids)."""
+    """gs_csr_reduce_fwd: out[r - row0] = mean | mean-with-self | max | softmax-weighted sum (CSR_SOFTMAX: the logit of a row is
+    column X.d of X, ws sized for width X.d + 4) over the whole neighbor list of row r of X's rows, for the window
+    [row0, row0 + n) of a planned CSR graph (inference.FullGraph owns the plan and has checked the column ids)."""
     q = _csr_desc(_lib.CsrReduceDesc(), rowptr, col, items, splits, n_rows, split_len, op, X, out, ws, act)
     q.row0, q.n = row0, n
     (q.item0, q.item1), (q.split0, q.split1), (q.slot0, q.slot1) = item_range, split_range, slot_range
@@ -750,6 +752,35 @@ def segment_max_fwd(H, n, s, pooled, argmax, stream=None):
 def segment_max_bwd(d_pooled, pooled, argmax, n, s, dH, stream=None):
     call("gs_segment_max_bwd", d_pooled.ptr, d_pooled.ld, pooled.ptr, pooled.ld, ptr(argmax), argmax.stride(0), n, s,
          pooled.d, dH.ptr, dH.ld, _s(stream))
+
+
+ATTN_MAX_S, ATTN_MAX_HIDDEN = 128, 1024      # GS_ATTN_MAX_S / GS_ATTN_MAX_HIDDEN (csrc/gs_attn.hip)
+
+
+def segment_attn_supported(s, hidden):
+    """The range of gs_segment_attn_fwd / _bwd (GS_ENOTSUP outside it)."""
+    return 1 <= s <= ATTN_MAX_S and 4 <= hidden <= ATTN_MAX_HIDDEN and hidden % 4 == 0
+
+
+def segment_attn_fwd(H, inv, a, n, s, pooled, alpha, stream=None):
+    """gs_segment_attn_fwd: alpha[i] = softmax_j <V_j, a>, pooled[i] = sum_j alpha[i, j] V_j over each group's s rows V_j =
+    H[inv[i*s + j]] (inv None: H[i*s + j]).  a: fp32 device vector [H.d]; alpha: fp32 device vector [n * s]."""
+    call("gs_segment_attn_fwd", H.ptr, H.ld, ptr(inv), ptr(a), n, s, H.d, pooled.ptr, pooled.ld, ptr(alpha), _s(stream))
+    return pooled
+
+
+def segment_attn_bwd(dP, H, inv, a, alpha, n, s, dV, n_slabs, slabs_ptr, stream=None):
+    """gs_segment_attn_bwd: dV [n*s, H.d] per sampled row (relu mask of V applied) and n_slabs partial sums of da
+    ([n_slabs, H.d] at slabs_ptr, each fully written)."""
+    call("gs_segment_attn_bwd", dP.ptr, dP.ld, H.ptr, H.ld, ptr(inv), ptr(a), ptr(alpha), n, s, H.d, dV.ptr, dV.ld, slabs_ptr,
+         n_slabs, _s(stream))
+    return dV
+
+
+def attn_scores(H, a, stream=None):
+    """gs_attn_scores: column H.d of every row of H = <H[r, :H.d], a> (H.ld >= H.d + 4): the logit column of CSR_SOFTMAX."""
+    call("gs_attn_scores", H.ptr, H.ld, H.rows, H.d, ptr(a), _s(stream))
+    return H
 
 
 def maxpool_sparse_wgrad(X, ids, n, s, argmax, dpm, hidden, n_slabs, slabs_ptr, ld_slab, stream=None):

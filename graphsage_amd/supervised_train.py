@@ -234,6 +234,14 @@ def refuse_dropout(flags):
                                 "input of both Dense layers of the aggregator; only --dropout 0 is implemented)")
 
 
+def refuse_samples(flags):
+    """The attention-pooling kernels take 1 <= s <= 128 sampled neighbors per node: refuse a wider --samples_* before any work."""
+    if flags.model == 'graphsage_attn':
+        from .aggregators import AttentionPoolingAggregator
+        AttentionPoolingAggregator.check_samples([s for s in (flags.samples_1, flags.samples_2, getattr(flags, "samples_3", 0))
+                                                  if s != 0])
+
+
 def full_graph(minibatch, n_nodes):
     """The test graph for full-neighborhood inference: the padded test table verbatim under --sampler padded, else the CSR."""
     from .inference import FullGraph
@@ -406,7 +414,8 @@ def train(G, embed_rows=None):
                        SAGEInfo("node", sampler, FLAGS.samples_2, 2 * FLAGS.dim_2)]
         model = SupervisedGraphsage(num_classes, placeholders, features, adj_info, minibatch.deg,
                                     layer_infos=layer_infos, aggregator_type="gcn", concat=False, **kw)
-    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_seq', 'graphsage_twomaxpool'):   # :190-236
+    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_seq', 'graphsage_twomaxpool',
+                         'graphsage_attn'):   # :190-236
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
         model = SupervisedGraphsage(num_classes, placeholders, features, adj_info, minibatch.deg,
@@ -538,6 +547,7 @@ def main(argv=None):
     FLAGS = build_flags(argv)
     refuse_full_inference(FLAGS)
     refuse_dropout(FLAGS)
+    refuse_samples(FLAGS)
     refuse_importance(FLAGS)
     tokens = read_embed_nodes(FLAGS)
     print("Loading training data..")

@@ -5,7 +5,8 @@ graphsage/unsupervised_train.py (flags :25-55, loop :246-316, save_val_embedding
     python -m graphsage_amd.unsupervised_train --synthetic small --model graphsage_mean --epochs 1
     python -m graphsage_amd.unsupervised_train --synthetic small --model n2v --learning_rate 0.1
 
-Models: graphsage_mean | gcn | graphsage_seq | graphsage_maxpool | graphsage_meanpool | graphsage_twomaxpool | n2v.  n2v is the DeepWalk /
+Models: graphsage_mean | gcn | graphsage_seq | graphsage_maxpool | graphsage_meanpool | graphsage_twomaxpool | graphsage_attn | n2v.  n2v is
+the DeepWalk /
 node2vec baseline (:227-232): after val.npy it retrains on random walks from the val / test nodes for --n2v_test_epochs
 epochs and writes val-test.npy / val-test.txt (:322-372).
 """
@@ -361,7 +362,7 @@ def train(G, context_pairs, embed_rows=None):
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
         model = SampleAndAggregate(placeholders, features, adj_info, minibatch.deg, layer_infos=layer_infos,
                                    aggregator_type="seq", **kw)
-    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_twomaxpool'):   # :203-230
+    elif FLAGS.model in ('graphsage_maxpool', 'graphsage_meanpool', 'graphsage_twomaxpool', 'graphsage_attn'):   # :203-230
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
         model = SampleAndAggregate(placeholders, features, adj_info, minibatch.deg, layer_infos=layer_infos,
@@ -487,6 +488,7 @@ def main(argv=None):
     from . import supervised_train as st
     st.refuse_full_inference(FLAGS)
     st.refuse_dropout(FLAGS)
+    st.refuse_samples(FLAGS)
     st.refuse_importance(FLAGS)
     refuse_walk_flags(FLAGS)
     refuse_eval_classifier(FLAGS)

@@ -389,6 +389,25 @@ int gs_dense_fwd_rows_dev(const float* X, int64_t ldx, const int32_t* idx, int32
 int gs_segment_max_gather_fwd(const float* H, int64_t ldh, const int32_t* inv, int64_t n, int32_t s, int32_t hidden,
                               float* pooled, int64_t ldp, int32_t* argmax, int64_t lda, void* stream);
 
+/* Attention pooling over each group's s sampled rows (graphsage_attn; csrc/gs_attn.hip).  Row j of group i is V_j =
+ * H[inv[i*s + j]], or H[i*s + j] when inv == NULL; H is the output of the aggregator's relu-Dense and a [hidden] the gate:
+ *   gs_segment_attn_fwd  t_j = <V_j, a>; alpha[i, j] = softmax_j(t_j) (maximum subtracted); pooled[i] = sum_j alpha[i, j] V_j.
+ *                        One wave per group, one pass with a running maximum / sum / rescaled accumulator: every row of H is
+ *                        read once, no [n*s, hidden] temporary, no atomics, bitwise repeatable.  alpha: [n, s], dense.
+ *   gs_segment_attn_bwd  from dP = d_pooled [n, hidden]: g_j = <dP_i, V_j>, G = sum_j alpha_j g_j, dt_j = alpha_j (g_j - G),
+ *                        dV[i*s + j] = (alpha_j dP_i + dt_j a) * (V_j > 0) (one row per SAMPLED row, the Dense's relu mask applied)
+ *                        and da_slabs [n_slabs, hidden] (row stride hidden): partial sums of da = sum_{i,j} dt_j V_j, one slab
+ *                        per workgroup, each fully written; their sum in slab order is da (the optimizer launch adds them as it
+ *                        adds the weight gradients' slabs).  No float atomics; the same n_slabs gives the same bits.
+ *   gs_attn_scores       H[r, hidden] = <H[r, :hidden], a> for every row: the logit column GS_CSR_SOFTMAX reads (ldh >= hidden + 4).
+ * Range: hidden % 4 == 0, 4 <= hidden <= 1024, 1 <= s <= 128; GS_ENOTSUP otherwise.  a must be 16-byte aligned. */
+int gs_segment_attn_fwd(const float* H, int64_t ldh, const int32_t* inv, const float* a, int64_t n, int32_t s, int32_t hidden,
+                        float* pooled, int64_t ldp, float* alpha, void* stream);
+int gs_segment_attn_bwd(const float* dP, int64_t ldd, const float* H, int64_t ldh, const int32_t* inv, const float* a,
+                        const float* alpha, int64_t n, int32_t s, int32_t hidden, float* dV, int64_t ldv, float* da_slabs,
+                        int32_t n_slabs, void* stream);
+int gs_attn_scores(float* H, int64_t ldh, int64_t rows, int32_t hidden, const float* a, void* stream);
+
 /* H[n*s, hidden] = relu(X[idx] · W_mlp + b_mlp)  (Dense, layers.py:104-116) is produced by
  * gs_sage_dense_fwd(self=NULL, agg=X, agg_idx=idx, ...).  This reduces it:
  *   pooled[i, c] = max_j H[i*s+j, c];  argmax[i, c] = first j attaining it   (reduce_max, :181) */
@@ -1035,6 +1054,12 @@ int gs_n2v_apply(float* target, int64_t ldt, float* context, int64_t ldc, float*
 #define GS_CSR_MEAN 0
 #define GS_CSR_MEAN_SELF 1
 #define GS_CSR_MAX 2
+/*      GS_CSR_SOFTMAX    out[r - row0] = sum_e softmax_e(X[col[e]][d]) * X[col[e]][:d]      (attention pooling, all neighbors)
+ *      The logit of table row r is column d of X, the column right behind the d value columns: ldx >= round_up(d + 1, 4)
+ *      (gs_attn_scores fills it).  The maximum is subtracted; an empty row gives 0; a duplicate entry counts as often as it
+ *      occurs.  A partial of a cut row carries (max, sum, accumulator) and the combine launch rescales the partials to their
+ *      common maximum in slot order; size the workspace with gs_csr_reduce_ws_bytes(n_slots, d + 4). */
+#define GS_CSR_SOFTMAX 3
 typedef struct gs_csr_reduce_desc {
     const int64_t* rowptr;     /* device [n_rows + 1] */
     const int32_t* col;        /* device [nnz] */
