@@ -1,0 +1,304 @@
+"""k-means of an embedding table at the Reddit shape: the fused assign kernel (csrc/gs_kmeans.hip, through ops.kmeans_assign),
+one full Lloyd iteration and a whole fit (graphsage_amd.clustering), next to the two routes that exist without it, all in one
+process:
+
+  * "topk":  the assignment forced through ops.topk_select with k = 1 on augmented tables x' = [x, 1], c' = [c, -|c|^2 / 2]
+             (a padded copy of the table, per-slice key lists, a merge launch); its iteration uses the same update launches.
+  * "torch": an eager restatement, S = addmm(-|c|^2 / 2, X, C^T), argmax, index_add_ for the sums.
+
+    python benchmarks/bench_clusters.py [--n 232965] [--cases 256:41,256:1024,128:4096] [--out profiles/eval_clusters.md]
+
+Prints one JSON line and writes the profile (markdown) to --out.  Device events around --reps calls,
+median (min .. max) of 5 regions after a warm-up call, for the launches; a host clock around work that ends in a device
+synchronise for an iteration and a fit (they hold host work: the 16-byte read, the plan of the update).  The share of the
+fp32-MFMA peak is 2 n k d useful FLOP (and, apart, the FLOP executed on whole 128-column tiles) over the time of one assign
+call over 157.3 TFLOP/s.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from benchmarks.bench_rank import regions  # noqa: E402
+
+PEAK_F32_MFMA = 157.3e12     # v_mfma_f32_32x32x2_f32, MI355X
+
+
+def lloyd(assign, update, C, max_iter=100, tol=1e-4):
+    """The loop and stop rules of clustering.fit_kmeans over an (assign, update) pair of the route under test;
+    assign(C, prev) -> (labels, inertia, rows whose label differs from prev)."""
+    prev, inertia_prev, iters = None, None, 0
+    while True:
+        labels, inertia, changed = assign(C, prev)
+        iters += 1
+        if changed == 0:
+            return C, labels, inertia, iters, "converged"
+        if inertia_prev is not None and inertia_prev - inertia <= tol * inertia_prev:
+            return C, labels, inertia, iters, "tol"
+        if iters >= max_iter:
+            return C, labels, inertia, iters, "max_iter"
+        C = update(labels, C)
+        prev, inertia_prev = labels, inertia
+
+
+def timed(fn, n=3):
+    """Host clock around fn() + synchronise: median, min, max of n runs after one warm-up run, in ms; and fn's last result."""
+    out = fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    return {"ms": float(np.median(ms)), "ms_min": float(np.min(ms)), "ms_max": float(np.max(ms))}, out
+
+
+def run_case(dev, N, d, K, reps):
+    from graphsage_amd import clustering as cl
+    from graphsage_amd import ops
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    true = torch.randn(K, d, device=dev, generator=g)
+    label = torch.randint(0, K, (N,), device=dev, generator=g)
+    X = ops.Mat.zeros(N, d, dev)
+    X.buf[:, :d].copy_(true[label] + 0.7 * torch.randn(N, d, device=dev, generator=g))
+    seeds = torch.randperm(N, device=dev, generator=g)[:K]
+    init = X.buf[seeds][:, :d].clone()                   # K data points: the three routes start from the same centres
+    C = ops.Mat.zeros(K, d, dev)
+    C.buf[:, :d].copy_(init)
+
+    def record():
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+
+    def elapsed(a, b):
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    res = {"n": N, "d": d, "k": K}
+    # ---- fused
+    xsq = ops.kmeans_sqnorm(X)
+    csq = ops.kmeans_sqnorm(C)
+    assign = torch.zeros(N, dtype=torch.int32, device=dev)
+    dist = torch.zeros(N, dtype=torch.float32, device=dev)
+    stats = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = torch.zeros(ops.kmeans_assign_ws_bytes(N) // 8 + 2, dtype=torch.int64, device=dev)
+
+    def fused_assign():
+        ops.kmeans_assign(X, C, csq, xsq=xsq, assign=assign, dist=dist, stats=stats, ws=ws)
+    fused_assign()
+    torch.cuda.synchronize()
+    r = regions(fused_assign, record, elapsed, reps)
+    useful = 2.0 * N * K * d
+    executed = 2.0 * (-(-N // 128) * 128) * (-(-K // 128) * 128) * (-(-d // 32) * 32)
+    r["useful_tflops"] = useful / (r["ms"] * 1e-3) / 1e12
+    r["share_of_f32_mfma_peak_useful"] = useful / (r["ms"] * 1e-3) / PEAK_F32_MFMA
+    r["share_of_f32_mfma_peak_executed"] = executed / (r["ms"] * 1e-3) / PEAK_F32_MFMA
+    res["assign"] = {"fused": r}
+    fused_labels = assign.clone()
+
+    # ---- the topk route: augmented tables, k = 1
+    Xa = ops.Mat.zeros(N, d + 4, dev)
+    Ca = ops.Mat.zeros(K, d + 4, dev)
+
+    def augment_x():
+        Xa.buf[:, :d].copy_(X.buf[:, :d])
+        Xa.buf[:, d] = 1.0
+
+    def augment_c(Cm):
+        Ca.buf[:, :d].copy_(Cm.buf[:, :d])
+        Ca.buf[:, d] = -0.5 * (Cm.buf[:, :d] * Cm.buf[:, :d]).sum(dim=1)
+    augment_x()
+    augment_c(C)
+    need = max(ops.topk_ws_bytes(q, K, 1) for q in {min(N, ops.RANK_CHUNK), N % ops.RANK_CHUNK})     # the two chunk sizes that occur
+    tk_ws = torch.zeros(need // 8 + 1, dtype=torch.int64, device=dev)
+    tk_ids = torch.zeros((N, 1), dtype=torch.int32, device=dev)
+    tk_sc = torch.zeros((N, 1), dtype=torch.float32, device=dev)
+    tk_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
+
+    def topk_assign():
+        ops.topk_select(Xa, Ca, 1, n_cand=K, ids=tk_ids, scores=tk_sc, count=tk_cnt, ws=tk_ws)
+    topk_assign()
+    torch.cuda.synchronize()
+    r = regions(topk_assign, record, elapsed, reps)
+    r["workspace_bytes"] = int(tk_ws.numel() * 8)
+    r["padded_table_bytes"] = int(Xa.buf.numel() * 4)
+    res["assign"]["topk"] = r
+    res["assign"]["topk_same_labels_share"] = float((tk_ids[:, 0] == fused_labels).float().mean())
+
+    # ---- torch
+    x = X.view()
+
+    def torch_assign_of(c):
+        S = torch.addmm(-0.5 * (c * c).sum(dim=1), x, c.t())
+        best, labels = S.max(dim=1)
+        return labels, best
+
+    torch_assign_of(init)
+    torch.cuda.synchronize()
+    res["assign"]["torch"] = regions(lambda: torch_assign_of(init), record, elapsed, reps)
+    res["assign"]["torch_same_labels_share"] = float((torch_assign_of(init)[0] == fused_labels.long()).float().mean())
+    for other in ("topk", "torch"):
+        res["assign"]["fused_over_" + other] = res["assign"]["fused"]["ms"] / res["assign"][other]["ms"]
+
+    # ---- one Lloyd iteration and a whole fit, per route (host clock + synchronise)
+    xsq_t = (x * x).sum(dim=1)
+    p = cl._Problem(None, X, None)
+    k = K
+    scratch = {"rowptr": torch.empty(k + 1, dtype=torch.int64, device=dev), "members": torch.empty(N, dtype=torch.int32, device=dev),
+               "members_ws": torch.empty(max(ops.kmeans_members_ws_bytes(N, k) // 4, 1), dtype=torch.int32, device=dev)}
+    bufs = [ops.Mat.zeros(K, d, dev), ops.Mat.zeros(K, d, dev)]
+    lab = [torch.zeros(N, dtype=torch.int32, device=dev), torch.zeros(N, dtype=torch.int32, device=dev)]
+    turn = [0]
+
+    def changed_rows(labels, prev):
+        return labels.numel() if prev is None else int((labels != prev).sum())
+
+    def fused_a(Cm, prev):
+        out = lab[turn[0] % 2]                           # never the buffer that holds prev
+        turn[0] += 1
+        inertia, changed = p.assign(Cm, prev=prev, assign=out)
+        return out, inertia, (N if prev is None else changed)
+
+    def device_update(labels, Cm):
+        nxt = bufs[0] if Cm is bufs[1] else bufs[1]
+        cl._update(p, Cm, nxt, labels, scratch)
+        return nxt
+
+    def topk_a(Cm, prev):
+        augment_c(Cm)
+        topk_assign()
+        labels = tk_ids[:, 0].clone()
+        inertia = float(torch.clamp(xsq_t - 2.0 * tk_sc[:, 0], min=0.0).double().sum())
+        return labels, inertia, changed_rows(labels, prev)
+
+    def torch_a(c, prev):
+        labels, best = torch_assign_of(c)
+        return labels, float(torch.clamp(xsq_t - 2.0 * best, min=0.0).double().sum()), changed_rows(labels, prev)
+
+    def torch_update(labels, c):
+        sums = torch.zeros_like(c).index_add_(0, labels, x)
+        cnt = torch.bincount(labels, minlength=K).to(c.dtype)
+        return torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1.0)[:, None], c)
+
+    def start():
+        bufs[0].buf[:, :d].copy_(init)
+        return bufs[0]
+    routes = {"fused": (fused_a, device_update, start), "topk": (topk_a, device_update, start),
+              "torch": (torch_a, torch_update, lambda: init.clone())}
+    res["iteration"], res["fit"] = {}, {}
+    for name, (a, u, s) in routes.items():
+        def one():
+            c = s()
+            labels = a(c, None)[0]
+            return u(labels, c)
+        res["iteration"][name], _ = timed(one)
+        t, out = timed(lambda: lloyd(a, u, s()), n=2)
+        t.update(iters=out[3], stop=out[4], inertia=out[2])
+        res["fit"][name] = t
+    t, fit = timed(lambda: cl.fit_kmeans(None, X, K, init=init.cpu().numpy()), n=2)
+    t.update(iters=fit.iters, stop=fit.stop, inertia=fit.inertia, empty=fit.empty)
+    res["fit"]["fit_kmeans"] = t                         # the library call itself: upload of the centres and |x|^2 included
+    for sect in ("iteration", "fit"):
+        for other in ("topk", "torch"):
+            res[sect]["fused_over_" + other] = res[sect]["fused"]["ms"] / res[sect][other]["ms"]
+    return res
+
+
+def fmt(r):
+    return "%.3f (%.3f .. %.3f)" % (r["ms"], r["ms_min"], r["ms_max"])
+
+
+def markdown(res):
+    out = ["# k-means of the embedding table (`--eval_clusters`): the fused assign kernel against the routes without it", "",
+           "Written by `benchmarks/bench_clusters.py` on one MI355X; N = %d rows, synthetic blobs (k centres + 0.7 noise), the "
+           "three routes start from the same k data points.  Times in ms: median (min .. max).  Launches: device events around "
+           "%d calls, 5 regions after a warm-up call.  Iteration and fit: host clock around work that ends in a device "
+           "synchronise, 3 (fit: 2) runs after a warm-up run." % (res["n"], res["reps"]), "",
+           "Routes: **fused** = `ops.kmeans_assign` (one sweep launch + the finishing launch; no score, key list or per-slice "
+           "workspace is written); **topk** = what the parent commit can do: `ops.topk_select` with k = 1 on x' = [x, 1], "
+           "c' = [c, -|c|^2 / 2] (a padded copy of the table, per-slice lists of 128 keys per row, a merge launch), with the "
+           "same update launches; **torch** = eager `addmm` + `max` + `index_add_`.", ""]
+    out += ["## One assignment", "",
+            "| d | k | fused | topk route | torch | fused / topk | fused / torch | useful TFLOP/s | share of fp32-MFMA peak (useful / executed on whole tiles) |",
+            "|---|---|---|---|---|---|---|---|---|"]
+    for c in res["cases"]:
+        a = c["assign"]
+        out.append("| %d | %d | %s | %s | %s | %.2f | %.2f | %.1f | %.1f %% / %.1f %% |" % (
+            c["d"], c["k"], fmt(a["fused"]), fmt(a["topk"]), fmt(a["torch"]), a["fused_over_topk"], a["fused_over_torch"],
+            a["fused"]["useful_tflops"], 100 * a["fused"]["share_of_f32_mfma_peak_useful"],
+            100 * a["fused"]["share_of_f32_mfma_peak_executed"]))
+    out += ["", "The peak is 157.3 TFLOP/s (`v_mfma_f32_32x32x2_f32`); useful FLOP = 2 n k d, executed = the same on whole "
+            "128 x 128 x 32 tiles (k = 41 fills a third of its one centroid tile).  These are rates of a whole assign call (both launches) "
+            "over the peak, not a kernel trace.", "",
+            "Same labels as the fused kernel on this assignment: " + ", ".join(
+                "d=%d k=%d topk %.5f torch %.5f" % (c["d"], c["k"], c["assign"]["topk_same_labels_share"],
+                                                    c["assign"]["torch_same_labels_share"]) for c in res["cases"]) +
+            " (the contractions sum in different orders: rows at a near-tie may differ).", "",
+            "topk route's extra memory: " + ", ".join("d=%d k=%d workspace %.1f MB + padded table %.1f MB" % (
+                c["d"], c["k"], c["assign"]["topk"]["workspace_bytes"] / 1e6, c["assign"]["topk"]["padded_table_bytes"] / 1e6)
+                for c in res["cases"]) + "; the fused kernel's workspace is 16 B per 128 rows.", ""]
+    for sect, title in (("iteration", "One Lloyd iteration (assign + group + update, host work included)"),
+                        ("fit", "A whole fit (same init, the stop rules of `fit_kmeans`, tol = 1e-4)")):
+        out += ["## " + title, "", "| d | k | fused | topk route | torch | fused / topk | fused / torch |" + (" iterations (fused, topk, torch) | `fit_kmeans` call |" if sect == "fit" else ""),
+                "|---|---|---|---|---|---|---|" + ("---|---|" if sect == "fit" else "")]
+        for c in res["cases"]:
+            s = c[sect]
+            row = "| %d | %d | %s | %s | %s | %.2f | %.2f |" % (c["d"], c["k"], fmt(s["fused"]), fmt(s["topk"]), fmt(s["torch"]),
+                                                                s["fused_over_topk"], s["fused_over_torch"])
+            if sect == "fit":
+                row += " %d %s, %d %s, %d %s | %s, %d iterations, %s |" % (
+                    s["fused"]["iters"], s["fused"]["stop"], s["topk"]["iters"], s["topk"]["stop"], s["torch"]["iters"],
+                    s["torch"]["stop"], fmt(s["fit_kmeans"]), s["fit_kmeans"]["iters"], s["fit_kmeans"]["stop"])
+            out.append(row)
+        out.append("")
+    slower = [c for c in res["cases"] if c["assign"]["fused_over_topk"] > 1.0]
+    out += ["## Verdict", ""]
+    if slower:
+        out.append("The fused kernel does NOT beat the topk route at " + ", ".join("d=%d k=%d (%.2fx its time)" % (
+            c["d"], c["k"], c["assign"]["fused_over_topk"]) for c in slower) + ": both run the same sweep, so what differs is "
+            "the epilogue and the shape of the grid; see the numbers above.")
+    else:
+        out.append("The fused kernel beats the topk route at every shape measured, k = 1024 included (fused / topk above).")
+    out += ["", "## Resources", "",
+            "`hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage`: kmeans_assign_kernel 234 vector registers, "
+            "84 scalar, no scratch, no spill, 73,776 B of LDS, two workgroups per CU (gs_topk.hip's select kernel: 206 "
+            "registers, 77,824 B).  kmeans_finish_kernel 61 registers / 4,096 B; kmeans_sqnorm_kernel 12 / 0; kmeans_hist_kernel "
+            "50 / 16,384 B; kmeans_place_kernel 34 / 16,384 B; kmeans_scan_chunks_kernel 6 / 0; kmeans_scan_k_kernel 26 / 2,048 B. "
+            "No scratch in any of them.", ""]
+    return "\n".join(out)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=232965)
+    ap.add_argument("--cases", default="256:41,256:1024,128:4096", help="d:k pairs")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default="profiles/eval_clusters.md")
+    args = ap.parse_args(argv)
+    assert torch.cuda.is_available(), "bench_clusters.py needs the GPU"
+    dev = torch.device("cuda:0")
+    res = {"metric": "k-means of an embedding table: fused assign vs the topk route vs eager torch", "n": args.n, "reps": args.reps,
+           "cases": []}
+    for case in args.cases.split(","):
+        d, k = (int(v) for v in case.split(":"))
+        res["cases"].append(run_case(dev, args.n, d, k, args.reps))
+        print("case d=%d k=%d done" % (d, k), file=sys.stderr, flush=True)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(markdown(res))
+            f.write("\n```json\n" + json.dumps(res) + "\n```\n")
+
+
+if __name__ == "__main__":
+    main()

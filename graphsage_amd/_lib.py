@@ -189,6 +189,11 @@ _PROTOS = {
     "gs_logreg_joined_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
     "gs_logreg_eval_joined": [_P, _P],
     "gs_col_moments": [_P, _P, c_int64, c_int32, c_int64, _P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P, c_int64, _P],
+    "gs_kmeans_sqnorm": [_P, c_int64, c_int64, _P, c_int64, c_int32, _P, _P],
+    "gs_kmeans_assign_ws_bytes": [c_int64, POINTER(c_int64)],
+    "gs_kmeans_assign": [_P, _P],
+    "gs_kmeans_members_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
+    "gs_kmeans_members": [_P, _P],
 }
 
 
@@ -408,6 +413,27 @@ class LogregJoinedDesc(ctypes.Structure):
 LOGREG_JOINED_MAX_D = 1024                  # GS_LOGREG_JOINED_MAX_D
 COL_MOMENTS_MAX_CHUNKS = 256                # GS_COL_MOMENTS_MAX_CHUNKS
 assert ctypes.sizeof(LogregJoinedDesc) == 224    # static_assert in csrc/gs_logreg.hip (passed by pointer, as LogregDesc)
+
+
+class KmeansDesc(ctypes.Structure):
+    """struct gs_kmeans_desc (include/graphsage_amd.h)"""
+    _fields_ = [("X", c_void_p), ("rows", c_void_p), ("C", c_void_p), ("csq", c_void_p), ("xsq", c_void_p), ("prev", c_void_p),
+                ("assign", c_void_p), ("dist", c_void_p), ("stats", c_void_p), ("ws", c_void_p),
+                ("n", c_int64), ("n_rows", c_int64), ("ld", c_int64), ("ldc", c_int64), ("ws_bytes", c_int64),
+                ("k", c_int32), ("d", c_int32)]
+
+
+class KmeansMembersDesc(ctypes.Structure):
+    """struct gs_kmeans_members_desc (include/graphsage_amd.h)"""
+    _fields_ = [("assign", c_void_p), ("rows", c_void_p), ("rowptr", c_void_p), ("members", c_void_p), ("ws", c_void_p),
+                ("n", c_int64), ("ws_bytes", c_int64),
+                ("k", c_int32), ("chunk", c_int32), ("reserved_", c_int64)]
+
+
+KMEANS_MAX_K = 4096                         # GS_KMEANS_MAX_K
+KMEANS_CHUNK = 2048                         # GS_KMEANS_CHUNK
+assert ctypes.sizeof(KmeansDesc) == 128    # static_assert in csrc/gs_kmeans.hip (passed by pointer, as LogregDesc)
+assert ctypes.sizeof(KmeansMembersDesc) == 72
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -31,6 +31,11 @@ def build_flags(argv=None):
                    help="what a row is made of: the embeddings, the dataset's feature table, or [features | embeddings]")
     p.add_argument("--log_counts", action="store_true",
                    help="log(f0 + 1) and log(f1 - min(min f1, -1)) on feature columns 0 and 1 first (reddit_eval.py:46-47)")
+    p.add_argument("--clusters", type=int, default=0,
+                   help="K: instead of the regression, k-means of ALL rows of --table into K clusters on the device (-1: the "
+                        "dataset's number of classes), scored against the class labels -> eval_clusters.txt, clusters.npy, "
+                        "cluster_centers.npy; the setting is not used")
+    p.add_argument("--clusters_seed", type=int, default=123, help="seed of the k-means++ seeding of --clusters")
     return p.parse_args(argv)
 
 
@@ -57,6 +62,15 @@ def main(argv=None):
     if flags.log_counts and flags.inputs == "embeddings":
         raise SystemExit("--log_counts transforms the feature table: it needs --inputs features or both")
     from . import evaluation, utils
+    if flags.clusters:
+        from . import clustering
+        clustering.refuse_flags("--clusters", flags.clusters)
+        print("Loading data...")
+        G = utils.load_data(flags.data_prefix, normalize=False)
+        clustering.refuse_flags("--clusters", flags.clusters, G=G)
+        print("Running k-means..")
+        return clustering.evaluate_embedding_dir(None, G, flags.embed_dir, flags.clusters, base=flags.table,
+                                                 seed=flags.clusters_seed, flag="--clusters")
     print("Loading data...")
     G = utils.load_data(flags.data_prefix, normalize=False)
     evaluation.refuse_graph(G)

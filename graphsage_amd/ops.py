@@ -1258,6 +1258,111 @@ def col_moments(Xa, Xb=None, n=None, rows_a=None, rows_b=None, mean=None, var=No
     return mean, var
 
 
+# ------------------------------------------------------------------------------------------ KMEANS (gs_kmeans.hip)
+KMEANS_MAX_K = _lib.KMEANS_MAX_K  # largest k of gs_kmeans_assign / gs_kmeans_members
+
+
+def _kmeans_rows(who, X, rows, n):
+    """n of a (table, rows) pair; rows: int32 device vector with entries in [0, X.rows) (checked by the caller) or None."""
+    n = (rows.numel() if rows is not None else X.rows) if n is None else int(n)
+    if rows is not None and (rows.dtype != torch.int32 or rows.numel() != n or not rows.is_contiguous()):
+        raise _lib.GraphsageAmdError("%s: rows must be a dense int32 vector of n=%d entries" % (who, n))
+    if n < 1 or (rows is None and n > X.rows):
+        raise _lib.GraphsageAmdError("%s: n=%d rows asked of a table of %d" % (who, n, X.rows))
+    return n
+
+
+def _kmeans_vec(who, name, t, dtype, n):
+    if t is not None and (t.dtype != dtype or t.numel() != n or not t.is_contiguous()):
+        raise _lib.GraphsageAmdError("%s: %s must be a dense %s vector of %d entries" % (who, name, str(dtype).split(".")[-1], n))
+
+
+def kmeans_sqnorm(X, rows=None, n=None, out=None, stream=None):
+    """gs_kmeans_sqnorm: out[i] = |X[rows[i]]|^2 (rows None: row i), float32 [n], in a fixed order of additions."""
+    n = _kmeans_rows("kmeans_sqnorm", X, rows, n)
+    out = torch.empty(n, dtype=torch.float32, device=X.buf.device) if out is None else out
+    _kmeans_vec("kmeans_sqnorm", "out", out, torch.float32, n)
+    call("gs_kmeans_sqnorm", X.ptr, X.ld, X.rows, ptr(rows), n, X.d, ptr(out), _s(stream))
+    return out
+
+
+def kmeans_assign_ws_bytes(n):
+    """Bytes of the workspace gs_kmeans_assign needs for n rows (one 16-byte slot per workgroup of 128 rows)."""
+    out = ctypes.c_int64(0)
+    call("gs_kmeans_assign_ws_bytes", n, ctypes.byref(out))
+    return out.value
+
+
+def kmeans_assign(X, C, csq, rows=None, n=None, xsq=None, prev=None, assign=None, dist=None, stats=None, ws=None, stream=None):
+    """gs_kmeans_assign: assign[i] = argmax_j <X[rows[i]], C[j]> - csq[j] / 2 (an exact tie to the lowest j), dist[i] =
+    max(0, xsq[i] - 2 * that score) where `dist` is given, and stats = one 16-byte device buffer (torch.int64 [2]): the bits
+    of the float64 sum of dist, then the number of rows with assign[i] != prev[i] (0 without prev); read it with
+    kmeans_stats.  X: Mat [n_rows, d]; C: Mat [k, d]; csq float32 [k] (kmeans_sqnorm(C)); rows: int32 [n] with entries in
+    [0, X.rows) (checked by the caller) or None; xsq float32 [n] by position; prev, assign int32 [n].
+    Returns (assign, dist, stats)."""
+    who = "kmeans_assign"
+    k, d = C.rows, C.d
+    n = _kmeans_rows(who, X, rows, n)
+    if X.d != d:
+        raise _lib.GraphsageAmdError("%s: X is [%d, %d], C [%d, %d]" % (who, X.rows, X.d, k, d))
+    if not 1 <= k <= KMEANS_MAX_K:
+        raise _lib.GraphsageAmdError("%s: k=%d must lie in [1, %d]" % (who, k, KMEANS_MAX_K))
+    dev = X.buf.device
+    assign = torch.empty(n, dtype=torch.int32, device=dev) if assign is None else assign
+    stats = torch.zeros(2, dtype=torch.int64, device=dev) if stats is None else stats
+    if ws is None:
+        ws = torch.empty(max(kmeans_assign_ws_bytes(n) // 8, 2), dtype=torch.int64, device=dev)
+    for name, t, dtype, m in (("csq", csq, torch.float32, k), ("xsq", xsq, torch.float32, n), ("prev", prev, torch.int32, n),
+                              ("assign", assign, torch.int32, n), ("dist", dist, torch.float32, n),
+                              ("stats", stats, torch.int64, 2)):
+        _kmeans_vec(who, name, t, dtype, m)
+    if csq is None:
+        raise _lib.GraphsageAmdError("%s: csq is needed (kmeans_sqnorm of the centroids)" % who)
+    q = _lib.KmeansDesc()
+    q.X, q.rows, q.C, q.csq, q.xsq, q.prev = X.ptr, ptr(rows), C.ptr, ptr(csq), ptr(xsq), ptr(prev)
+    q.assign, q.dist, q.stats, q.ws = ptr(assign), ptr(dist), ptr(stats), ptr(ws)
+    q.n, q.n_rows, q.ld, q.ldc, q.ws_bytes = n, X.rows, X.ld, C.ld, ws.numel() * ws.element_size()
+    q.k, q.d = k, d
+    call("gs_kmeans_assign", ctypes.addressof(q), _s(stream))
+    return assign, dist, stats
+
+
+def kmeans_stats(stats):
+    """(inertia, changed) of kmeans_assign's stats buffer: one 16-byte copy to the host."""
+    h = stats.cpu().numpy()
+    return float(h.view("float64")[0]), int(h[1])
+
+
+def kmeans_members_ws_bytes(n, k, chunk=0):
+    """Bytes of the int32 workspace gs_kmeans_members needs (one histogram of k counters per chunk of the n entries)."""
+    out = ctypes.c_int64(0)
+    call("gs_kmeans_members_ws_bytes", n, k, chunk, ctypes.byref(out))
+    return out.value
+
+
+def kmeans_members(assign, k, rows=None, rowptr=None, members=None, ws=None, chunk=0, stream=None):
+    """gs_kmeans_members: the stable grouping of assign int32 [n] (entries in [0, k)): rowptr int64 [k + 1] and members int32
+    [n], cluster j's run holding rows[i] (i without rows) of its members in ascending i.  chunk: the entries one wave walks
+    (0: the library's default; a multiple of 64) -- the result does not depend on it.  Returns (rowptr, members)."""
+    who = "kmeans_members"
+    n, k, chunk = assign.numel(), int(k), int(chunk)
+    if not 1 <= k <= KMEANS_MAX_K or n < 1:
+        raise _lib.GraphsageAmdError("%s: k=%d must lie in [1, %d] and n=%d be positive" % (who, k, KMEANS_MAX_K, n))
+    dev = assign.device
+    rowptr = torch.empty(k + 1, dtype=torch.int64, device=dev) if rowptr is None else rowptr
+    members = torch.empty(n, dtype=torch.int32, device=dev) if members is None else members
+    for name, t, dtype, m in (("assign", assign, torch.int32, n), ("rows", rows, torch.int32, n),
+                              ("rowptr", rowptr, torch.int64, k + 1), ("members", members, torch.int32, n)):
+        _kmeans_vec(who, name, t, dtype, m)
+    if ws is None:
+        ws = torch.empty(max(kmeans_members_ws_bytes(n, k, chunk) // 4, 1), dtype=torch.int32, device=dev)
+    q = _lib.KmeansMembersDesc()
+    q.assign, q.rows, q.rowptr, q.members, q.ws = ptr(assign), ptr(rows), ptr(rowptr), ptr(members), ptr(ws)
+    q.n, q.ws_bytes, q.k, q.chunk, q.reserved_ = n, ws.numel() * ws.element_size(), k, chunk, 0
+    call("gs_kmeans_members", ctypes.addressof(q), _s(stream))
+    return rowptr, members
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

@@ -83,6 +83,11 @@ def build_flags(argv=None):
                    help='with --eval_classifier: besides the embeddings line, the same classifier on the feature table the model '
                         'trained on (features -> eval_classifier_features.txt), on [features | embeddings] (both -> '
                         'eval_classifier_both.txt), or the two of them (all); these rows are standardised on the train nodes')
+    p.add_argument('--eval_clusters', type=int, default=0,
+                   help='K: after val.npy (and --eval_classifier), k-means of ALL rows of the embedding table on the device into '
+                        'K clusters (-1: the dataset\'s number of classes), scored against the class labels (NMI, ARI, purity) '
+                        '-> eval_clusters.txt, clusters.npy, cluster_centers.npy; with --full_inference on val_full.npy')
+    p.add_argument('--eval_clusters_seed', type=int, default=123, help='seed of the k-means++ seeding of --eval_clusters')
     p.add_argument('--max_walk_pairs', type=int, default=2000000, help='cap on generated random-walk pairs (synthetic data)')
     p.add_argument('--walk_p', type=float, default=1.0,
                    help='return parameter p of node2vec\'s second-order walk (a step back to the previous node weighs 1/p)')
@@ -141,6 +146,28 @@ def refuse_eval_classifier(flags, G=None):
             evaluation.refuse_inputs(kind, width, embedding_width(flags), width is not None)
     if G is not None:
         evaluation.refuse_graph(G)
+
+
+def refuse_eval_clusters(flags, G=None):
+    """--eval_clusters needs the saved embeddings, K in {-1} U [1, 4096], a width the k-means kernel takes, for K = -1 a
+    single-label dataset and (once the graph is loaded) no more clusters than nodes: anything else is refused before training,
+    with the rule in the message."""
+    K = getattr(flags, "eval_clusters", 0)
+    if not K:
+        return 0
+    from . import clustering
+    single = False if flags.synthetic == 'ppi' else (True if flags.synthetic else None)
+    return clustering.refuse_flags("--eval_clusters", K, width=embedding_width(flags), save_embeddings=flags.save_embeddings,
+                                   G=G, single_label=single)
+
+
+def save_eval_clusters(G, out_dir):
+    """eval_clusters.txt, clusters.npy, cluster_centers.npy: k-means of every row of the table that was just written."""
+    from . import clustering
+    from . import engine as eng
+    base = "val_full" if FLAGS.full_inference else "val"
+    return clustering.evaluate_embedding_dir(eng.get_engine(), G, out_dir, FLAGS.eval_clusters, base=base,
+                                             seed=FLAGS.eval_clusters_seed)
 
 
 def eval_classifier_kinds(flags):
@@ -433,6 +460,8 @@ def train(G, context_pairs, embed_rows=None):
             n2v_retrain(G, model, minibatch, placeholders)
         if FLAGS.eval_classifier:
             save_eval_classifier(G, log_dir())
+        if FLAGS.eval_clusters:
+            save_eval_clusters(G, log_dir())
     if embed_rows is not None:
         from .supervised_train import save_embed_nodes
         save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=False)
@@ -492,11 +521,13 @@ def main(argv=None):
     st.refuse_importance(FLAGS)
     refuse_walk_flags(FLAGS)
     refuse_eval_classifier(FLAGS)
+    refuse_eval_clusters(FLAGS)
     tokens = st.read_embed_nodes(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)
     G = st.load_graph()
     refuse_eval_classifier(FLAGS, G)
+    refuse_eval_clusters(FLAGS, G)
     pairs = None
     if FLAGS.random_context:
         walks = FLAGS.train_prefix + "-walks.txt"

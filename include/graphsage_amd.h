@@ -1381,6 +1381,71 @@ int gs_col_moments(const float* Xa, const int32_t* rows_a, int64_t lda, int32_t 
                    double* mean, double* var, void* ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * KMEANS Lloyd's k-means over the rows of an embedding table (csrc/gs_kmeans.hip): squared norms, the fused assignment, and the
+ *      stable grouping of rows by cluster.  The centroid update is gs_csr_reduce_fwd (GS_CSR_MEAN) over (rowptr, members).
+ *
+ *      gs_kmeans_sqnorm: out[i] = sum_j X[rows ? rows[i] : i][j]^2 over fp32 rows, i < n.  One wave per row: every lane adds
+ *      the squares of its float4 columns in ascending column order (fmaf chain), then the xor butterfly; the order of the
+ *      additions is fixed, so two bit-identical rows give the same bits.  d % 4 == 0, 4 <= d <= 1024, ld >= d.
+ *
+ *      gs_kmeans_assign: with the table rows x_i = X[rows ? rows[i] : i], i < n, and the centroids c_j = C[j], j < k,
+ *        s(i, j)   = <x_i, c_j> - 0.5f * csq[j]             (the sweep of gs_rank_count: fp32 on the matrix cores, the same
+ *                                                             k-ordered chain for every cell; then ONE fp32 subtract)
+ *        assign[i] = argmax_j s(i, j), an exact tie going to the LOWEST j  (= argmin_j |x_i - c_j|^2 when csq[j] = |c_j|^2)
+ *        dist[i]   = max(0, xsq[i] - 2 s(i, assign[i]))      (dist nullable; xsq nullable: taken as 0)
+ *        stats     = { double inertia = sum_i dist[i];  int64 changed = #{i : assign[i] != prev[i]} }   (16 bytes; prev
+ *                    nullable: changed = 0)
+ *      One workgroup takes 128 rows and sweeps every centroid tile of 128, keeping a running (best score, id) in registers;
+ *      no score is written to memory.  It writes one fp64 partial of sum dist and one int64 partial of the changed count to
+ *      ws ([workgroups][2] words of 8 bytes, gs_kmeans_assign_ws_bytes(n) = 16 * ceil(n / 128)); a second launch of one
+ *      workgroup adds them in workgroup order (256 contiguous runs, each in order, then the runs in order).  No atomics:
+ *      bitwise repeatable.  Two bit-identical centroid rows score bit-equal.  Inputs are finite by contract (a NaN score never
+ *      wins; a row whose scores are all NaN gets 0).  1 <= k <= GS_KMEANS_MAX_K, d % 4 == 0, 4 <= d <= 1024, ld, ldc >= d,
+ *      1 <= n < 2^31; rows entries must lie in [0, n_rows) (the caller checks them once; the kernel clamps).
+ *
+ *      gs_kmeans_members: the stable grouping.  From assign int32 [n] it writes rowptr int64 [k + 1] (rowptr[j + 1] -
+ *      rowptr[j] = the members of cluster j) and members int32 [n]: cluster j's run holds rows[i] (i when rows is NULL) for
+ *      its members in ascending i.  Entries of assign outside [0, k) are skipped (rowptr[k] is then below n).  Per-chunk
+ *      histograms, a scan over the chunks and over the clusters, and an ordered re-walk: integers only, no global atomics,
+ *      and a result that does not depend on `chunk`, the entries one wave walks (0: the default, 2048; else a multiple of 64).
+ *      ws: int32 [ceil(n / chunk)][k] (gs_kmeans_members_ws_bytes(n, k, chunk)), 4-byte aligned.  n < 2^31.
+ *      gs_kmeans_desc is 128 and gs_kmeans_members_desc 72 bytes on every target (checked at compile time and by the
+ *      binding; passed by pointer, not part of gs_abi_struct_sizes).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_KMEANS_MAX_K 4096
+#define GS_KMEANS_CHUNK 2048
+typedef struct gs_kmeans_desc {
+    const float* X;            /* device [n_rows][ld] table */
+    const int32_t* rows;       /* device [n] rows of X; nullable (0 .. n-1) */
+    const float* C;            /* device [k][ldc] centroids */
+    const float* csq;          /* device [k]: |c_j|^2 (gs_kmeans_sqnorm) */
+    const float* xsq;          /* device [n]: |x_i|^2 by position i; nullable */
+    const int32_t* prev;       /* device [n]: the previous assignment; nullable */
+    int32_t* assign;           /* device [n] */
+    float* dist;               /* device [n]; nullable */
+    void* stats;               /* device, 8-byte aligned, 16 bytes: double inertia, int64 changed */
+    void* ws;                  /* device, 8-byte aligned, ws_bytes >= gs_kmeans_assign_ws_bytes(n) */
+    int64_t n, n_rows, ld, ldc, ws_bytes;
+    int32_t k, d;
+} gs_kmeans_desc;
+typedef struct gs_kmeans_members_desc {
+    const int32_t* assign;     /* device [n] */
+    const int32_t* rows;       /* device [n]; nullable (the members are 0 .. n-1) */
+    int64_t* rowptr;           /* device [k + 1] */
+    int32_t* members;          /* device [n] */
+    int32_t* ws;               /* device, ws_bytes >= gs_kmeans_members_ws_bytes(n, k, chunk) */
+    int64_t n, ws_bytes;
+    int32_t k, chunk;          /* chunk: 0 (GS_KMEANS_CHUNK) or a positive multiple of 64 */
+    int64_t reserved_;         /* 0 */
+} gs_kmeans_members_desc;
+int gs_kmeans_sqnorm(const float* X, int64_t ld, int64_t n_rows, const int32_t* rows, int64_t n, int32_t d, float* out,
+                     void* stream);
+int gs_kmeans_assign_ws_bytes(int64_t n, int64_t* bytes_out_host);
+int gs_kmeans_assign(const gs_kmeans_desc* desc_host, void* stream);
+int gs_kmeans_members_ws_bytes(int64_t n, int32_t k, int32_t chunk, int64_t* bytes_out_host);
+int gs_kmeans_members(const gs_kmeans_members_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
