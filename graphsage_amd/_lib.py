@@ -194,6 +194,8 @@ _PROTOS = {
     "gs_kmeans_assign": [_P, _P],
     "gs_kmeans_members_ws_bytes": [c_int64, c_int32, c_int32, POINTER(c_int64)],
     "gs_kmeans_members": [_P, _P],
+    "gs_ivf_ws_bytes": [c_int64, c_int32, c_int32, c_int32, POINTER(c_int64)],
+    "gs_ivf_search": [_P, _P],
 }
 
 
@@ -434,6 +436,21 @@ KMEANS_MAX_K = 4096                         # GS_KMEANS_MAX_K
 KMEANS_CHUNK = 2048                         # GS_KMEANS_CHUNK
 assert ctypes.sizeof(KmeansDesc) == 128    # static_assert in csrc/gs_kmeans.hip (passed by pointer, as LogregDesc)
 assert ctypes.sizeof(KmeansMembersDesc) == 72
+
+
+class IvfDesc(ctypes.Structure):
+    """struct gs_ivf_desc (include/graphsage_amd.h)"""
+    _fields_ = [("Xq", c_void_p), ("Zc", c_void_p), ("centers", c_void_p), ("list_ptr", c_void_p), ("list_ids", c_void_p),
+                ("src", c_void_p), ("f_rowptr", c_void_p), ("f_col", c_void_p),
+                ("ids", c_void_p), ("scores", c_void_p), ("count", c_void_p), ("scanned", c_void_p), ("ws", c_void_p),
+                ("Q", c_int64), ("ldq", c_int64), ("n_rows", c_int64), ("n_cand", c_int64), ("ldz", c_int64), ("ldc", c_int64),
+                ("n_list", c_int64), ("f_nnz", c_int64), ("ws_bytes", c_int64),
+                ("d", c_int32), ("k", c_int32), ("nprobe", c_int32), ("n_clusters", c_int32), ("flags", c_int32),
+                ("stop_after", c_int32)]
+
+
+IVF_MAX_PROBE = 128                         # GS_IVF_MAX_PROBE
+assert ctypes.sizeof(IvfDesc) == 200       # static_assert in csrc/gs_ivf.hip (passed by pointer, as TopkDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

@@ -1037,6 +1037,20 @@ class SampleAndAggregate(object):
         return inf.topk_full(self.engine, self._exact_table(graph), np.arange(graph.n_nodes) if nodes is None else nodes, k,
                              n_cand=graph.n_nodes, filt=graph.rank_filter() if filtered else None, weights=W)
 
+    def topk_ivf(self, graph, nodes=None, k=10, nprobe=8, n_clusters=0, filtered=True, seed=123, index=None):
+        """topk_full through an inverted file (retrieval.IVFIndex): the same table, candidates (n_cand = N), filter and bilinear
+        weights, but every query sees only the members of the nprobe lists it probes.  index: a retrieval.IVFIndex built by an
+        earlier call on this graph and these weights (None: retrieval.build_ivf with n_clusters lists, 0 = 4 sqrt(N), seeded
+        by `seed`).  Returns topk_full's dict plus "scanned" (int64 [n]) and "index"."""
+        from . import retrieval
+        W = self.link_pred_layer.vars['weights'].value if self.bilinear_weights else None
+        if index is None:
+            index = retrieval.build_ivf(self.engine, self._exact_table(graph), n_clusters, n_cand=graph.n_nodes, seed=seed)
+        res = index.search(np.arange(graph.n_nodes) if nodes is None else nodes, k, nprobe,
+                           filt=graph.rank_filter() if filtered else None, weights=W)
+        res["index"] = index
+        return res
+
     # ------------------------------------------------------------------------------ step machinery (shared)
     def _samplers(self):
         seen = []

@@ -1363,6 +1363,68 @@ def kmeans_members(assign, k, rows=None, rowptr=None, members=None, ws=None, chu
     return rowptr, members
 
 
+# ------------------------------------------------------------------------------------------ IVF (gs_ivf.hip)
+IVF_MAX_PROBE = _lib.IVF_MAX_PROBE  # largest nprobe of gs_ivf_search
+
+
+def ivf_ws_bytes(Q, n_clusters, k, nprobe):
+    """Bytes of the workspace gs_ivf_search needs for Q queries probing nprobe of n_clusters lists at this k."""
+    out = ctypes.c_int64(0)
+    call("gs_ivf_ws_bytes", Q, n_clusters, k, nprobe, ctypes.byref(out))
+    return out.value
+
+
+def ivf_search(Xq, Zc, centers, list_ptr, list_ids, k, nprobe, n_cand=None, src=None, f_rowptr=None, f_col=None, keep_src=False,
+               ids=None, scores=None, count=None, scanned=None, ws=None, chunk=RANK_CHUNK, stop_after=0, stream=None):
+    """gs_ivf_search: for every row q of Xq the k first candidates of gs_topk_select (same src, filter and keep_src) among the
+    members of the nprobe lists whose centres come first by (<Xq[q], centers[j]> descending, j ascending).  centers: Mat [C, d];
+    list_ptr int64 [C + 1] and list_ids int32 (ops.kmeans_members; entries in [0, n_cand), checked by the caller).  chunk:
+    the queries of one library call (the result does not depend on it); stop_after: 1 .. 5 ends every call after that step
+    (measurement only).  Returns (ids int32 [Q, k], scores float32 [Q, k], count int32 [Q], scanned int64 [Q])."""
+    who = "ivf_search"
+    Q, k, nprobe, chunk = Xq.rows, int(k), int(nprobe), int(chunk)
+    n_cand = Zc.rows if n_cand is None else int(n_cand)
+    q = _query_desc(_lib.IvfDesc(), (who, ""), Xq, Zc, Q, n_cand, f_rowptr, f_col, keep_src)
+    C = centers.rows
+    if centers.d != Zc.d or not 1 <= C <= KMEANS_MAX_K:
+        raise _lib.GraphsageAmdError("%s: centers is [%d, %d], Zc [%d, %d]; 1 to %d clusters" % (who, C, centers.d, Zc.rows, Zc.d,
+                                                                                            KMEANS_MAX_K))
+    if not 1 <= k <= TOPK_MAX:
+        raise _lib.GraphsageAmdError("%s: k=%d must lie in [1, %d]" % (who, k, TOPK_MAX))
+    if not 1 <= nprobe <= min(IVF_MAX_PROBE, C):
+        raise _lib.GraphsageAmdError("%s: nprobe=%d must lie in [1, min(%d, %d clusters)]" % (who, nprobe, IVF_MAX_PROBE, C))
+    if not 1 <= chunk <= RANK_CHUNK:
+        raise _lib.GraphsageAmdError("%s: chunk=%d must lie in [1, %d]" % (who, chunk, RANK_CHUNK))
+    if src is not None and (src.dtype != torch.int32 or src.numel() != Q):
+        raise _lib.GraphsageAmdError("%s: src must be an int32 vector with one entry per query" % who)
+    if (list_ptr.dtype, list_ids.dtype) != (torch.int64, torch.int32) or list_ptr.numel() != C + 1 or not (
+            list_ptr.is_contiguous() and list_ids.is_contiguous()):
+        raise _lib.GraphsageAmdError("%s: the lists are a dense int64 list_ptr [C + 1] with a dense int32 list_ids" % who)
+    dev = Xq.buf.device
+    ids = torch.empty((Q, k), dtype=torch.int32, device=dev) if ids is None else ids
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev) if scores is None else scores
+    count = torch.empty(Q, dtype=torch.int32, device=dev) if count is None else count
+    scanned = torch.empty(Q, dtype=torch.int64, device=dev) if scanned is None else scanned
+    if tuple(ids.shape) != (Q, k) or tuple(scores.shape) != (Q, k) or count.numel() != Q or scanned.numel() != Q or not (
+            ids.is_contiguous() and scores.is_contiguous() and count.is_contiguous() and scanned.is_contiguous()) or (
+            ids.dtype, scores.dtype, count.dtype, scanned.dtype) != (torch.int32, torch.float32, torch.int32, torch.int64):
+        raise _lib.GraphsageAmdError("%s: ids int32 [Q, k], scores float32 [Q, k], count int32 [Q] and scanned int64 [Q] must be "
+                                     "dense" % who)
+    need = max(ivf_ws_bytes(n, C, k, nprobe) for n in {min(Q, chunk), Q % chunk})        # the two chunk sizes that occur
+    if ws is None:
+        ws = torch.empty(max((need + 7) // 8, 2), dtype=torch.int64, device=dev)
+    q.centers, q.ldc, q.list_ptr, q.list_ids, q.n_list = centers.ptr, centers.ld, ptr(list_ptr), ptr(list_ids), list_ids.numel()
+    q.ws, q.ws_bytes, q.k, q.nprobe, q.n_clusters, q.stop_after = ptr(ws), ws.element_size() * ws.numel(), k, nprobe, C, stop_after
+    for q0 in range(0, max(Q, 1), chunk):
+        n = min(chunk, Q - q0)
+        q.Q, q.Xq = n, Xq.ptr + 4 * q0 * Xq.ld
+        q.src = ptr(src[q0:q0 + n]) if src is not None else None
+        q.ids, q.scores, q.count, q.scanned = (ptr(ids[q0:q0 + n]), ptr(scores[q0:q0 + n]), ptr(count[q0:q0 + n]),
+                                               ptr(scanned[q0:q0 + n]))
+        call("gs_ivf_search", ctypes.addressof(q), _s(stream))
+    return ids, scores, count, scanned
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

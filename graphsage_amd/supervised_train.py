@@ -103,7 +103,7 @@ def refuse_importance(flags):
     if flags.model == 'n2v':
         raise SystemExit("--importance_neighbors is not available with --model n2v: node2vec has no aggregation layers (it "
                          "samples no neighborhoods)")
-    for flag in ("rank_full", "topk_full"):
+    for flag in ("rank_full", "topk_full", "topk_ivf"):
         if getattr(flags, flag, False):
             raise SystemExit("--importance_neighbors cannot be combined with --%s: its filter is the known edges of the graph it "
                              "is given, and that must stay the true graph, not the importance neighborhoods" % flag)
@@ -162,9 +162,9 @@ def importance_adjacencies(flags, minibatch, n_nodes, device):
 
 
 def refuse_full_inference(flags):
-    """--full_inference (and --rank_full / --topk_full, which rank the embed_full embeddings) has no meaning for the models
+    """--full_inference (and --rank_full / --topk_full / --topk_ivf, which rank the embed_full embeddings) has no meaning for the models
     without a full-neighborhood form: say so before any work is done."""
-    for flag in ("full_inference", "rank_full", "topk_full", "embed_nodes"):
+    for flag in ("full_inference", "rank_full", "topk_full", "topk_ivf", "embed_nodes"):
         if getattr(flags, flag, False) and flags.model in ('n2v', 'graphsage_seq'):
             raise SystemExit("--%s is not available with --model %s: %s" % (
                 flag, flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v'

@@ -72,6 +72,17 @@ def build_flags(argv=None):
                    help='K > 0: after val.npy, the K best-scoring partners of every node among ALL nodes with the exact '
                         'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
                         'topk_full_scores.npy; not for n2v / graphsage_seq')
+    p.add_argument('--topk_ivf', type=int, default=0,
+                   help='K > 0: after val.npy (and --topk_full), the K best-scoring partners of every node through an inverted '
+                        'file over a k-means partition of the exact embeddings (topk_ivf: every query scans only the lists it '
+                        'probes) -> topk_ivf.npy / topk_ivf_scores.npy / ivf_centers.npy / ivf_labels.npy / topk_ivf.txt; not '
+                        'for n2v / graphsage_seq')
+    p.add_argument('--topk_ivf_clusters', type=int, default=0, help='lists of --topk_ivf: 1 to 4096 (0: 4 sqrt(N), at most 4096)')
+    p.add_argument('--topk_ivf_nprobe', type=int, default=8, help='lists every query of --topk_ivf probes: 1 to 128')
+    p.add_argument('--topk_ivf_recall', type=int, default=0,
+                   help='S > 0: S nodes are also searched exactly (topk_full) and the line of --topk_ivf carries their recall@K')
+    p.add_argument('--topk_ivf_seed', type=int, default=123,
+                   help='seed of the k-means++ seeding of --topk_ivf and of its recall sample')
     from .supervised_train import add_embed_nodes_flag, add_importance_flags
     add_embed_nodes_flag(p)
     add_importance_flags(p)
@@ -343,6 +354,56 @@ def save_full_topk(model, minibatch, out_dir, k):
     return res
 
 
+def refuse_topk_ivf(flags):
+    """--topk_ivf with K, lists, probes or a sample outside their ranges is refused before any work is done."""
+    if getattr(flags, "topk_ivf", 0):
+        from . import retrieval
+        retrieval.refuse_flags(flags.topk_ivf, flags.topk_ivf_clusters, flags.topk_ivf_nprobe, flags.topk_ivf_recall)
+
+
+def save_ivf_topk(model, minibatch, out_dir, flags):
+    """topk_ivf.npy (int32 [N, K]) / topk_ivf_scores.npy (float32 [N, K]): save_full_topk through an inverted file, with the
+    index (ivf_centers.npy, ivf_labels.npy) and the line of topk_ivf.txt.  With --topk_ivf_recall S the line carries the
+    recall@K of S nodes drawn from RandomState(--topk_ivf_seed) against their exact lists (topk_full)."""
+    from . import retrieval
+    from ._lib import GraphsageAmdError
+    from .supervised_train import full_graph
+    N, k, nprobe = minibatch.G.n_nodes, flags.topk_ivf, flags.topk_ivf_nprobe
+    graph = full_graph(minibatch, N)
+    t0 = time.time()
+    try:
+        index = retrieval.build_ivf(model.engine, model._exact_table(graph), flags.topk_ivf_clusters, n_cand=N,
+                                    seed=flags.topk_ivf_seed)
+    except GraphsageAmdError as e:
+        raise SystemExit("--topk_ivf: %s" % e)
+    build_time = time.time() - t0
+    if nprobe > index.n_clusters:
+        raise SystemExit("--topk_ivf_nprobe %d: the index has %d lists" % (nprobe, index.n_clusters))
+    t0 = time.time()
+    res = model.topk_ivf(graph, k=k, nprobe=nprobe, index=index)
+    search_time = time.time() - t0
+    sample, rec = min(flags.topk_ivf_recall, N), float("nan")
+    if sample > 0:
+        nodes = np.sort(np.random.RandomState(flags.topk_ivf_seed).choice(N, size=sample, replace=False))
+        rec = retrieval.recall(res["ids"][nodes], model.topk_full(graph, nodes=nodes, k=k)["ids"])
+    ids = res["ids"]
+    res.update({"k": k, "nodes": N, "clusters": index.n_clusters, "empty": index.empty, "nprobe": nprobe,
+                "list_min": int(index.sizes.min()), "list_max": int(index.sizes.max()),
+                "scanned_share": float(np.mean(res["scanned"]) / max(N, 1)) if ids.size else 0.0,
+                "filled": float(np.mean(ids >= 0)) if ids.size else 0.0, "recall": rec, "sample": sample,
+                "build_time": build_time, "search_time": search_time})
+    line = retrieval.result_line(res)
+    print(line)
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    with open(out_dir + retrieval.LINE_FILE, "w") as fp:
+        fp.write(line + "\n")
+    np.save(out_dir + "topk_ivf.npy", ids)
+    np.save(out_dir + "topk_ivf_scores.npy", res["scores"])
+    index.save(out_dir)
+    return res
+
+
 def construct_placeholders():
     """unsupervised_train.py:119-130"""
     from .models import Placeholder
@@ -456,6 +517,8 @@ def train(G, context_pairs, embed_rows=None):
             save_full_ranking(model, minibatch, log_dir())
         if FLAGS.topk_full:
             save_full_topk(model, minibatch, log_dir(), FLAGS.topk_full)
+        if FLAGS.topk_ivf:
+            save_ivf_topk(model, minibatch, log_dir(), FLAGS)
         if FLAGS.model == "n2v":
             n2v_retrain(G, model, minibatch, placeholders)
         if FLAGS.eval_classifier:
@@ -522,6 +585,7 @@ def main(argv=None):
     refuse_walk_flags(FLAGS)
     refuse_eval_classifier(FLAGS)
     refuse_eval_clusters(FLAGS)
+    refuse_topk_ivf(FLAGS)
     tokens = st.read_embed_nodes(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)

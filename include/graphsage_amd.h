@@ -1446,6 +1446,53 @@ int gs_kmeans_members_ws_bytes(int64_t n, int32_t k, int32_t chunk, int64_t* byt
 int gs_kmeans_members(const gs_kmeans_members_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * IVF  approximate top-k partners through an inverted file over a k-means partition (csrc/gs_ivf.hip): the sweep of TOPK over
+ *      gathered (query, cluster-member) tiles.
+ *        index   = centers [n_clusters][ldc] and the lists of gs_kmeans_members: list_ptr int64 [n_clusters + 1], list_ids int32
+ *                  [n_list], cluster j's run in ascending row id, every entry in [0, n_cand) and in one list only (the caller
+ *                  checks them once; the kernel clamps and never makes a stray read)
+ *        P_q     = the nprobe centres that come first in the order (<Xq[q], c_j> descending, j ascending)
+ *        C_q     = the candidate set of gs_topk_select (src, filter and flags as there)
+ *        ids[q], scores[q] = the first count[q] = min(k, .) members of C_q n U_{j in P_q} list_j in the total order (s
+ *                  descending, w ascending), s(q, w) = <Xq[q], Zc[w]>; entries at and beyond count[q] are -1 / -inf, a score of
+ *                  -0.0f is reported as +0.0f.  scanned[q] (nullable) = the members of the probed lists.
+ *      s(q, w) is the arithmetic of gs_topk_select bit for bit, and so are the key, the lists and the merge: with nprobe =
+ *      n_clusters the ids, the score bits and the counts are those of gs_topk_select.
+ *      Five steps, plain launches on the caller's stream, nothing read back: probe (gs_topk_select on the centres with k =
+ *      nprobe), group (gs_kmeans_members over the pairs p = j * Q + q of probe slot j and query q), plan (one workgroup: an
+ *      exclusive scan of ceil(pairs_c / 128)), scan (one workgroup per (cluster, 128 of its pairs) sweeps the list's member
+ *      tiles; grid floor(Q * nprobe / 128) + n_clusters, a workgroup without an item exits), merge (topk_merge_kernel with
+ *      slices = nprobe).  The filter row of src[q] is consulted by binary search, and only for a key that already beats the
+ *      row's threshold.  Integers and compares only after the MFMA chain, no atomics: bitwise reproducible.
+ *      1 <= k <= GS_TOPK_MAX; 1 <= nprobe <= min(GS_IVF_MAX_PROBE, n_clusters); 1 <= n_clusters <= GS_KMEANS_MAX_K; d is a
+ *      multiple of 4 in [4, 1024]; ld >= d; Q < 2^24 (the binding passes chunks of 65,536).  stop_after: 0, or 1 .. 5 to return
+ *      after that step (for measuring the steps; the outputs are then not written).
+ *      gs_ivf_ws_bytes(Q, n_clusters, k, nprobe): the probe's workspace and results, the pairs and their grouping, item_ptr and
+ *      Q * nprobe lists of cap = 64 * (1 + ceil(k / 64)) uint64 keys with their lengths, every part at a multiple of 16 bytes.
+ *      gs_ivf_desc is 200 bytes on every target (checked at compile time and by the binding; passed by pointer).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_IVF_MAX_PROBE 128
+typedef struct gs_ivf_desc {
+    const float* Xq;           /* device [Q][ldq] query rows */
+    const float* Zc;           /* device [n_rows][ldz] candidate table */
+    const float* centers;      /* device [n_clusters][ldc] */
+    const int64_t* list_ptr;   /* device [n_clusters + 1] */
+    const int32_t* list_ids;   /* device [n_list] */
+    const int32_t* src;        /* device [Q] or NULL: table row of the query node */
+    const int64_t* f_rowptr;   /* device [n_rows + 1] or NULL */
+    const int32_t* f_col;      /* device [f_nnz] or NULL (with f_rowptr) */
+    int32_t* ids;              /* device [Q][k] */
+    float* scores;             /* device [Q][k] */
+    int32_t* count;            /* device [Q] */
+    int64_t* scanned;          /* device [Q]; nullable */
+    void* ws;                  /* device, 16-byte aligned, ws_bytes >= gs_ivf_ws_bytes(Q, n_clusters, k, nprobe) */
+    int64_t Q, ldq, n_rows, n_cand, ldz, ldc, n_list, f_nnz, ws_bytes;
+    int32_t d, k, nprobe, n_clusters, flags, stop_after;     /* flags: 0 or GS_RANK_KEEP_SRC */
+} gs_ivf_desc;
+int gs_ivf_ws_bytes(int64_t Q, int32_t n_clusters, int32_t k, int32_t nprobe, int64_t* bytes_out_host);
+int gs_ivf_search(const gs_ivf_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
