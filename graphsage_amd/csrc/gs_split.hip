@@ -1,8 +1,8 @@
 // fp32 contractions on the bf16 matrix pipe, EXACTLY: every fp32 operand is cut into three bf16 pieces
 //     x = h + m + l,   h = top 8 significant bits of x, m = the next 8, l = the last 8   (24 = 8 + 8 + 8: no bit is lost)
 // and a product of two fp32 numbers is the sum of piece products, each of which the bf16 MFMA forms exactly (8 x 8 bits) and
-// accumulates in fp32.  Six of the nine piece products are kept -- hh, hm, mh, mm, hl, lh; the dropped ml, lm, ll are
-// <= 3 * 2^-24 |x y|, the size of ONE fp32 rounding -- so a K-term dot product carries the error of an fp32 FMA chain
+// accumulates in fp32.  Six of the nine piece products are kept -- hh, hm, mh, mm, hl, lh; the dropped ml, lm, ll are < 2^-21 |x y|
+// at worst (|m| < 2^-7 |x|) and 2^-24 of |x| . |w| on dense rows (tests/test_split_oracle.py) -- so a K-term dot product carries the error of an fp32 FMA chain
 // (measured against fp64: tests/test_split_gemm_gpu.py), while v_mfma_f32_32x32x16_bf16 issues every 32 cycles for 32 x 32 x
 // 16 MACs against 64 cycles for 32 x 32 x 2 on the fp32 form: 6 / 16 of the matrix-pipe time.  (MI355X_MICROARCH.md: fp32 MFMA
 // = the fp32 VECTOR rate, 1/16 of bf16; there is no xf32 on gfx950.)  dtype stays f32: inputs, outputs and accumulation are
