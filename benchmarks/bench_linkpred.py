@@ -6,11 +6,13 @@ training steps replayed as captured graphs.  bench.py times the default head onl
     xent_per_op       the same loss on the per-operator schedule (model.fuse_tail = False): the comparison point
     hinge, skipgram   gs_linkpred_loss_fwd_bwd on the per-operator schedule
     hinge_bilinear, xent_bilinear   + U = Y1 . W, dY1 = dU . W^T, dW = Y1^T . dU (three 512 x 256 x 256 products)
+    infonce, infonce_bilinear       the in-batch softmax, gs_linkpred_infonce_fwd_bwd (normalise | [U = Y1 . W] | the head's
+                      launches | [dY1 = dU . W^T] | normalisation backward); `hinge` is its yardstick: same schedule, the old head
 
 in ONE process, alternating the configurations round by round (other work shares the machine: the spread of a
 configuration over the rounds is printed next to its median).
 
-    python benchmarks/bench_linkpred.py [--steps 200] [--rounds 7] [--md profiles/linkpred_losses.md]
+    python benchmarks/bench_linkpred.py [--steps 200] [--rounds 7] [--heads hinge,infonce] [--md profiles/linkpred_losses.md]
 
 Prints one JSON line; --md also writes the table.
 """
@@ -33,6 +35,8 @@ CONFIGS = [
     ("skipgram", dict(loss_fn="skipgram"), True),
     ("hinge_bilinear", dict(loss_fn="hinge", bilinear_weights=True), True),
     ("xent_bilinear", dict(loss_fn="xent", bilinear_weights=True), True),
+    ("infonce", dict(loss_fn="infonce"), True),
+    ("infonce_bilinear", dict(loss_fn="infonce", bilinear_weights=True), True),
 ]
 
 
@@ -72,7 +76,14 @@ def main(argv=None):
     ap.add_argument("--avg_degree", type=int, default=492)
     ap.add_argument("--steps_per_launch", type=int, default=8)
     ap.add_argument("--md", default="", help="also write the table as markdown to this path")
+    ap.add_argument("--heads", default="", help="comma-separated subset of the configurations (default: all; xent_per_op, the "
+                                                "table's comparison point, is always among them)")
     args = ap.parse_args(argv)
+    want = set(args.heads.split(",")) | {"xent_per_op"} if args.heads else None
+    unknown = (want or set()) - {name for name, _, _ in CONFIGS}
+    if unknown:
+        ap.error("unknown heads: %s" % ", ".join(sorted(unknown)))
+    configs = [c for c in CONFIGS if want is None or c[0] in want]
     from graphsage_amd.utils import random_walk_pairs_device, reddit_shaped_device
     B, spl = 512, args.steps_per_launch
     t0 = time.time()
@@ -80,7 +91,7 @@ def main(argv=None):
     DG = reddit_shaped_device(dev, n_nodes=args.nodes, feat_dim=602, num_classes=41, avg_degree=args.avg_degree, seed=123)
     pairs = random_walk_pairs_device(DG.train_csr[0], DG.train_csr[1], DG.train_nodes, max_pairs=1000000, seed=123).cpu().numpy()
     models = []
-    for name, head, fuse_tail in CONFIGS:
+    for name, head, fuse_tail in configs:
         e, model = build(DG, pairs, head, fuse_tail, args)
         # eager + capture of every graph length the timed call uses, then one untimed region
         model.train_steps_device(B, 2 * spl + 2, steps_per_launch=spl)
@@ -114,8 +125,9 @@ def main(argv=None):
         "metric": "Reddit-shaped unsupervised graphsage_mean training step per link-prediction head, fan-out 25x10, batch 512, "
                   "dims 128/128, 20 negatives",
         "heads": res, "steps": args.steps, "rounds": args.rounds, "steps_per_launch": spl, "setup_s": round(setup_s, 1),
-        "bilinear_cost_us": {"hinge": res["hinge_bilinear"]["us_per_step"] - res["hinge"]["us_per_step"],
-                             "xent": res["xent_bilinear"]["us_per_step"] - base},
+        "bilinear_cost_us": {k: res[k + "_bilinear"]["us_per_step"] - res["xent_per_op" if k == "xent" else k]["us_per_step"]
+                             for k in ("hinge", "xent", "infonce")
+                             if k + "_bilinear" in res and ("xent_per_op" if k == "xent" else k) in res},
         "basis": "hipEventElapsedTime on each model's engine stream around %d-step regions, configurations alternated, "
                  "median over %d rounds" % (args.steps, args.rounds)}))
 

@@ -141,6 +141,12 @@ _PROTOS = {
     "gs_linkpred_loss_fwd_bwd_step": [c_int32, _P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_float, c_float, c_float,
                                       _P, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int, _P, _P,
                                       c_uint64, _P, c_uint64, _P, c_uint64, _P],
+    "gs_linkpred_infonce_ws_floats": [c_int64, c_int32, c_int32, c_int, POINTER(c_int64)],
+    "gs_linkpred_infonce_fwd_bwd": [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P, _P,
+                                    c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gs_linkpred_infonce_fwd_bwd_step": [_P, c_int64, _P, c_int64, c_int64, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P,
+                                         _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P, _P, c_uint64, _P,
+                                         c_uint64, _P, c_uint64, _P],
     "gs_linkpred_tail_supported": [c_int32, c_int32, c_int32],
     "gs_linkpred_tail": [_P, _P, c_int32, _P],
     "gs_linkpred_tail_means": [_P, _P, c_int32, _P],

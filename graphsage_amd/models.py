@@ -112,7 +112,8 @@ class SampleAndAggregate(object):
 
     def __init__(self, placeholders, features, adj, degrees, layer_infos, concat=True, aggregator_type="mean",
                  model_size="small", identity_dim=0, learning_rate=0.00001, weight_decay=0.0, neg_sample_size=20,
-                 world_size=1, rank=0, _defer_build=False, loss_fn='xent', bilinear_weights=False, pred_bias=False, **kwargs):
+                 world_size=1, rank=0, _defer_build=False, loss_fn='xent', bilinear_weights=False, pred_bias=False,
+                 loss_temperature=0.1, **kwargs):
         allowed_kwargs = {'name', 'logging', 'model_size'}
         for kwarg in kwargs.keys():
             assert kwarg in allowed_kwargs, 'Invalid keyword argument: ' + kwarg
@@ -120,6 +121,7 @@ class SampleAndAggregate(object):
         self.engine = get_engine()
         # arguments of the link-prediction layer (prediction.py:12-15; the reference hard-codes the defaults, models.py:363-366)
         self.loss_fn, self.bilinear_weights, self.pred_bias = loss_fn, bool(bilinear_weights), bool(pred_bias)
+        self.loss_temperature = float(loss_temperature)       # loss_fn='infonce' only (not in the reference)
         self.aggregator_cls = _aggregator_cls(aggregator_type)
         self.aggregator_type = aggregator_type
         self.model_size = model_size
@@ -250,7 +252,8 @@ class SampleAndAggregate(object):
         dim_mult = 2 if self.concat else 1
         self.link_pred_layer = BipartiteEdgePredLayer(dim_mult * self.dims[-1], dim_mult * self.dims[-1], self.placeholders,
                                                       act="sigmoid", loss_fn=self.loss_fn, bias=self.pred_bias,
-                                                      bilinear_weights=self.bilinear_weights, name='edge_predict')
+                                                      bilinear_weights=self.bilinear_weights,
+                                                      temperature=self.loss_temperature, name='edge_predict')
         e.finalize()
         if self.embeds is not None:
             self._refresh_embeds()
@@ -366,8 +369,17 @@ class SampleAndAggregate(object):
             fold = epilogue is not None and self._dropout_rate() == 0.0
             self._epilogue_folded = fold
             epi = (self.loss_dev, False, self.mrr_dev, self._epilogue_counters(epilogue)) if fold else None
-            self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B, self._loss_rows,
-                                                      self._rr_rows, self.aff_all, self._d_agg_out, epilogue=epi)
+            if self.loss_fn == 'infonce':
+                # the in-batch softmax masks its false negatives by the pairs' node ids (the head of the id buffer, on the
+                # device already for the sampler); validation takes its forward-only form
+                self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B,
+                                                          self._loss_rows, self._rr_rows, self.aff_all,
+                                                          self._d_agg_out if train else None, epilogue=epi,
+                                                          ids=(roots[:B], roots[B:2 * B]))
+            else:
+                self.link_pred_layer.loss_and_grads_fused(out, self.outputs_all, B, self.neg_sample_size, 1.0 / B,
+                                                          self._loss_rows, self._rr_rows, self.aff_all, self._d_agg_out,
+                                                          epilogue=epi)
         # loss = (sum_vars wd*l2_loss + xent) / batch_size  (:386-390, :378); the xent mean (and the mrr, :404) are formed
         # by the epilogue (folded: the weight-decay terms are added behind it; separate launch: it adds to them)
         self._weight_decay_loss([v for a in self.aggregators for v in a.vars.values()], 0.5 * self.weight_decay / B,

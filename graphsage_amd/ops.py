@@ -1028,6 +1028,47 @@ def linkpred_loss_fwd_bwd(kind, X, B, n_neg, neg_weight, margin, scale, loss_row
     call("gs_linkpred_loss_fwd_bwd_step", *args, ptr(loss_out), 1 if accumulate else 0, ptr(mrr_out), *cargs, _s(stream))
 
 
+# ------------------------------------------------------------------------------------------ in-batch softmax (gs_infonce.hip)
+INFONCE_TAU_RANGE = (0.01, 10.0)
+
+
+def linkpred_infonce_ws_floats(B, d, n_neg, train=True):
+    """gs_linkpred_infonce_ws_floats: fp32 elements of the head's workspace (row statistics, per-tile partial statistics and,
+    when training, the partial gradients of the cut sweeps)."""
+    n = ctypes.c_int64()
+    call("gs_linkpred_infonce_ws_floats", int(B), int(d), int(n_neg), 1 if train else 0, ctypes.byref(n))
+    return int(n.value)
+
+
+def linkpred_infonce_fwd_bwd(X, U, B, n_neg, tau, scale, loss_rows, rr_rows, aff_all, ws, dX=None, dU=None, ids=None,
+                             epilogue=None, stream=None):
+    """gs_linkpred_infonce_fwd_bwd[_step].  X [2B + n_neg, d] normalised rows, U [B, d] the left operand; ws: fp32 workspace of
+    linkpred_infonce_ws_floats(B, d, n_neg, train) elements (its first 2B hold the rows' (maximum, log sum) afterwards).
+    dX and dU both given: dU and rows [B, 2B + n_neg) of dX are written; both None: forward only.
+    ids: (ids1, ids2) int32 device tensors of the pairs' node ids (the false-negative mask) or None.
+    epilogue: (loss_out, accumulate, mrr_out, [(counter, delta)] * 3), as linkpred_loss_fwd_bwd."""
+    m = lambda a: (a.ptr, a.ld) if a is not None else (None, 0)
+    ids1, ids2 = ids if ids is not None else (None, None)
+    for t in (ids1, ids2):
+        if t is not None and (t.dtype != torch.int32 or t.numel() < B or not t.is_contiguous()):
+            raise _lib.GraphsageAmdError("linkpred_infonce_fwd_bwd: ids must be contiguous int32 tensors of B elements")
+    if ws.dtype != torch.float32 or not ws.is_contiguous():
+        raise _lib.GraphsageAmdError("linkpred_infonce_fwd_bwd: ws must be a contiguous float32 tensor")
+    for name, a in (("U", U), ("dX", dX), ("dU", dU)):
+        if a is not None and a.d != X.d:
+            raise _lib.GraphsageAmdError("linkpred_infonce_fwd_bwd: %s has width %d, X has %d" % (name, a.d, X.d))
+    args = (X.ptr, X.ld, U.ptr, U.ld, B, X.d, n_neg, float(tau), float(scale), ptr(ids1), ptr(ids2), ptr(loss_rows),
+            ptr(rr_rows)) + m(aff_all) + (ptr(ws), ws.numel()) + m(dX) + m(dU)
+    if epilogue is None:
+        call("gs_linkpred_infonce_fwd_bwd", *args, _s(stream))
+        return
+    loss_out, accumulate, mrr_out, counters = epilogue
+    cargs = []
+    for c, dlt in counters:
+        cargs += [ptr(c) if (c is not None and dlt) else None, int(dlt) if c is not None else 0]
+    call("gs_linkpred_infonce_fwd_bwd_step", *args, ptr(loss_out), 1 if accumulate else 0, ptr(mrr_out), *cargs, _s(stream))
+
+
 # ------------------------------------------------------------------------------------------ LSTM aggregator (gs_lstm.hip)
 def lstm_segments(segs):
     """segs: [(X Mat | None, ids int32 tensor | None, n sequences, T steps, row0)] -> (struct gs_lstm_seg array, number of

@@ -57,9 +57,12 @@ def build_flags(argv=None):
                    help='sampling law of the CSR sampler: reference (the reference\'s joint law on a virtual padded '
                         '[N+1, max_degree] table, minibatch.py:227-245 + neigh_samplers.py:24-29) | iid (independent '
                         'draws with replacement from the full neighbor list) | distinct (per-row without replacement)')
-    p.add_argument('--loss_fn', default='xent', choices=['xent', 'skipgram', 'hinge'],
+    p.add_argument('--loss_fn', default='xent', choices=['xent', 'skipgram', 'hinge', 'infonce'],
                    help='loss of the link-prediction layer (prediction.py:58-63); skipgram keeps the reference\'s sign; '
-                        'ignored by --model n2v')
+                        'infonce (not in the reference): softmax over the other contexts of the batch and the sampled '
+                        'negatives; ignored by --model n2v (infonce is refused there)')
+    p.add_argument('--loss_temperature', type=float, default=0.1,
+                   help='temperature of --loss_fn infonce, in [0.01, 10]; ignored by the other losses')
     p.add_argument('--bilinear_weights', action='store_true',
                    help='affinity u^T A v with a trainable A (prediction.py:68-92); ignored by --model n2v')
     p.add_argument('--full_inference', type=b, nargs='?', const=True, default=False,
@@ -129,6 +132,19 @@ def refuse_walk_flags(flags):
         walk_thresholds(flags.walk_p, flags.walk_q)
     except ValueError as e:
         raise SystemExit("--walk_p / --walk_q: %s" % e)
+
+
+def refuse_loss_flags(flags):
+    """--loss_fn infonce: the temperature must lie in the head's range and the model must have a link-prediction layer; refused
+    before any work is done, with the rule in the message."""
+    if getattr(flags, "loss_fn", "xent") != "infonce":
+        return
+    if flags.model == 'n2v':
+        raise SystemExit("--loss_fn infonce: --model n2v has no link-prediction layer")
+    from .ops import INFONCE_TAU_RANGE
+    lo, hi = INFONCE_TAU_RANGE
+    if not lo <= flags.loss_temperature <= hi:
+        raise SystemExit("--loss_temperature %g: must lie in [%g, %g]" % (flags.loss_temperature, lo, hi))
 
 
 def embedding_width(flags):
@@ -435,7 +451,7 @@ def train(G, context_pairs, embed_rows=None):
     sampler = UniformNeighborSampler(adj_info, law=FLAGS.sampler_law, max_degree=FLAGS.max_degree)
     kw = dict(model_size=FLAGS.model_size, identity_dim=FLAGS.identity_dim, learning_rate=FLAGS.learning_rate,
               weight_decay=FLAGS.weight_decay, neg_sample_size=FLAGS.neg_sample_size, logging=True,
-              loss_fn=FLAGS.loss_fn, bilinear_weights=FLAGS.bilinear_weights)
+              loss_fn=FLAGS.loss_fn, bilinear_weights=FLAGS.bilinear_weights, loss_temperature=FLAGS.loss_temperature)
     if FLAGS.model in ('graphsage_mean', 'graphsage'):          # unsupervised_train.py:160-172
         layer_infos = [SAGEInfo("node", sampler, FLAGS.samples_1, FLAGS.dim_1),
                        SAGEInfo("node", sampler, FLAGS.samples_2, FLAGS.dim_2)]
@@ -583,6 +599,7 @@ def main(argv=None):
     st.refuse_samples(FLAGS)
     st.refuse_importance(FLAGS)
     refuse_walk_flags(FLAGS)
+    refuse_loss_flags(FLAGS)
     refuse_eval_classifier(FLAGS)
     refuse_eval_clusters(FLAGS)
     refuse_topk_ivf(FLAGS)

@@ -561,6 +561,35 @@ int gs_linkpred_loss_fwd_bwd_step(int32_t loss_kind, const float* X, int64_t ldx
                                   uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1, uint64_t* c2, uint64_t d2,
                                   void* stream);
 
+/* The in-batch softmax (InfoNCE) head (csrc/gs_infonce.hip): every normalised outputs2 row of the batch and every sampled
+ * negative is a candidate for every left-operand row.  X [2B + n_neg, d] are the NORMALISED rows, U [B, d] the left operand
+ * (rows [0, B) of X themselves, or l2_normalize(outputs1) . W), C = rows [B, 2B + n_neg) of X:
+ *   L_ij   = <U_i, C_j> / tau
+ *   mask   : j < B, j != i and (ids2[j] == ids2[i] or ids2[j] == ids1[i]) -> candidate j is left out of row i (ids1 / ids2: the
+ *            int32 node ids of the pairs, both given or both NULL = nothing masked; sampled negatives are never masked)
+ *   loss_rows[i] = logsumexp_{j not masked} L_ij - L_ii
+ *   dU = G . C,  rows [B, 2B + n_neg) of dX = G^T . U,   G = scale (softmax - I) / tau   (rows [0, B) of dX are left alone)
+ *   aff_all [B, n_neg + 1] = [<U_i, neg_q> | <U_i, y2_i>] (raw, not divided by tau; required: the ranks are counted from it)
+ *   and rr_rows as gs_linkpred_loss_fwd_bwd.
+ * ws: fp32 workspace of gs_linkpred_infonce_ws_floats(B, d, n_neg, train) floats, 16-byte aligned: the rows' statistics
+ * (maximum, log of the rescaled sum), the per-tile partial statistics and, when training, the partial gradients of the cut
+ * sweeps.  dU == dX == NULL: forward only (train = 0; the same loss_rows / rr_rows / aff_all bits).  No float atomics, every
+ * sum in a fixed order: bitwise repeatable.  The _step form carries the epilogue of gs_linkpred_norm_fwd_bwd_step, once.
+ * d in {64,128,256,512}; B >= 1; n_neg >= 0 (no LDS bound; B + n_neg <= 65,535 * 128, refused beyond); tau in [0.01, 10];
+ * X / U / dX / dU 16-byte aligned, ld % 4 == 0, ld >= d.  The workspace grows with B * (B + n_neg) / 64 floats (two per row and
+ * candidate tile) plus at most 8 * (2B + n_neg) * d for the partial gradients. */
+int gs_linkpred_infonce_ws_floats(int64_t B, int32_t d, int32_t n_neg, int train, int64_t* floats_out_host);
+int gs_linkpred_infonce_fwd_bwd(const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B, int32_t d, int32_t n_neg,
+                                float tau, float scale, const int32_t* ids1, const int32_t* ids2, float* loss_rows,
+                                float* rr_rows, float* aff_all, int64_t ld_aff, float* ws, int64_t ws_floats, float* dX,
+                                int64_t lddx, float* dU, int64_t lddu, void* stream);
+int gs_linkpred_infonce_fwd_bwd_step(const float* X, int64_t ldx, const float* U, int64_t ldu, int64_t B, int32_t d,
+                                     int32_t n_neg, float tau, float scale, const int32_t* ids1, const int32_t* ids2,
+                                     float* loss_rows, float* rr_rows, float* aff_all, int64_t ld_aff, float* ws,
+                                     int64_t ws_floats, float* dX, int64_t lddx, float* dU, int64_t lddu, float* loss_out,
+                                     int accumulate, float* mrr_out, uint64_t* c0, uint64_t d0, uint64_t* c1, uint64_t d1,
+                                     uint64_t* c2, uint64_t d2, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K6  optimizer              replaces supervised_models.py:95-99 (clip_by_value +-5, Adam) and the
  *                             weight-decay terms :104-108
