@@ -271,7 +271,8 @@ def markdown(res):
         out.append("The fused kernel beats the topk route at every shape measured, k = 1024 included (fused / topk above).")
     out += ["", "## Resources", "",
             "`hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage`: kmeans_assign_kernel 234 vector registers, "
-            "84 scalar, no scratch, no spill, 73,776 B of LDS, two workgroups per CU (gs_topk.hip's select kernel: 206 "
+            "90 scalar (84 before the sweeps took the one tile pipeline of gs_rank_dev.h: profiles/sweep_pipeline.md), "
+            "no scratch, no spill, 73,776 B of LDS, two workgroups per CU (gs_topk.hip's select kernel: 204 "
             "registers, 77,824 B).  kmeans_finish_kernel 61 registers / 4,096 B; kmeans_sqnorm_kernel 12 / 0; kmeans_hist_kernel "
             "50 / 16,384 B; kmeans_place_kernel 34 / 16,384 B; kmeans_scan_chunks_kernel 6 / 0; kmeans_scan_k_kernel 26 / 2,048 B. "
             "No scratch in any of them.", ""]

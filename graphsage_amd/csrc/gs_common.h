@@ -59,6 +59,11 @@ __host__ __device__ static inline int64_t gs_ceil_div(int64_t a, int64_t b) { re
     GS_REQUIRE((ptr) != nullptr && gs_aligned16(ptr) && ((ld) % 4) == 0,                   \
                "%s: matrix must be non-null, 16-byte aligned, ld %% 4 == 0 (ld=%lld)", name, (long long)(ld))
 
+// ... with the name in two parts: `who` (an entry point's name) and the matrix's field
+#define GS_CHECK_MAT_OF(ptr, ld, who, field)                                               \
+    GS_REQUIRE((ptr) != nullptr && gs_aligned16(ptr) && ((ld) % 4) == 0,                   \
+               "%s %s: matrix must be non-null, 16-byte aligned, ld %% 4 == 0 (ld=%lld)", who, field, (long long)(ld))
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -8,8 +8,9 @@
 //   dU = G . C        dC = G^T . U            (dC = rows [B, 2B + n_neg) of dX)
 //   aff_all row = [<u_i, neg_q> .. | <u_i, y2_i>] (raw, not divided by tau);  rr_i = 1 / (1 + #{q : <u_i, neg_q> >= <u_i, y2_i>})
 //
-// The contractions run the 128 x 128 fp32-MFMA tile code of gs_rank_dev.h (rank_load_tiles, rank_store_tiles, rank_compute:
-// BK = 32, two LDS stages).  After a tile's K loop the 2 x 2 x 16 accumulator cells of every lane go to a tile buffer in LDS,
+// The logit tiles run the 128 x 128 fp32-MFMA tile pipeline of gs_rank_dev.h (rank_first_loads, rank_k_loop: BK = 32, two LDS
+// stages), the gradient contractions its rank_compute alone.
+// After a tile's K loop the 2 x 2 x 16 accumulator cells of every lane go to a tile buffer in LDS,
 // laid out as four [128][RK_KP] chunks of 32 columns -- the layout rank_compute reads an A operand in -- and two threads per
 // row (columns [0, 64) and [64, 128), ascending) take it from there.  The B x (B + n_neg) matrix is never written to memory.
 // One such tile is 13.6 us of fp32 MFMA at d = 256 (the rate of ONE CU), so the cut that matters at the driver's B = 512 is
@@ -54,48 +55,18 @@ struct NceArgs {
     float inv_tau, gscale;              // 1 / tau, scale / tau
 };
 
-// acc = P[p0 .. p0 + 128, :] . S[s0 .. s0 + 128, :]^T over K = d: the K loop of gs_kmeans.hip.  Rows at or beyond n_p / n_s
-// read as zeros.  The caller puts a __syncthreads between two calls (the stage buffers change hands).
+// acc = P[p0 .. p0 + 128, :] . S[s0 .. s0 + 128, :]^T over K = d through the pipeline of gs_rank_dev.h.  Rows at or beyond
+// n_p / n_s read as zeros.  The caller puts a __syncthreads between two calls (the stage buffers change hands).
 __device__ __forceinline__ void nce_tile(const float* __restrict__ P, const int64_t ldp, const int64_t n_p, const int64_t p0,
                                          const float* __restrict__ S, const int64_t lds_, const int64_t n_s, const int64_t s0,
-                                         const int d, float* smem, const int tid, const int wm, const int wn, const int l31,
-                                         const int lh, f32x16 (&acc)[2][2]) {
-    constexpr int BM = RK_BM, BK = RK_BK, KP = RK_KP;
-    const int srow = tid >> 3, sk = (tid & 7) * 4;
-    const float* a_row[4];
-    const float* b_row[4];
-    bool a_ok[4], b_ok[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int64_t ia = p0 + p * 32 + srow, ib = s0 + p * 32 + srow;
-        a_ok[p] = ia < n_p;
-        b_ok[p] = ib < n_s;
-        a_row[p] = P + (a_ok[p] ? ia : 0) * ldp + sk;
-        b_row[p] = S + (b_ok[p] ? ib : 0) * lds_ + sk;
-    }
-    float* As0 = smem;
-    float* Bs0 = smem + BM * KP;
-    float* As1 = smem + RK_STAGE_FLOATS;
-    float* Bs1 = smem + RK_STAGE_FLOATS + BM * KP;
-    f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
-    rank_load_tiles(0, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-    rank_load_tiles(BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);          // d >= 64: a second stage exists
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-    for (int k0 = 0; k0 < d; k0 += 2 * BK) {
-        rank_store_tiles(ra0, rb0, As0, Bs0, srow, sk);
-        __syncthreads();
-        if (k0 + 2 * BK < d) rank_load_tiles(k0 + 2 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-        rank_compute(As0, Bs0, wm, wn, l31, lh, acc);
-        rank_store_tiles(ra1, rb1, As1, Bs1, srow, sk);
-        __syncthreads();
-        if (k0 + 3 * BK < d) rank_load_tiles(k0 + 3 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
-        rank_compute(As1, Bs1, wm, wn, l31, lh, acc);
-    }
+                                         const int d, float* smem, const int wm, const int wn, const int l31, const int lh,
+                                         f32x16 (&acc)[2][2]) {
+    RankOperand A, B;
+    rank_rows(A, P, ldp, p0, n_p);
+    rank_rows(B, S, lds_, s0, n_s);
+    RankRegs ra0, rb0, ra1, rb1;
+    rank_first_loads<true>(A, B, d, ra0, rb0, ra1, rb1);      // d is 64, 128, 256 or 512: whole pairs of stages
+    rank_k_loop<true>(A, B, d, smem, ra0, rb0, ra1, rb1, wm, wn, l31, lh, acc);
 }
 
 // the lane's accumulator cells into the tile buffer: cell (row, col) at T[(col >> 5) NCE_CH + row RK_KP + (col & 31)]
@@ -107,7 +78,7 @@ __device__ __forceinline__ void nce_dump(const f32x16 (&acc)[2][2], float* T, co
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int row = wm * 64 + tm * 32 + rank_acc_row(e, lh);
                 T[(wn * 2 + tn) * NCE_CH + row * RK_KP + l31] = acc[tm][tn][e];
             }
 }
@@ -139,7 +110,7 @@ __global__ __launch_bounds__(256) void infonce_stats_kernel(const NceArgs g) {
         id2 = g.ids2[i];
     }
     f32x16 acc[2][2];
-    nce_tile(g.U, g.ldu, B, m0, g.C, g.ldc, n_cand, n0, g.d, smem, tid, wm, wn, l31, lh, acc);
+    nce_tile(g.U, g.ldu, B, m0, g.C, g.ldc, n_cand, n0, g.d, smem, wm, wn, l31, lh, acc);
     if (tid < RK_BN) cid2[tid] = (has_ids && n0 + tid < B) ? g.ids2[n0 + tid] : 0;
     nce_dump(acc, T, wm, wn, l31, lh);
     __syncthreads();
@@ -281,22 +252,15 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const NceArgs g, cons
     }
 
     f32x16 oacc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) oacc[a][b][e] = 0.f;
+    rank_zero(oacc);
 
-    float* Bs0 = smem + RK_BM * RK_KP;
-    float* Bs1 = smem + RK_STAGE_FLOATS + RK_BM * RK_KP;
     // the swept rows' output columns, transposed into a B stage: lane k = tid & 31 takes swept row k of the chunk
     const int tk = tid & 31, tc = tid >> 5;
 
     for (int tile = t0; tile < t1; ++tile) {
         const int64_t s0 = (int64_t)tile * RK_BN;
         f32x16 acc[2][2];
-        nce_tile(P, ldp, n_p, p0, S, lds_, n_s, s0, d, smem, tid, wm, wn, l31, lh, acc);
+        nce_tile(P, ldp, n_p, p0, S, lds_, n_s, s0, d, smem, wm, wn, l31, lh, acc);
         if (tid < RK_BN) {
             const int64_t c = s0 + tid;
             int32_t a1 = 0, a2 = 0;
@@ -356,7 +320,7 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const NceArgs g, cons
         };
         load_chunk(0);
         for (int ch = 0; ch < 4; ++ch) {
-            float* Bs = (ch & 1) ? Bs1 : Bs0;
+            float* Bs = rank_stage_b(smem, ch & 1);
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int cc = (p * 8 + tc) * 4;
@@ -378,7 +342,7 @@ __global__ __launch_bounds__(256) void infonce_grad_kernel(const NceArgs g, cons
         for (int tn = 0; tn < 2; ++tn)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int64_t row = p0 + wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int64_t row = p0 + wm * 64 + tm * 32 + rank_acc_row(e, lh);
                 const int col = col0 + wn * 64 + tn * 32 + l31;
                 if (row < n_p && col < d) out[row * ldo + col] = oacc[tm][tn][e];
             }

@@ -7,7 +7,8 @@
 //   out     = the first min(k, .) members of C_q n U_{j in P_q} list_j by (<x_q, z_w> descending, w ascending)
 //
 // A (query row, candidate row) pair goes through rank_compute's k-ordered chain whatever tile it sits in, and the key, the list
-// code and the merge are gs_topk_dev.h: with nprobe = C the ids, the score bits and the counts are those of gs_topk_select.
+// code, the dump, the offer and the merge are gs_topk_dev.h: with nprobe = C the ids, the score bits and the counts are those
+// of gs_topk_select.
 //
 // Five steps per call, plain launches on the caller's stream, nothing read back in between:
 //   1 probe   gs_topk_select on (queries, centres) with k = nprobe                                -> probe ids [Q][nprobe]
@@ -17,8 +18,8 @@
 //             scan of ceil(pairs_c / 128).  The scan grid is the bound floor(Q nprobe / 128) + C; a workgroup finds its item by a
 //             binary search on item_ptr (at most 13 steps) or exits.  Integers, no atomics, no workgroup waits on another.
 //   4 scan    ivf_scan_kernel, one workgroup per item: A operand rows Xq + (p mod Q) ldq of its 128 pairs (fixed), B operand
-//             rows Zc + list_ids[.] ldz of one member tile after the other; rank_load_tiles / rank_store_tiles / rank_compute
-//             unchanged, then the dump-and-scan epilogue of topk_select_kernel with w = ids[col] (the tile's 128 ids wait in
+//             rows Zc + list_ids[.] ldz of one member tile after the other; the tile pipeline of gs_rank_dev.h (rank_first_loads,
+//             rank_k_loop), then topk_dump and the row scan of topk_select_kernel with w = ids[col] (the tile's 128 ids wait in
 //             LDS, two buffers: the next tile's are fetched under this tile's row scan).  Pair p's key list is ws + p cap, its
 //             length counts[p]: the [slices][Q][cap] layout of topk_merge_kernel with slices = nprobe.  One workgroup owns a
 //             pair's list for the whole launch; counts is cleared first (a pair of an empty probe slot is never scanned).
@@ -36,7 +37,7 @@
 // does, a ballot skips the group.  tau only rises, so a key tested against an older tau is at worst searched for in vain.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; quoted in profiles/topk_ivf.md):
-// ivf_scan_kernel 198 vector registers, 102 scalar, no scratch, no spill of either kind, 78,848 B of LDS (the two stage buffers
+// ivf_scan_kernel 198 vector registers, 100 scalar, no scratch, no spill of either kind, 78,848 B of LDS (the two stage buffers
 // and 5,120 B of per-pair state and member ids; topk_select_kernel: 77,824 B): two workgroups per CU under
 // __launch_bounds__(256, 2).  The list and candidate bounds are 32-bit on purpose: as 64-bit values they cost 2 scalar spills.
 // ivf_pairs_kernel 14 registers, ivf_plan_kernel 44 and 1,024 B of LDS.
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void ivf_plan_kernel(const int64_t* __restrict
 
 // (256, 2): a budget of 256 registers per lane, two workgroups per CU
 __global__ __launch_bounds__(256, 2) void ivf_scan_kernel(const IvfArgs g) {
-    constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
+    constexpr int BM = RK_BM, BN = RK_BN;
     __shared__ __attribute__((aligned(16))) float smem[2 * RK_STAGE_FLOATS];
     __shared__ uint64_t tauS[BM];
     __shared__ int64_t f0S[BM];                  // the filter run of the row's query node: first entry, length
@@ -155,74 +156,39 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_kernel(const IvfArgs g) {
 
     // ---- operand rows of this thread: 4 query rows (fixed), 4 member rows (per tile); 8 threads x float4 span BK
     const int srow = tid >> 3, sk = (tid & 7) * 4;
-    const float* a_row[4];
-    bool a_ok[4];
+    RankOperand A, B;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int32_t pr = pairS[p * 32 + srow];
-        a_ok[p] = pr >= 0;
-        a_row[p] = g.Xq + (a_ok[p] ? (int64_t)pr % g.Q : 0) * g.ldq + sk;
+        A.ok[p] = pr >= 0;
+        A.row[p] = g.Xq + (A.ok[p] ? (int64_t)pr % g.Q : 0) * g.ldq + sk;
     }
-    const float* b_row[4];
-    bool b_ok[4];
     auto member_rows = [&](const int tile) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int j = l0 + tile * BN + p * 32 + srow;                 // (j - l0 < tiles BN <= l1 - l0 + 127: no overflow)
             int32_t w = j < l1 ? g.list_ids[j] : -1;
-            b_ok[p] = w >= 0 && w < g.n_cand;                             // the caller checked; never a stray read (n_cand <= n_rows)
-            w = b_ok[p] ? w : -1;
-            b_row[p] = g.Zc + (int64_t)(b_ok[p] ? w : 0) * g.ldz + sk;
+            B.ok[p] = w >= 0 && w < g.n_cand;                             // the caller checked; never a stray read (n_cand <= n_rows)
+            w = B.ok[p] ? w : -1;
+            B.row[p] = g.Zc + (int64_t)(B.ok[p] ? w : 0) * g.ldz + sk;
             if ((tid & 7) == 0) idS[tile & 1][p * 32 + srow] = w;
         }
     };
 
-    float* As0 = smem;
-    float* Bs0 = smem + BM * KP;
-    float* As1 = smem + RK_STAGE_FLOATS;
-    float* Bs1 = smem + RK_STAGE_FLOATS + BM * KP;
-
-    // the software pipeline of topk_select_kernel: a tile's first two stages are requested before the previous tile's rows are scanned
-    f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
+    // the pipeline of gs_rank_dev.h, with a tile's first two stages requested before the previous tile's rows are scanned
+    RankRegs ra0, rb0, ra1, rb1;
     auto first_loads = [&](const int tile) {
         member_rows(tile);
-        rank_load_tiles(0, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-        if (BK < d) rank_load_tiles(BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
+        rank_first_loads(A, B, d, ra0, rb0, ra1, rb1);
     };
     if (0 < tiles) first_loads(0);
 
     for (int tile = 0; tile < tiles; ++tile) {
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        rank_k_loop(A, B, d, smem, ra0, rb0, ra1, rb1, wm, wn, l31, lh, acc);
 
-        for (int k0 = 0; k0 < d; k0 += 2 * BK) {
-            rank_store_tiles(ra0, rb0, As0, Bs0, srow, sk);
-            __syncthreads();
-            if (k0 + 2 * BK < d) rank_load_tiles(k0 + 2 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-            rank_compute(As0, Bs0, wm, wn, l31, lh, acc);
-            if (k0 + BK < d) {
-                rank_store_tiles(ra1, rb1, As1, Bs1, srow, sk);
-                __syncthreads();
-                if (k0 + 3 * BK < d) rank_load_tiles(k0 + 3 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
-                rank_compute(As1, Bs1, wm, wn, l31, lh, acc);
-            }
-        }
-
-        // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
-        __syncthreads();                         // every wave is done with the stage buffers
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    smem[(wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * TK_LD + wn * 64 + tn * 32 + l31] = acc[tm][tn][e];
-        __syncthreads();
+        // ---- epilogue
+        topk_dump(acc, smem, wm, wn, l31, lh);
         if (tile + 1 < tiles) first_loads(tile + 1);         // (writes the OTHER id buffer: its readers passed the barrier that ended tile - 1)
 
         // the two columns of this lane: their table rows (-1: no such column, or an id outside [0, n_cand): no candidate)
@@ -297,21 +263,10 @@ __global__ __launch_bounds__(256, 2) void ivf_scan_kernel(const IvfArgs g) {
                             if (flen[i] > 0 && at[i][h] == w_col[h]) key[i0 + i][h] = 0ull;
                 }
             }
-#pragma unroll
-            for (int i = 0; i < TK_ROWS; ++i) {
-                const int r = r0 + i;
+            topk_offer(key, tau_r, r0, cntS, tauS, g.cap, g.k, lane, [&](const int r) -> uint64_t* {
                 const int32_t p = topk_uniform(pairS[r]);
-                uint64_t tau = topk_uniform(tau_r[i]);
-                if (p < 0 || __ballot(key[i][0] > tau || key[i][1] > tau) == 0ull) continue;      // after warm-up: the usual case
-                int cnt = topk_uniform(cntS[r]);
-                uint64_t* list = g.lists + (int64_t)p * g.cap;
-                topk_push(list, g.cap, g.k, cnt, tau, key[i][0], lane);
-                topk_push(list, g.cap, g.k, cnt, tau, key[i][1], lane);
-                if (lane == 0) {
-                    cntS[r] = cnt;
-                    tauS[r] = tau;
-                }
-            }
+                return p >= 0 ? g.lists + (int64_t)p * g.cap : nullptr;
+            });
         }
         // the stage buffers change hands here
         __syncthreads();
@@ -382,25 +337,16 @@ extern "C" int gs_ivf_search(const gs_ivf_desc* desc_host, void* stream) {
     GS_REQUIRE(q.n_rows >= 0 && q.n_rows <= 0x7fffffffll && q.n_cand >= 0 && q.n_list >= 0 && q.n_list <= 0x7fffffffll,
                "gs_ivf_search: bad sizes n_rows=%lld n_cand=%lld n_list=%lld", (long long)q.n_rows, (long long)q.n_cand,
                (long long)q.n_list);
-    GS_REQUIRE(q.n_cand <= q.n_rows, "gs_ivf_search: n_cand=%lld exceeds the table's n_rows=%lld", (long long)q.n_cand,
-               (long long)q.n_rows);
-    GS_REQUIRE(q.d >= 4 && q.d <= 1024 && (q.d & 3) == 0, "gs_ivf_search: d=%d must be a multiple of 4 in [4, 1024]", q.d);
     int rc = ivf_check_sizes("gs_ivf_search", q.Q, q.n_clusters, q.k, q.nprobe);
     if (rc != GS_OK) return rc;
-    GS_REQUIRE((q.flags & ~GS_RANK_KEEP_SRC) == 0, "gs_ivf_search: unknown flags 0x%x", (unsigned)q.flags);
     GS_REQUIRE(q.stop_after >= 0 && q.stop_after <= 5, "gs_ivf_search: stop_after=%d must lie in [0, 5]", q.stop_after);
-    if (q.Q == 0) return GS_OK;
-    GS_CHECK_MAT(q.Xq, q.ldq, "gs_ivf_search Xq");
-    GS_CHECK_MAT(q.Zc, q.ldz, "gs_ivf_search Zc");
+    rc = rank_check_query("gs_ivf_search", q);
+    if (rc != GS_OK || q.Q == 0) return rc;
     GS_CHECK_MAT(q.centers, q.ldc, "gs_ivf_search centers");
-    GS_REQUIRE(q.ldq >= q.d && q.ldz >= q.d && q.ldc >= q.d, "gs_ivf_search: ld must be >= d");
+    GS_REQUIRE(q.ldc >= q.d, "gs_ivf_search: ld must be >= d");
     GS_REQUIRE(q.list_ptr && q.list_ids, "gs_ivf_search: list_ptr and list_ids must be non-null");
     GS_REQUIRE(q.ids && q.scores && q.count, "gs_ivf_search: ids, scores and count must be non-null");
-    GS_REQUIRE((q.f_rowptr == nullptr) == (q.f_col == nullptr), "gs_ivf_search: f_rowptr and f_col go together");
-    GS_REQUIRE(!q.f_rowptr || q.src, "gs_ivf_search: a filter is indexed by src, which is null");
-    GS_REQUIRE(!q.src || q.n_rows >= 1, "gs_ivf_search: the candidate table is empty (src needs a row)");
     GS_REQUIRE(q.n_list == 0 || q.n_rows >= 1, "gs_ivf_search: the candidate table is empty (the lists name rows)");
-    GS_REQUIRE(q.f_nnz >= 0, "gs_ivf_search: f_nnz=%lld", (long long)q.f_nnz);
     IvfLayout L;
     rc = ivf_layout(q.Q, q.n_clusters, q.k, q.nprobe, &L);
     if (rc != GS_OK) return rc;
@@ -452,7 +398,7 @@ extern "C" int gs_ivf_search(const gs_ivf_desc* desc_host, void* stream) {
     g.counts = reinterpret_cast<int32_t*>(ws + L.counts);
     g.Q = q.Q; g.n_pairs = n_pairs; g.ldq = q.ldq; g.n_rows = q.n_rows; g.ldz = q.ldz; g.f_nnz = q.f_nnz;
     g.n_cand = (int32_t)q.n_cand; g.n_list = (int32_t)q.n_list;
-        g.d = q.d; g.k = q.k; g.cap = (int32_t)topk_cap(q.k); g.n_clusters = C;
+    g.d = q.d; g.k = q.k; g.cap = (int32_t)topk_cap(q.k); g.n_clusters = C;
     g.keep_src = (q.flags & GS_RANK_KEEP_SRC) ? 1 : 0;
     GS_HIP(hipMemsetAsync(g.counts, 0, (size_t)n_pairs * sizeof(int32_t), st));
     const int64_t blocks = n_pairs / RK_BM + C;          // >= sum over the clusters of ceil(pairs_c / 128)

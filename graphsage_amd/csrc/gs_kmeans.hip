@@ -5,12 +5,12 @@
 //   assign[i] = argmax_j s(i, j), an exact tie to the lowest j          (= argmin_j |x_i - c_j|^2)
 //   dist[i]   = max(0, xsq[i] - 2 s(i, assign[i]))
 //
-// kmeans_assign_kernel.  One workgroup owns 128 table rows and sweeps ALL centroid tiles of 128; the K loop is gs_rank_dev.h
-// (rank_load_tiles, rank_store_tiles, rank_compute: fp32 MFMA, BM = BN = 128, BK = 32, two LDS stages, the one-exit loop of
-// gs_topk.hip), so a (row, centroid) pair goes through the k-ordered chain of gs_rank_count and two bit-identical centroid
-// rows score bit-equal.  Epilogue: after a tile's K loop the next tile's first two stages are requested, and under those
-// loads every lane folds its 2 x 2 x 16 accumulator cells into a running (best score, id) per (tm, e) -- the 32 table rows a
-// lane holds cells of; the two cells of one row (tn = 0, 1) are taken in ascending column, replacement is by strict `>` and
+// kmeans_assign_kernel.  One workgroup owns 128 table rows and sweeps ALL centroid tiles of 128; the K loop is the tile pipeline
+// of gs_rank_dev.h (rank_first_loads, rank_k_loop: fp32 MFMA, BM = BN = 128, BK = 32, two LDS stages), so a (row, centroid)
+// pair goes through the k-ordered chain of gs_rank_count and two bit-identical centroid rows score bit-equal.
+//   Epilogue: after a tile's K loop the next tile's first two stages are requested, and under those loads every lane folds
+// its 2 x 2 x 16 accumulator cells into a running (best score, id) per (tm, e) -- the 32 table rows a lane holds cells of;
+// the two cells of one row (tn = 0, 1) are taken in ascending column, replacement is by strict `>` and
 // the tiles ascend, so within a lane the lowest id of a tie survives.  Nothing is written per tile: no score, no key, no
 // per-slice workspace.  After the last tile the 32 x 64 lane candidates of every row meet once in the (dead) stage buffers,
 // two threads per row pick the best by (score descending, id ascending), and the same threads write assign and dist; the
@@ -26,7 +26,7 @@
 // members in ascending i whatever the chunk length: the result is uniquely defined.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; quoted in profiles/eval_clusters.md):
-// kmeans_assign_kernel 234 vector registers, 84 scalar, no scratch, no spill of either kind, 73,776 B of LDS (the two stage
+// kmeans_assign_kernel 234 vector registers, 90 scalar, no scratch, no spill of either kind, 73,776 B of LDS (the two stage
 // buffers of the sweep and 48 B of partial sums; gs_topk.hip: 77,824 B): two workgroups per CU under __launch_bounds__(256, 2).
 // The running ids are kept as one byte (2 tile + tn) packed four to a register: with one int32 per row slot (32 registers
 // instead of 8) the kernel took all 256 registers and spilled 3 of them to 16 B of scratch.  kmeans_finish_kernel 61
@@ -57,7 +57,7 @@ __device__ __forceinline__ double km_wave_sum(double v) {
 
 // (256, 2): a budget of 256 registers per lane, two workgroups per CU
 __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const KmArgs g) {
-    constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
+    constexpr int BM = RK_BM, BN = RK_BN;
     __shared__ __attribute__((aligned(16))) float smem[2 * RK_STAGE_FLOATS];
     __shared__ double dsumS[4];
     __shared__ int32_t csumS[4];
@@ -71,44 +71,27 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const KmArgs g) {
 
     // ---- operand rows of this thread: 4 table rows (fixed), 4 centroid rows (per tile); 8 threads x float4 span BK
     const int srow = tid >> 3, sk = (tid & 7) * 4;
-    const float* a_row[4];
-    bool a_ok[4];
+    RankOperand A, B;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         const int64_t i = m0 + p * 32 + srow;
-        a_ok[p] = i < g.n;
+        A.ok[p] = i < g.n;
         int64_t r = 0;
-        if (a_ok[p]) {
+        if (A.ok[p]) {
             r = g.rows ? (int64_t)g.rows[i] : i;
             r = r < 0 ? 0 : (r >= g.n_rows ? g.n_rows - 1 : r);      // the caller checked; never a stray read
         }
-        a_row[p] = g.X + r * g.ld + sk;
+        A.row[p] = g.X + r * g.ld + sk;
     }
-    const float* b_row[4];
-    bool b_ok[4];
-    auto centroid_rows = [&](const int tile) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int r = tile * BN + p * 32 + srow;
-            b_ok[p] = r < g.k;
-            b_row[p] = g.C + (int64_t)(b_ok[p] ? r : 0) * g.ldc + sk;
-        }
-    };
 
-    float* As0 = smem;
-    float* Bs0 = smem + BM * KP;
-    float* As1 = smem + RK_STAGE_FLOATS;
-    float* Bs1 = smem + RK_STAGE_FLOATS + BM * KP;
-
-    f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
+    RankRegs ra0, rb0, ra1, rb1;
     auto first_loads = [&](const int tile) {
-        centroid_rows(tile);
-        rank_load_tiles(0, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-        if (BK < d) rank_load_tiles(BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
+        rank_rows(B, g.C, g.ldc, (int64_t)tile * BN, g.k);
+        rank_first_loads(A, B, d, ra0, rb0, ra1, rb1);
     };
     first_loads(0);
 
-    // running best of the 32 table rows this lane holds cells of: row(tm, e) = wm 64 + tm 32 + (e & 3) + 8 (e >> 2) + 4 lh
+    // running best of the 32 table rows this lane holds cells of: row(tm, e) = wm 64 + tm 32 + rank_acc_row(e, lh)
     // The id is kept as the byte 2 tile + tn (k <= 4096: below 64), four to a register: 8 registers where the ids would take 32.
     float best[2][16];
     uint32_t bcode[2][4];
@@ -126,25 +109,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const KmArgs g) {
         const float h1 = c1 < g.k ? 0.5f * g.csq[c1] : __builtin_inff();
 
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-        for (int k0 = 0; k0 < d; k0 += 2 * BK) {
-            rank_store_tiles(ra0, rb0, As0, Bs0, srow, sk);
-            __syncthreads();
-            if (k0 + 2 * BK < d) rank_load_tiles(k0 + 2 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-            rank_compute(As0, Bs0, wm, wn, l31, lh, acc);
-            if (k0 + BK < d) {
-                rank_store_tiles(ra1, rb1, As1, Bs1, srow, sk);
-                __syncthreads();
-                if (k0 + 3 * BK < d) rank_load_tiles(k0 + 3 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
-                rank_compute(As1, Bs1, wm, wn, l31, lh, acc);
-            }
-        }
+        rank_k_loop(A, B, d, smem, ra0, rb0, ra1, rb1, wm, wn, l31, lh, acc);
 
         if (tile + 1 < g.tiles_n) first_loads(tile + 1);
 
@@ -172,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void kmeans_assign_kernel(const KmArgs g) {
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int r = wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+            const int r = wm * 64 + tm * 32 + rank_acc_row(e, lh);
             sc[r * KM_LD + wn * 32 + l31] = best[tm][e];
             const int code = (int)((bcode[tm][e >> 2] >> (8 * (e & 3))) & 0xffu);
             si[r * KM_LD + wn * 32 + l31] = (code >> 1) * BN + wn * 64 + (code & 1) * 32 + l31;

@@ -4,7 +4,7 @@
 //   n_gt[q] = #{w in C_q : <Xq[q], Zc[w]> >  t[q]}        C_q = {0 <= w < n_cand} \ {dst[q]} \ {src[q]} \ filter row of src[q]
 //   n_eq[q] = #{w in C_q : <Xq[q], Zc[w]> == t[q]}
 //
-// Arithmetic: plain fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), the NT tile loop of gs_gemm.hip: both operands
+// Arithmetic: plain fp32 on the matrix cores (v_mfma_f32_32x32x2_f32), the tile pipeline of gs_rank_dev.h: both operands
 // k-contiguous, staged through LDS as direct float4 copies ([row][32 + 4], one ds_read_b128 per 4 k-steps), two LDS stages and
 // two register stages, one barrier per stage.  An MFMA result is a k-ordered fmaf chain whose order (k0 + 4 * (lane >> 5) + i)
 // does not depend on where a row or a column sits in the tile.
@@ -16,7 +16,7 @@
 //
 // Tiling: 256 threads = 4 waves (2 x 2), block tile BM x BN = 128 x 128 (each wave 2 x 2 MFMA tiles of 32 x 32, 64 accumulator
 // registers), BK = 32.  LDS: 2 stages x (128 + 128) rows x 36 floats = 72 KB + 5.5 KB of epilogue state => two workgroups per
-// CU of the 160 KB, one wave of each per SIMD, inside a budget of 256 registers per lane: the compiler reports 229 vector
+// CU of the 160 KB, one wave of each per SIMD, inside a budget of 256 registers per lane: the compiler reports 227 vector
 // registers, no vector spill and no scratch; 18 scalar registers (the argument block is large) are parked in lanes of a
 // vector register.  Measured at the Reddit shape against one workgroup per CU with 512 registers: profiles/rank_full.md.
 // 128 x 128 is the tile of the dense kernels' large form: 32 FLOP per operand byte read from LDS.
@@ -39,8 +39,9 @@
 // slice's first candidate, then it only moves forward).  The epilogue tests the bit, so a filtered cell is skipped with the
 // very score that would have been counted; dst listed in its own filter row just sets the same bit twice.
 //
-// The operand loads and stores, the compute stage, the exclusion-word builder and the slice plan live in gs_rank_dev.h, which
-// gs_topk.hip (the same sweep with a select epilogue) includes too; this kernel's resource report is what it was before.
+// The tile pipeline (operand rows, stage buffers, the first two stage requests, the K loop), the exclusion-word builder, the
+// slice plan and the host's check of the query descriptor live in gs_rank_dev.h, which the other score sweeps include too:
+// gs_topk.hip (select), gs_ivf.hip (inverted-file scan), gs_kmeans.hip (argmax) and gs_infonce.hip (softmax).
 #include "gs_rank_dev.h"
 
 static_assert(sizeof(gs_rank_desc) == 144, "gs_rank_desc layout (mirrored by graphsage_amd/_lib.py)");
@@ -57,9 +58,8 @@ struct RankArgs {
 
 // (256, 2): a budget of 256 registers per lane, two workgroups per CU
 __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
-    constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
-    constexpr int STAGE_FLOATS = RK_STAGE_FLOATS;
-    __shared__ __attribute__((aligned(16))) float smem[2 * STAGE_FLOATS];
+    constexpr int BM = RK_BM, BN = RK_BN;
+    __shared__ __attribute__((aligned(16))) float smem[2 * RK_STAGE_FLOATS];
     __shared__ __attribute__((aligned(16))) uint32_t excl[BM][4];      // bit c of row r: (query r, column c of the tile) is not a candidate
     __shared__ float tq[BM];
     __shared__ int32_t dq[BM], sq[BM];
@@ -97,15 +97,8 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
     __syncthreads();
 
     // ---- operand rows of this thread: 4 query rows (fixed), 4 candidate rows (per tile); 8 threads x float4 span BK
-    const int srow = tid >> 3, sk = (tid & 7) * 4;
-    const float* a_row[4];
-    bool a_ok[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int64_t r = m0 + p * 32 + srow;
-        a_ok[p] = r < g.Q;
-        a_row[p] = g.Xq + (a_ok[p] ? r : 0) * g.ldq + sk;
-    }
+    RankOperand A;
+    rank_rows(A, g.Xq, g.ldq, m0, g.Q);
 
     uint32_t c[2][16];           // packed (gt | eq << 16) per accumulator row, both column tiles of the wave together
 #pragma unroll
@@ -113,75 +106,59 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) c[tm][e] = 0u;
 
-    float* As0 = smem;
-    float* Bs0 = smem + BM * KP;
-    float* As1 = smem + STAGE_FLOATS;
-    float* Bs1 = smem + STAGE_FLOATS + BM * KP;
-
     // tile -1 is the t tile (candidate rows gathered through dst, the diagonal kept), then the slice's candidate tiles
     for (int tile = tile0 - 1; tile < tile1; ++tile) {
         const bool t_tile = tile < tile0;
         const int64_t n0 = (int64_t)tile * BN;
-        const float* b_row[4];
-        bool b_ok[4];
+        RankOperand B;
         if (t_tile) {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                b_ok[p] = true;
-                b_row[p] = g.Zc + (int64_t)dq[p * 32 + srow] * g.ldz + sk;
+                B.ok[p] = true;
+                B.row[p] = g.Zc + (int64_t)dq[p * 32 + (tid >> 3)] * g.ldz + (tid & 7) * 4;
             }
         } else {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const int64_t r = n0 + p * 32 + srow;
-                b_ok[p] = r < g.n_cand;
-                b_row[p] = g.Zc + (b_ok[p] ? r : 0) * g.ldz + sk;
-            }
+            rank_rows(B, g.Zc, g.ldz, n0, g.n_cand);
             if (tid < BM)
                 *reinterpret_cast<uint4*>(&excl[tid][0]) = rank_excl_words(n0, g.n_cand, dq[tid], sq[tid], g.f_col, cur, cend);
         }
 
+        // The pipeline of gs_rank_dev.h written out with a `break` where rank_k_loop has an `if` -- the one kernel that keeps a
+        // loop of its own.  Its accumulators do not outlive the loop into a dump, so the second exit costs no registers (227
+        // either way), and through rank_k_loop the kernel ran 0.2 % to 0.5 % slower than before (profiles/sweep_pipeline.md).
+        // The order of the arithmetic is the same either way.
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-        f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
-        // (the three lambdas stay: with the helpers called directly the compiler's report moves from 229 to 237 registers)
-        auto load_tiles = [&](const int k0, f32x4 (&ra)[4], f32x4 (&rb)[4]) {
-            rank_load_tiles(k0, sk, d, a_row, a_ok, b_row, b_ok, ra, rb);
-        };
-        auto store_tiles = [&](const f32x4 (&ra)[4], const f32x4 (&rb)[4], float* As, float* Bs) {
-            rank_store_tiles(ra, rb, As, Bs, srow, sk);
-        };
+        rank_zero(acc);
+        RankRegs ra0, rb0, ra1, rb1;
+        float* As0 = rank_stage_a(smem, 0);
+        float* Bs0 = rank_stage_b(smem, 0);
+        float* As1 = rank_stage_a(smem, 1);
+        float* Bs1 = rank_stage_b(smem, 1);
+        auto load_tiles = [&](const int k0, RankRegs& ra, RankRegs& rb) { rank_load_tiles(k0, d, A, B, ra, rb); };
+        auto store_tiles = [&](const RankRegs& ra, const RankRegs& rb, float* As, float* Bs) { rank_store_tiles(ra, rb, As, Bs); };
         auto compute = [&](const float* As, const float* Bs) { rank_compute(As, Bs, wm, wn, l31, lh, acc); };
-
-        // the software pipeline of gs_gemm.hip: the global loads of stage s + 2 are in flight while stage s is consumed
         load_tiles(0, ra0, rb0);
-        if (BK < d) load_tiles(BK, ra1, rb1);
-        for (int k0 = 0; k0 < d; k0 += 2 * BK) {
+        if (RK_BK < d) load_tiles(RK_BK, ra1, rb1);
+        for (int k0 = 0; k0 < d; k0 += 2 * RK_BK) {
             store_tiles(ra0, rb0, As0, Bs0);
             __syncthreads();
-            if (k0 + 2 * BK < d) load_tiles(k0 + 2 * BK, ra0, rb0);
+            if (k0 + 2 * RK_BK < d) load_tiles(k0 + 2 * RK_BK, ra0, rb0);
             compute(As0, Bs0);
-            if (k0 + BK >= d) break;
+            if (k0 + RK_BK >= d) break;
             store_tiles(ra1, rb1, As1, Bs1);
             __syncthreads();
-            if (k0 + 3 * BK < d) load_tiles(k0 + 3 * BK, ra1, rb1);
+            if (k0 + 3 * RK_BK < d) load_tiles(k0 + 3 * RK_BK, ra1, rb1);
             compute(As1, Bs1);
         }
 
-        // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
+        // ---- epilogue
         if (t_tile) {
             if (wm == wn) {
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
-                        if ((e & 3) + 8 * (e >> 2) + 4 * lh == l31) tq[wm * 64 + tm * 32 + l31] = acc[tm][tm][e];
+                        if (rank_acc_row(e, lh) == l31) tq[wm * 64 + tm * 32 + l31] = acc[tm][tm][e];
             }
         } else {
             // (the exclusion words were written before the K loop's first barrier)
@@ -189,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
             for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int lr = wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    const int lr = wm * 64 + tm * 32 + rank_acc_row(e, lh);
                     const float tv = tq[lr];
                     const uint2 mw = *reinterpret_cast<const uint2*>(&excl[lr][wn * 2]);
                     uint32_t add = 0u;
@@ -221,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void rank_count_kernel(const RankArgs g) {
                 eq += __shfl_xor(eq, off, 64);
             }
             if (l31 == 0) {
-                const int lr = wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                const int lr = wm * 64 + tm * 32 + rank_acc_row(e, lh);
                 cnt[wn][lr][0] = gt;
                 cnt[wn][lr][1] = eq;
             }
@@ -261,19 +238,10 @@ extern "C" int gs_rank_count(const gs_rank_desc* desc_host, void* stream) {
     const gs_rank_desc& q = *desc_host;
     GS_REQUIRE(q.Q >= 0 && q.n_rows >= 0 && q.n_rows <= 0x7fffffffll && q.n_cand >= 0,
                "gs_rank_count: bad sizes Q=%lld n_rows=%lld n_cand=%lld", (long long)q.Q, (long long)q.n_rows, (long long)q.n_cand);
-    GS_REQUIRE(q.n_cand <= q.n_rows, "gs_rank_count: n_cand=%lld exceeds the table's n_rows=%lld", (long long)q.n_cand,
-               (long long)q.n_rows);
-    GS_REQUIRE(q.d >= 4 && q.d <= 1024 && (q.d & 3) == 0, "gs_rank_count: d=%d must be a multiple of 4 in [4, 1024]", q.d);
-    if (q.Q == 0) return GS_OK;
-    GS_REQUIRE(q.n_rows >= 1, "gs_rank_count: the candidate table is empty (dst needs a row)");
-    GS_CHECK_MAT(q.Xq, q.ldq, "gs_rank_count Xq");
-    GS_CHECK_MAT(q.Zc, q.ldz, "gs_rank_count Zc");
-    GS_REQUIRE(q.ldq >= q.d && q.ldz >= q.d, "gs_rank_count: ld must be >= d");
+    GS_REQUIRE(q.Q == 0 || q.n_rows >= 1, "gs_rank_count: the candidate table is empty (dst needs a row)");
+    const int rc = rank_check_query("gs_rank_count", q);
+    if (rc != GS_OK || q.Q == 0) return rc;
     GS_REQUIRE(q.dst && q.t && q.n_gt && q.n_eq, "gs_rank_count: dst, t, n_gt and n_eq must be non-null");
-    GS_REQUIRE((q.f_rowptr == nullptr) == (q.f_col == nullptr), "gs_rank_count: f_rowptr and f_col go together");
-    GS_REQUIRE(!q.f_rowptr || q.src, "gs_rank_count: a filter is indexed by src, which is null");
-    GS_REQUIRE(q.f_nnz >= 0, "gs_rank_count: f_nnz=%lld", (long long)q.f_nnz);
-    GS_REQUIRE((q.flags & ~GS_RANK_KEEP_SRC) == 0, "gs_rank_count: unknown flags 0x%x", (unsigned)q.flags);
     int64_t tiles_n, tps, slices;
     rank_plan(q.Q, q.n_cand, &tiles_n, &tps, &slices);
     const int64_t need = slices * q.Q * 2 * (int64_t)sizeof(int32_t);

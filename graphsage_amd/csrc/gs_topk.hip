@@ -5,10 +5,10 @@
 //   s(q, w) = <Xq[q], Zc[w]>
 //   out     = the k members of C_q that come first in the total order (s descending, w ascending)
 //
-// The sweep is gs_rank_dev.h, shared with rank_count_kernel: fp32 MFMA (v_mfma_f32_32x32x2_f32), BM = BN = 128, BK = 32, two
-// LDS stages, the slice plan, one 128-bit exclusion word per query row written before a tile's K loop from the sorted filter
-// row with a forward-only cursor.  Same helpers, same k-ordered chain: s(q, w) here is bit-equal to the t that gs_rank_count
-// returns for dst[q] = w.
+// The sweep is gs_rank_dev.h, shared with rank_count_kernel: its tile pipeline (rank_first_loads, rank_k_loop: fp32 MFMA
+// v_mfma_f32_32x32x2_f32, BM = BN = 128, BK = 32, two LDS stages), the slice plan, one 128-bit exclusion word per query row
+// written before a tile's K loop from the sorted filter row with a forward-only cursor.  Same code, same k-ordered chain:
+// s(q, w) here is bit-equal to the t that gs_rank_count returns for dst[q] = w.
 //
 // Order: a key is one uint64 -- high half the score's bits mapped monotonically to unsigned (-0.0f first made +0.0f), low half
 // ~w.  Keys are distinct, a larger key comes first, one unsigned compare is the whole order, and the k largest keys of a set do
@@ -40,13 +40,13 @@
 // Integers and compares only after the MFMA chain: bitwise reproducible.  No atomics, no workgroup waits on another, plain
 // launches on the caller's stream.
 //
-// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; quoted in profiles/topk_full.md):
-// topk_select_kernel 206 vector registers, 102 scalar, no scratch, no spill of either kind, 77,824 B of LDS: two workgroups per
-// CU under __launch_bounds__(256, 2), as the count kernel (229 registers; unchanged by the shared header).  topk_merge_kernel 30
-// registers, 6,144 B of LDS.  The report depends on the K loop having ONE exit (the odd last stage is an `if`, not the count
-// kernel's `break`: with two exits the accumulators, which here outlive the loop into the dump, were kept in two register
-// sets and 49 to 70 registers spilled).  The order of the arithmetic is the same either way.
-#include "gs_topk_dev.h"        // the key, the list code, topk_merge_kernel and its launcher (shared with gs_ivf.hip)
+// Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage; profiles/sweep_pipeline.md, and as they
+// were when the kernel was written in profiles/topk_full.md):
+// topk_select_kernel 204 vector registers, 102 scalar, no scratch, no spill of either kind, 77,824 B of LDS: two workgroups per
+// CU under __launch_bounds__(256, 2), as the count kernel (227 registers).  topk_merge_kernel 30 registers, 6,144 B of LDS.
+// The report depends on the pipeline's K loop having ONE exit (gs_rank_dev.h: with two exits the accumulators, which here
+// outlive the loop into the dump, were kept in two register sets and 49 to 70 registers spilled).
+#include "gs_topk_dev.h"        // the key, the list code, the dump and the offer, the merge (shared with gs_ivf.hip)
 
 static_assert(sizeof(gs_topk_desc) == 144, "gs_topk_desc layout (mirrored by graphsage_amd/_lib.py)");
 static_assert(GS_TOPK_MAX == 128, "the merge kernel ranks two keys per lane");
@@ -63,7 +63,7 @@ struct TopkArgs {
 
 // (256, 2): a budget of 256 registers per lane, two workgroups per CU
 __global__ __launch_bounds__(256, 2) void topk_select_kernel(const TopkArgs g) {
-    constexpr int BM = RK_BM, BN = RK_BN, BK = RK_BK, KP = RK_KP;
+    constexpr int BM = RK_BM, BN = RK_BN;
     __shared__ __attribute__((aligned(16))) float smem[2 * RK_STAGE_FLOATS];
     __shared__ __attribute__((aligned(16))) uint32_t excl[BM][4];      // bit c of row r: (query r, column c of the tile) is not a candidate
     __shared__ uint64_t tauS[BM];
@@ -98,37 +98,14 @@ __global__ __launch_bounds__(256, 2) void topk_select_kernel(const TopkArgs g) {
     __syncthreads();
 
     // ---- operand rows of this thread: 4 query rows (fixed), 4 candidate rows (per tile); 8 threads x float4 span BK
-    const int srow = tid >> 3, sk = (tid & 7) * 4;
-    const float* a_row[4];
-    bool a_ok[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int64_t r = m0 + p * 32 + srow;
-        a_ok[p] = r < g.Q;
-        a_row[p] = g.Xq + (a_ok[p] ? r : 0) * g.ldq + sk;
-    }
-    const float* b_row[4];
-    bool b_ok[4];
-    auto candidate_rows = [&](const int tile) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const int64_t r = (int64_t)tile * BN + p * 32 + srow;
-            b_ok[p] = r < g.n_cand;
-            b_row[p] = g.Zc + (b_ok[p] ? r : 0) * g.ldz + sk;
-        }
-    };
+    RankOperand A, B;
+    rank_rows(A, g.Xq, g.ldq, m0, g.Q);
 
-    float* As0 = smem;
-    float* Bs0 = smem + BM * KP;
-    float* As1 = smem + RK_STAGE_FLOATS;
-    float* Bs1 = smem + RK_STAGE_FLOATS + BM * KP;
-
-    // the software pipeline of gs_gemm.hip, with a tile's first two stages requested before the previous tile's rows are scanned
-    f32x4 ra0[4], rb0[4], ra1[4], rb1[4];
+    // the pipeline of gs_rank_dev.h, with a tile's first two stages requested before the previous tile's rows are scanned
+    RankRegs ra0, rb0, ra1, rb1;
     auto first_loads = [&](const int tile) {
-        candidate_rows(tile);
-        rank_load_tiles(0, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-        if (BK < d) rank_load_tiles(BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
+        rank_rows(B, g.Zc, g.ldz, (int64_t)tile * BN, g.n_cand);
+        rank_first_loads(A, B, d, ra0, rb0, ra1, rb1);
     };
     if (tile0 < tile1) first_loads(tile0);
 
@@ -138,36 +115,10 @@ __global__ __launch_bounds__(256, 2) void topk_select_kernel(const TopkArgs g) {
             *reinterpret_cast<uint4*>(&excl[tid][0]) = rank_excl_words(n0, g.n_cand, -1, sq[tid], g.f_col, cur, cend);
 
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        rank_k_loop(A, B, d, smem, ra0, rb0, ra1, rb1, wm, wn, l31, lh, acc);
 
-        for (int k0 = 0; k0 < d; k0 += 2 * BK) {
-            rank_store_tiles(ra0, rb0, As0, Bs0, srow, sk);
-            __syncthreads();
-            if (k0 + 2 * BK < d) rank_load_tiles(k0 + 2 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra0, rb0);
-            rank_compute(As0, Bs0, wm, wn, l31, lh, acc);
-            if (k0 + BK < d) {
-                rank_store_tiles(ra1, rb1, As1, Bs1, srow, sk);
-                __syncthreads();
-                if (k0 + 3 * BK < d) rank_load_tiles(k0 + 3 * BK, sk, d, a_row, a_ok, b_row, b_ok, ra1, rb1);
-                rank_compute(As1, Bs1, wm, wn, l31, lh, acc);
-            }
-        }
-
-        // ---- epilogue.  C/D layout of the 32x32 MFMA: col = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)
-        __syncthreads();                         // every wave is done with the stage buffers
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    smem[(wm * 64 + tm * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh) * TK_LD + wn * 64 + tn * 32 + l31] = acc[tm][tn][e];
-        __syncthreads();
+        // ---- epilogue
+        topk_dump(acc, smem, wm, wn, l31, lh);
         if (tile + 1 < tile1) first_loads(tile + 1);
 
 #pragma unroll 1
@@ -184,21 +135,10 @@ __global__ __launch_bounds__(256, 2) void topk_select_kernel(const TopkArgs g) {
                     key[i][h] = ((word >> l31) & 1u) ? 0ull : topk_key(s, (uint32_t)(n0 + h * 64 + lane));
                 }
             }
-#pragma unroll
-            for (int i = 0; i < TK_ROWS; ++i) {
-                const int r = r0 + i;
+            topk_offer(key, tau_r, r0, cntS, tauS, g.cap, g.k, lane, [&](const int r) -> uint64_t* {
                 const int64_t q = m0 + r;
-                uint64_t tau = topk_uniform(tau_r[i]);
-                if (q >= g.Q || __ballot(key[i][0] > tau || key[i][1] > tau) == 0ull) continue;      // after warm-up: the usual case
-                int cnt = topk_uniform(cntS[r]);
-                uint64_t* list = g.lists + ((int64_t)slice * g.Q + q) * g.cap;
-                topk_push(list, g.cap, g.k, cnt, tau, key[i][0], lane);
-                topk_push(list, g.cap, g.k, cnt, tau, key[i][1], lane);
-                if (lane == 0) {
-                    cntS[r] = cnt;
-                    tauS[r] = tau;
-                }
-            }
+                return q < g.Q ? g.lists + ((int64_t)slice * g.Q + q) * g.cap : nullptr;
+            });
         }
         // the stage buffers and the exclusion words change hands here
         __syncthreads();
@@ -221,20 +161,10 @@ extern "C" int gs_topk_select(const gs_topk_desc* desc_host, void* stream) {
     const gs_topk_desc& q = *desc_host;
     GS_REQUIRE(q.Q >= 0 && q.n_rows >= 0 && q.n_rows <= 0x7fffffffll && q.n_cand >= 0,
                "gs_topk_select: bad sizes Q=%lld n_rows=%lld n_cand=%lld", (long long)q.Q, (long long)q.n_rows, (long long)q.n_cand);
-    GS_REQUIRE(q.n_cand <= q.n_rows, "gs_topk_select: n_cand=%lld exceeds the table's n_rows=%lld", (long long)q.n_cand,
-               (long long)q.n_rows);
-    GS_REQUIRE(q.d >= 4 && q.d <= 1024 && (q.d & 3) == 0, "gs_topk_select: d=%d must be a multiple of 4 in [4, 1024]", q.d);
     GS_REQUIRE(q.k >= 1 && q.k <= GS_TOPK_MAX, "gs_topk_select: k=%d must lie in [1, %d]", q.k, GS_TOPK_MAX);
-    if (q.Q == 0) return GS_OK;
-    GS_CHECK_MAT(q.Xq, q.ldq, "gs_topk_select Xq");
-    GS_CHECK_MAT(q.Zc, q.ldz, "gs_topk_select Zc");
-    GS_REQUIRE(q.ldq >= q.d && q.ldz >= q.d, "gs_topk_select: ld must be >= d");
+    const int rc = rank_check_query("gs_topk_select", q);
+    if (rc != GS_OK || q.Q == 0) return rc;
     GS_REQUIRE(q.ids && q.scores && q.count, "gs_topk_select: ids, scores and count must be non-null");
-    GS_REQUIRE((q.f_rowptr == nullptr) == (q.f_col == nullptr), "gs_topk_select: f_rowptr and f_col go together");
-    GS_REQUIRE(!q.f_rowptr || q.src, "gs_topk_select: a filter is indexed by src, which is null");
-    GS_REQUIRE(!q.src || q.n_rows >= 1, "gs_topk_select: the candidate table is empty (src needs a row)");
-    GS_REQUIRE(q.f_nnz >= 0, "gs_topk_select: f_nnz=%lld", (long long)q.f_nnz);
-    GS_REQUIRE((q.flags & ~GS_RANK_KEEP_SRC) == 0, "gs_topk_select: unknown flags 0x%x", (unsigned)q.flags);
     int64_t tiles_n, tps, slices;
     rank_plan(q.Q, q.n_cand, &tiles_n, &tps, &slices);
     const int64_t cap = topk_cap(q.k);

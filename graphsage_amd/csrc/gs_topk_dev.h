@@ -1,5 +1,6 @@
 // The select machinery that gs_topk.hip (exhaustive) and gs_ivf.hip (inverted-file scan) share: the uint64 key and its order,
-// the append / compact code of a per-row key list, the merge kernel over [slices][Q][cap] lists and its host launcher.  Both
+// the append / compact code of a per-row key list, the dump of a finished accumulator tile and the offer of its rows' keys to
+// the lists (the epilogue of both scan kernels), the merge kernel over [slices][Q][cap] lists and its host launcher.  Both
 // files run THESE functions, so a (score, id) pair maps to the same key, meets the same compares and is reported with the
 // same bits in either.  The order, the lists and the reasons are in the header comment of gs_topk.hip.
 #pragma once
@@ -68,6 +69,46 @@ __device__ __forceinline__ void topk_push(uint64_t* list, const int cap, const i
     }
     if (key > tau) list[cnt + __popcll(b & ((1ull << lane) - 1ull))] = key;
     cnt += __popcll(b);
+}
+
+// The finished 128 x 128 accumulator tile into the two stage buffers as [128][TK_LD] floats (lane = column on the way in and on
+// the way out: the pad of 1 keeps both free of bank conflicts).  Barriers: every wave is done with the stages; the tile is whole.
+__device__ __forceinline__ void topk_dump(const f32x16 (&acc)[2][2], float* smem, const int wm, const int wn, const int l31,
+                                          const int lh) {
+    __syncthreads();
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+                smem[(wm * 64 + tm * 32 + rank_acc_row(e, lh)) * TK_LD + wn * 64 + tn * 32 + l31] = acc[tm][tn][e];
+    __syncthreads();
+}
+
+// One wave offers the keys of tile rows r0 .. r0 + TK_ROWS - 1 (two per lane and row; tau_r: the rows' thresholds as read with
+// the keys) to the rows' lists: list_of(r) is row r's list, nullptr for a row that does not exist.  A row's length and threshold
+// live in cntS / tauS (LDS, touched by this wave only).  list_of is called behind the ballot: ahead of it, whatever it
+// computes sits on the critical path of every row (the address: 2.8 % of topk_select_kernel; a slot number alone: 1.5 %).
+template <class ListOf>
+__device__ __forceinline__ void topk_offer(const uint64_t (&key)[TK_ROWS][2], const uint64_t (&tau_r)[TK_ROWS], const int r0,
+                                           int32_t* cntS, uint64_t* tauS, const int cap, const int k, const int lane,
+                                           const ListOf list_of) {
+#pragma unroll
+    for (int i = 0; i < TK_ROWS; ++i) {
+        const int r = r0 + i;
+        uint64_t tau = topk_uniform(tau_r[i]);
+        if (__ballot(key[i][0] > tau || key[i][1] > tau) == 0ull) continue;      // after warm-up: the usual case
+        uint64_t* list = list_of(r);
+        if (list == nullptr) continue;
+        int cnt = topk_uniform(cntS[r]);
+        topk_push(list, cap, k, cnt, tau, key[i][0], lane);
+        topk_push(list, cap, k, cnt, tau, key[i][1], lane);
+        if (lane == 0) {
+            cntS[r] = cnt;
+            tauS[r] = tau;
+        }
+    }
 }
 
 // one wave per query: the slices' lists -> the k first keys, in order  (static: every file that includes this launches its own)

@@ -245,8 +245,10 @@ def test_header_binding_and_error_reporting():
     assert "sizeof(gs_kmeans_desc) == 128" in src and "sizeof(gs_kmeans_members_desc) == 72" in src
     # the K loop is the shared sweep, called and not restated
     assert '#include "gs_rank_dev.h"' in src and "__builtin_amdgcn_mfma" not in src
-    for fn in ("rank_load_tiles(", "rank_store_tiles(", "rank_compute("):
+    for fn in ("rank_first_loads(", "rank_k_loop("):
         assert fn in src
+    for own in ("rank_load_tiles(", "rank_store_tiles(", "rank_compute(", "k0"):      # the pipeline's pieces: gs_rank_dev.h alone
+        assert own not in src
 
     out = ctypes.c_int64(0)
     for n in (0, 1, 128, 129, 232965):
