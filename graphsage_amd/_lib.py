@@ -202,6 +202,10 @@ _PROTOS = {
     "gs_kmeans_members": [_P, _P],
     "gs_ivf_ws_bytes": [c_int64, c_int32, c_int32, c_int32, POINTER(c_int64)],
     "gs_ivf_search": [_P, _P],
+    "gs_prop_weights": [_P, _P, c_int64, c_int64, _P, _P, _P],
+    "gs_prop_ws_bytes": [c_int64, c_int32, POINTER(c_int64)],
+    "gs_prop_step": [_P, _P],
+    "gs_prop_correct": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_float, _P, c_int64, _P],
 }
 
 
@@ -457,6 +461,20 @@ class IvfDesc(ctypes.Structure):
 
 IVF_MAX_PROBE = 128                         # GS_IVF_MAX_PROBE
 assert ctypes.sizeof(IvfDesc) == 200       # static_assert in csrc/gs_ivf.hip (passed by pointer, as TopkDesc)
+
+
+class PropDesc(ctypes.Structure):
+    """struct gs_prop_desc (include/graphsage_amd.h)"""
+    _fields_ = [("rowptr", c_void_p), ("col", c_void_p), ("items", c_void_p), ("splits", c_void_p), ("X", c_void_p),
+                ("R", c_void_p), ("w", c_void_p), ("out", c_void_p), ("ws", c_void_p),
+                ("n_rows", c_int64), ("nnz", c_int64), ("n_items", c_int64), ("n_split", c_int64), ("n_slots", c_int64),
+                ("pad", c_int64), ("ldx", c_int64), ("ldr", c_int64), ("ldo", c_int64), ("ws_bytes", c_int64),
+                ("alpha", c_float), ("lo", c_float), ("hi", c_float),
+                ("d", c_int32), ("split_len", c_int32), ("reserved_", c_int32)]
+
+
+PROP_MAX_D = 256                            # GS_PROP_MAX_D
+assert ctypes.sizeof(PropDesc) == 176      # static_assert in csrc/gs_propagate.hip (passed by pointer, as CsrReduceDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

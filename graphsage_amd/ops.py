@@ -1466,6 +1466,68 @@ def ivf_search(Xq, Zc, centers, list_ptr, list_ids, k, nprobe, n_cand=None, src=
     return ids, scores, count, scanned
 
 
+# ------------------------------------------------------------------------------------------ PROP
+PROP_MAX_D = _lib.PROP_MAX_D        # widest table of gs_prop_step / gs_prop_correct
+
+
+def prop_weights(rowptr, col, n_rows, pad, deg=None, w=None, stream=None):
+    """gs_prop_weights: deg[r] = the entries of CSR row r that are not `pad` (deg[pad] = 0), w[r] = fp32(1 / sqrt((double)deg[r])),
+    0 at deg 0.  Returns (deg int32 [n_rows], w float32 [n_rows])."""
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.numel() != n_rows + 1:
+        raise _lib.GraphsageAmdError("prop_weights: the CSR is an int64 rowptr [n_rows + 1] with an int32 col")
+    deg = torch.empty(n_rows, dtype=torch.int32, device=rowptr.device) if deg is None else deg
+    w = torch.empty(n_rows, dtype=torch.float32, device=rowptr.device) if w is None else w
+    if (deg.dtype, w.dtype) != (torch.int32, torch.float32) or deg.numel() != n_rows or w.numel() != n_rows or not (
+            deg.is_contiguous() and w.is_contiguous()):
+        raise _lib.GraphsageAmdError("prop_weights: deg int32 [n_rows] and w float32 [n_rows] must be dense")
+    call("gs_prop_weights", ptr(rowptr), ptr(col), n_rows, pad, ptr(deg), ptr(w), _s(stream))
+    return deg, w
+
+
+def prop_ws_bytes(n_slots, d):
+    """Bytes of the partials workspace gs_prop_step needs for n_slots segments of cut rows at width d."""
+    out = ctypes.c_int64(0)
+    call("gs_prop_ws_bytes", n_slots, d, ctypes.byref(out))
+    return out.value
+
+
+def prop_step(rowptr, col, items, splits, n_rows, split_len, pad, w, X, out, R=None, alpha=1.0, lo=float("-inf"),
+              hi=float("inf"), n_slots=0, ws=None, d=None, stream=None):
+    """gs_prop_step: out[r] = clamp(fmaf(alpha, w[r] * sum_e w[col[e]] * X[col[e]], R[r])) for every row of a planned CSR graph
+    (inference.FullGraph owns the plan: items / splits over all rows, n_slots partial slots), out[pad] = 0; a pad entry adds
+    exactly 0.  X, out, R (nullable): Mats of n_rows rows, out not X; w: float32 [n_rows] (prop_weights); d: the width, X.d
+    unless given."""
+    for name, m in (("X", X), ("out", out), ("R", R)):
+        if m is not None and m.rows < n_rows:
+            raise _lib.GraphsageAmdError("prop_step: %s has %d rows, the graph %d" % (name, m.rows, n_rows))
+    if w.dtype != torch.float32 or w.numel() != n_rows or not w.is_contiguous():
+        raise _lib.GraphsageAmdError("prop_step: w must be a dense float32 vector of n_rows = %d entries" % n_rows)
+    q = _lib.PropDesc()
+    q.rowptr, q.col, q.items, q.splits = ptr(rowptr), ptr(col), ptr(items), ptr(splits)
+    q.X, q.R, q.w, q.out, q.ws = X.ptr, (R.ptr if R is not None else None), ptr(w), out.ptr, ptr(ws)
+    q.n_rows, q.nnz, q.n_items, q.n_split = n_rows, col.numel(), items.shape[0], (splits.shape[0] if splits is not None else 0)
+    q.n_slots, q.pad, q.ldx, q.ldr, q.ldo = n_slots, pad, X.ld, (R.ld if R is not None else 0), out.ld
+    q.ws_bytes = 4 * ws.numel() if ws is not None else 0
+    q.alpha, q.lo, q.hi, q.d, q.split_len = alpha, lo, hi, (X.d if d is None else d), split_len
+    call("gs_prop_step", ctypes.addressof(q), _s(stream))
+    return out
+
+
+def prop_correct(P, E, sigma, out, Y=None, known=None, n=None, stream=None):
+    """gs_prop_correct: out[i] = known[i] ? Y[i] : P[i] + scale_i * E[i] for the first n rows, scale_i = sigma / sum_j |E[i][j]|,
+    replaced by 1 where it is not finite or exceeds 1000.  known: int32 device flags [n]; Y, known None: no row is known."""
+    n = P.rows if n is None else int(n)
+    for name, m in (("P", P), ("E", E), ("out", out), ("Y", Y)):
+        if m is not None and (m.rows < n or m.d != P.d):
+            raise _lib.GraphsageAmdError("prop_correct: %s is [%d, %d], wanted [>= %d, %d]" % (name, m.rows, m.d, n, P.d))
+    if (Y is None) != (known is None) or (known is not None and (known.dtype != torch.int32 or known.numel() < n
+                                                                  or not known.is_contiguous())):
+        raise _lib.GraphsageAmdError("prop_correct: Y comes with a dense int32 vector known of n = %d flags" % n)
+    call("gs_prop_correct", P.ptr, P.ld, E.ptr, E.ld, (Y.ptr if Y is not None else None), (Y.ld if Y is not None else 0),
+         ptr(known), n, P.d, sigma, out.ptr, out.ld, _s(stream))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

@@ -359,6 +359,20 @@ class SupervisedGraphsage(SampleAndAggregate):
         rows, n = inf.request_rows(self, H, S, nodes)
         return self._head_rows(rows, n) + (stats,)
 
+    def correct_and_smooth(self, graph, labels, known, nodes=None, **kw):
+        """propagation.correct_and_smooth over `graph` from this model's exact predictions predict_full(graph) of every node, the
+        `labels` ([N, C]) and the rows `known`; kw: correct_alpha, smooth_alpha, iters.  nodes: the rows of "preds" and
+        "corrected" to return (default: all N, in id order)."""
+        from . import propagation
+        ids = None if nodes is None else np.asarray(nodes, dtype=np.int64).reshape(-1)
+        if ids is not None and ids.size and (ids.min() < 0 or ids.max() >= graph.n_nodes):
+            raise ops._lib.GraphsageAmdError("correct_and_smooth: node ids must lie in [0, %d)" % graph.n_nodes)
+        _, preds = self.predict_full(graph)
+        res = propagation.correct_and_smooth(self.engine, graph, preds, labels, known, **kw)
+        if ids is not None:
+            res["preds"], res["corrected"] = res["preds"][ids], res["corrected"][ids]
+        return res
+
     def _head_rows(self, rows, n):
         """l2_normalize, the prediction Dense and its softmax / sigmoid over the first n rows of `rows`."""
         from . import inference as inf

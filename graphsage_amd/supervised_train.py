@@ -67,7 +67,24 @@ def build_flags(argv=None):
                         '(predict_full) -> val_stats_full.txt / test_stats_full.txt; not for graphsage_seq')
     add_embed_nodes_flag(p)
     add_importance_flags(p)
+    add_propagation_flags(p)
     return p.parse_args(argv)
+
+
+def add_propagation_flags(p):
+    b = lambda v: str(v).lower() in ("1", "true", "yes")
+    p.add_argument('--correct_smooth', type=b, nargs='?', const=True, default=False,
+                   help='after training: Correct and Smooth (autoscale) over the TRUE test graph from the predict_full predictions '
+                        'and the labels of every node that is neither val nor test -> val_stats_cs.txt / test_stats_cs.txt; not '
+                        'for graphsage_seq')
+    p.add_argument('--label_propagation', type=b, nargs='?', const=True, default=False,
+                   help='after training: plain label propagation of the same labels over the same graph (the graph-only '
+                        'baseline; --cs_smooth_alpha, --cs_iters) -> val_stats_lp.txt / test_stats_lp.txt; not for graphsage_seq')
+    p.add_argument('--cs_correct_alpha', type=float, default=0.8, help='alpha of the error propagation of --correct_smooth')
+    p.add_argument('--cs_smooth_alpha', type=float, default=0.8,
+                   help='alpha of the label propagation of --correct_smooth and --label_propagation')
+    p.add_argument('--cs_iters', type=int, default=50, help='propagation steps of --correct_smooth (each phase) and '
+                                                           '--label_propagation')
 
 
 def add_embed_nodes_flag(p):
@@ -164,7 +181,7 @@ def importance_adjacencies(flags, minibatch, n_nodes, device):
 def refuse_full_inference(flags):
     """--full_inference (and --rank_full / --topk_full / --topk_ivf, which rank the embed_full embeddings) has no meaning for the models
     without a full-neighborhood form: say so before any work is done."""
-    for flag in ("full_inference", "rank_full", "topk_full", "topk_ivf", "embed_nodes"):
+    for flag in ("full_inference", "rank_full", "topk_full", "topk_ivf", "embed_nodes", "correct_smooth", "label_propagation"):
         if getattr(flags, flag, False) and flags.model in ('n2v', 'graphsage_seq'):
             raise SystemExit("--%s is not available with --model %s: %s" % (
                 flag, flags.model, "node2vec has no aggregation layers (its embeddings are table rows)" if flags.model == 'n2v'
@@ -252,11 +269,98 @@ def full_graph(minibatch, n_nodes):
     return FullGraph.from_csr(minibatch.test_csr[0], minibatch.test_csr[1], n_nodes)
 
 
-def full_inference_stats(model, minibatch, n_nodes):
-    """Exact inference for every node at once (model.predict_full), scored on the validation and the test nodes."""
+def refuse_propagation(flags):
+    """--correct_smooth / --label_propagation with an alpha or a step count outside the kernel's schedule are refused before any
+    work is done."""
+    if not (getattr(flags, "correct_smooth", False) or getattr(flags, "label_propagation", False)):
+        return
+    from . import propagation
+    from ._lib import GraphsageAmdError
+    try:
+        if flags.correct_smooth:
+            propagation.check_schedule(flags.cs_correct_alpha, flags.cs_iters, "--cs_correct_alpha / --cs_iters")
+        propagation.check_schedule(flags.cs_smooth_alpha, flags.cs_iters, "--cs_smooth_alpha / --cs_iters")
+    except GraphsageAmdError as e:
+        raise SystemExit(str(e))
+
+
+def refuse_propagation_classes(flags, num_classes):
+    """... and a label table wider than the propagation kernel takes, once the data is loaded."""
+    if getattr(flags, "correct_smooth", False) or getattr(flags, "label_propagation", False):
+        from . import propagation
+        from ._lib import GraphsageAmdError
+        try:
+            propagation.check_classes(num_classes, "--correct_smooth / --label_propagation")
+        except GraphsageAmdError as e:
+            raise SystemExit(str(e))
+
+
+def _write_f1_files(tag, stats, duration):
+    """val_stats_<tag>.txt / test_stats_<tag>.txt in the layout of val_stats_full.txt."""
+    with open(log_dir() + "val_stats_%s.txt" % tag, "w") as fp:
+        fp.write("f1_micro={:.5f} f1_macro={:.5f} time={:.5f}".format(stats[0][0], stats[0][1], duration))
+    with open(log_dir() + "test_stats_%s.txt" % tag, "w") as fp:
+        fp.write("f1_micro={:.5f} f1_macro={:.5f}".format(stats[1][0], stats[1][1]))
+
+
+def _val_test_f1(minibatch, scores):
+    return [calc_f1(minibatch.label_matrix[nodes], scores[nodes]) if len(nodes) else (0.0, 0.0)
+            for nodes in (minibatch.val_nodes, minibatch.test_nodes)]
+
+
+def propagation_stats(model, minibatch, n_nodes, preds=None):
+    """--correct_smooth and --label_propagation: over the TRUE test graph (the real edges, also under --sampler padded and
+    --importance_neighbors), from the labels of every node that is neither val nor test.  preds: the predict_full predictions
+    of every node when --full_inference has computed them already."""
+    from . import propagation
+    from .inference import FullGraph
+    graph = FullGraph.from_csr(minibatch.test_csr[0], minibatch.test_csr[1], n_nodes)
+    known = np.ones(n_nodes, dtype=bool)
+    known[minibatch.val_nodes] = False
+    known[minibatch.test_nodes] = False
+    known = np.flatnonzero(known)
+    labels = np.asarray(minibatch.label_matrix, dtype=np.float32)[:n_nodes]          # (the table also has the pad node's row)
+    e = model.engine
+    prop = propagation.Propagator(e, graph)
+    out = {}
+    if FLAGS.correct_smooth:
+        if preds is None:
+            _, preds = model.predict_full(full_graph(minibatch, n_nodes))
+        t0 = time.time()
+        res = propagation.correct_and_smooth(e, graph, preds, labels, known, correct_alpha=FLAGS.cs_correct_alpha,
+                                             smooth_alpha=FLAGS.cs_smooth_alpha, iters=FLAGS.cs_iters, propagator=prop)
+        duration = time.time() - t0
+        base, stats = _val_test_f1(minibatch, preds), _val_test_f1(minibatch, res["preds"])
+        print("Correct and smooth: nodes= %d known= %d classes= %d correct_alpha= %g smooth_alpha= %g iters= %d sigma= %.5f "
+              "base_val_f1_micro= %.5f val_f1_micro= %.5f val_f1_macro= %.5f base_test_f1_micro= %.5f test_f1_micro= %.5f "
+              "test_f1_macro= %.5f time= %.5f" % (
+                  n_nodes, len(known), labels.shape[1], FLAGS.cs_correct_alpha, FLAGS.cs_smooth_alpha, FLAGS.cs_iters,
+                  res["sigma"], base[0][0], stats[0][0], stats[0][1], base[1][0], stats[1][0], stats[1][1], duration))
+        _write_f1_files("cs", stats, duration)
+        out["correct_smooth"] = stats
+    if FLAGS.label_propagation:
+        t0 = time.time()
+        scores = propagation.label_propagation(e, graph, labels, known, alpha=FLAGS.cs_smooth_alpha, iters=FLAGS.cs_iters,
+                                               propagator=prop)
+        duration = time.time() - t0
+        stats = _val_test_f1(minibatch, scores)
+        print("Label propagation: nodes= %d known= %d classes= %d alpha= %g iters= %d val_f1_micro= %.5f val_f1_macro= %.5f "
+              "test_f1_micro= %.5f test_f1_macro= %.5f time= %.5f" % (
+                  n_nodes, len(known), labels.shape[1], FLAGS.cs_smooth_alpha, FLAGS.cs_iters, stats[0][0], stats[0][1],
+                  stats[1][0], stats[1][1], duration))
+        _write_f1_files("lp", stats, duration)
+        out["label_propagation"] = stats
+    return out
+
+
+def full_inference_stats(model, minibatch, n_nodes, keep=None):
+    """Exact inference for every node at once (model.predict_full), scored on the validation and the test nodes.  keep: a dict
+    that receives the predictions under "preds", for what follows."""
     t_test = time.time()
     _, preds = model.predict_full(full_graph(minibatch, n_nodes))
     duration = time.time() - t_test
+    if keep is not None:
+        keep["preds"] = preds
     stats = []
     for nodes in (minibatch.val_nodes, minibatch.test_nodes):
         stats.append(calc_f1(minibatch.label_matrix[nodes], preds[nodes]) if len(nodes) else (0.0, 0.0))
@@ -535,8 +639,11 @@ def train(G, embed_rows=None):
     val_cost, val_f1_mic, val_f1_mac, duration = incremental_evaluate(model, minibatch, FLAGS.batch_size, test=True)
     with open(log_dir() + "test_stats.txt", "w") as fp:
         fp.write("loss={:.5f} f1_micro={:.5f} f1_macro={:.5f}".format(val_cost, val_f1_mic, val_f1_mac))
+    kept = {}
     if FLAGS.full_inference:
-        full_inference_stats(model, minibatch, G.n_nodes)
+        full_inference_stats(model, minibatch, G.n_nodes, keep=kept)
+    if getattr(FLAGS, "correct_smooth", False) or getattr(FLAGS, "label_propagation", False):
+        propagation_stats(model, minibatch, G.n_nodes, preds=kept.get("preds"))
     if embed_rows is not None:
         save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=True)
     return val_f1_mic
@@ -549,10 +656,12 @@ def main(argv=None):
     refuse_dropout(FLAGS)
     refuse_samples(FLAGS)
     refuse_importance(FLAGS)
+    refuse_propagation(FLAGS)
     tokens = read_embed_nodes(FLAGS)
     print("Loading training data..")
     G = load_graph()
     print("Done loading training data..")
+    refuse_propagation_classes(FLAGS, G.num_classes)
     return train(G, embed_nodes_rows(G, tokens, FLAGS.embed_nodes) if tokens is not None else None)
 
 

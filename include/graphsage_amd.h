@@ -1522,6 +1522,61 @@ int gs_ivf_ws_bytes(int64_t Q, int32_t n_clusters, int32_t k, int32_t nprobe, in
 int gs_ivf_search(const gs_ivf_desc* desc_host, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PROP label propagation / Correct and Smooth (Huang et al., ICLR 2021) over a CSR adjacency (csrc/gs_propagate.hip): the
+ *      normalised operator applied to a NARROW table (d = the number of classes), one fused launch per step.
+ *
+ *      gs_prop_weights: for every row r of the CSR (rowptr int64 [n_rows + 1], col int32)
+ *        deg[r] = the number of entries of row r that are not `pad`; a duplicate counts as often as it occurs; deg[pad] = 0
+ *        w[r]   = the fp32 nearest to 1.0 / sqrt((double)deg[r]) (one fp64 square root and division, rounded once); 0 at deg 0
+ *      One wave per row, integer counts only, no atomics.
+ *
+ *      gs_prop_step: one step for every row r < n_rows and column j < d
+ *        s         = w[r] * sum_e w[col[e]] * X[col[e]][j]       e over the row's entries; an entry equal to pad contributes
+ *                                                                exactly 0 (its table row is not read)
+ *        y         = fmaf(alpha, s, R ? R[r][j] : 0)             R: the residual table, nullable
+ *        out[r][j] = min(max(y, lo), hi)                         lo = -inf, hi = +inf: no clamp
+ *        out[pad][:] = 0
+ *      Rows may be directed, hold duplicates and hold pad entries anywhere.  The launch follows the work-item plan of INF
+ *      (items / splits over ALL rows, no window): one wave reduces one item.  With cpad = round_up(d, 4) the wave is cut into
+ *      G = 64 / Lg groups of Lg lanes, Lg = 16 (cpad <= 64), 32 (cpad <= 128), 64 (cpad <= 256); group g takes the entries
+ *      g, g + G, ... of the item in ascending order, a lane holds one float4 of the row and adds with fmaf(w_c, x, acc); the
+ *      groups are then added in one fixed order ((g0 + g2) + (g1 + g3); g0 + g1).  An uncut row is finished by its wave; a cut
+ *      row's plain sum (before w[r]) goes to its slot of ws ([n_slots][cpad] floats, gs_prop_ws_bytes) and a second launch adds
+ *      the partials in slot order and finishes the row.  No float atomics: bitwise repeatable.  Columns d .. cpad - 1 of out are
+ *      written 0; columns at and beyond cpad are not written.  An item, split or column id outside the graph is skipped.
+ *      1 <= d <= GS_PROP_MAX_D (else GS_ENOTSUP); ldx, ldr, ldo >= cpad, out != X, X and R hold n_rows rows (else GS_EINVAL).
+ *      gs_prop_desc is 176 bytes on every target (checked at compile time and by the binding; passed by pointer, not part of
+ *      gs_abi_struct_sizes).
+ *
+ *      gs_prop_correct: the autoscaled correction and the label overwrite in one launch, for every row i < n
+ *        l1     = sum_j |E[i][j]|                 one lane group per row: per lane in column order, then the xor butterfly
+ *        scale  = sigma / l1, replaced by 1 where it is not finite or exceeds 1000
+ *        out[i] = known[i] ? Y[i] : P[i] + scale * E[i]          (fmaf; out may be P)
+ *      known: int32 [n] flags; Y (and known) may be NULL: no row is known.  1 <= d <= GS_PROP_MAX_D, every ld >= cpad.
+ * ------------------------------------------------------------------------------------------- */
+#define GS_PROP_MAX_D 256
+typedef struct gs_prop_desc {
+    const int64_t* rowptr;     /* device [n_rows + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const int64_t* items;      /* device [n_items][4]: the plan of INF over all rows */
+    const int64_t* splits;     /* device [n_split][3]; nullable when n_split == 0 */
+    const float* X;            /* device [n_rows][ldx] */
+    const float* R;            /* device [n_rows][ldr]; nullable */
+    const float* w;            /* device [n_rows] (gs_prop_weights) */
+    float* out;                /* device [n_rows][ldo]; not X */
+    float* ws;                 /* partials of the cut rows; nullable when there are none */
+    int64_t n_rows, nnz, n_items, n_split, n_slots, pad;
+    int64_t ldx, ldr, ldo, ws_bytes;
+    float alpha, lo, hi;
+    int32_t d, split_len, reserved_;       /* reserved_: 0 */
+} gs_prop_desc;
+int gs_prop_weights(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t pad, int32_t* deg, float* w, void* stream);
+int gs_prop_ws_bytes(int64_t n_slots, int32_t d, int64_t* bytes_out_host);
+int gs_prop_step(const gs_prop_desc* desc_host, void* stream);
+int gs_prop_correct(const float* P, int64_t ldp, const float* E, int64_t lde, const float* Y, int64_t ldy, const int32_t* known,
+                    int64_t n, int32_t d, float sigma, float* out, int64_t ldo, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
