@@ -206,6 +206,9 @@ _PROTOS = {
     "gs_prop_ws_bytes": [c_int64, c_int32, POINTER(c_int64)],
     "gs_prop_step": [_P, _P],
     "gs_prop_correct": [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_float, _P, c_int64, _P],
+    "gs_nbr_rank_grid": [c_int64, c_int32, POINTER(c_int64)],
+    "gs_nbr_rank_ws_bytes": [c_int64, c_int64, POINTER(c_int64)],
+    "gs_nbr_rank": [_P, _P],
 }
 
 
@@ -475,6 +478,20 @@ class PropDesc(ctypes.Structure):
 
 PROP_MAX_D = 256                            # GS_PROP_MAX_D
 assert ctypes.sizeof(PropDesc) == 176      # static_assert in csrc/gs_propagate.hip (passed by pointer, as CsrReduceDesc)
+
+
+class NbrRankDesc(ctypes.Structure):
+    """struct gs_nbr_rank_desc (include/graphsage_amd.h)"""
+    _fields_ = [(n, c_void_p) for n in ("rowptr", "col", "q", "deg", "f_rowptr", "f_col", "group_ptr", "group_src", "dst", "t",
+                                        "n_gt", "n_eq", "ws")] + \
+               [(n, c_int64) for n in ("n_nodes", "n_groups", "n_queries", "ws_stride", "ws_bytes")] + \
+               [(n, c_int32) for n in ("kind", "tile", "max_workgroups", "reserved_")]
+
+
+NBR_TILE, NBR_MIN_TILE, NBR_MAX_TILE = 8192, 64, 16384      # GS_NBR_TILE, GS_NBR_MIN_TILE, GS_NBR_MAX_TILE
+NBR_PARTNER_CHUNK, NBR_CURSORS = 64, 2048                   # GS_NBR_PARTNER_CHUNK, GS_NBR_CURSORS
+NBR_SUM, NBR_JACCARD = 0, 1                                 # GS_NBR_SUM, GS_NBR_JACCARD
+assert ctypes.sizeof(NbrRankDesc) == 160   # static_assert in csrc/gs_nbr_rank.hip (passed by pointer, as PropDesc)
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOS.keys()) + ["gs_last_error", "gs_abi_version"])
 

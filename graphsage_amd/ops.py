@@ -1528,6 +1528,71 @@ def prop_correct(P, E, sigma, out, Y=None, known=None, n=None, stream=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ NBR
+NBR_TILE = _lib.NBR_TILE                        # candidate ids per LDS tile unless the caller overrides it
+NBR_MIN_TILE, NBR_MAX_TILE = _lib.NBR_MIN_TILE, _lib.NBR_MAX_TILE
+NBR_PARTNER_CHUNK = _lib.NBR_PARTNER_CHUNK      # partners of one source that are ranked per pass over a tile
+NBR_CURSORS = _lib.NBR_CURSORS                  # neighbors of a source whose row cursors fit in LDS
+NBR_KINDS = {"sum": _lib.NBR_SUM, "jaccard": _lib.NBR_JACCARD}
+
+
+def nbr_rank_grid(n_groups, max_workgroups=0):
+    """Workgroups gs_nbr_rank launches for n_groups source groups (max_workgroups > 0 caps them)."""
+    out = ctypes.c_int64(0)
+    call("gs_nbr_rank_grid", n_groups, max_workgroups, ctypes.byref(out))
+    return out.value
+
+
+def nbr_rank_ws_bytes(n_workgroups, max_src_degree):
+    """Bytes of the cursor workspace gs_nbr_rank wants for sources of up to max_src_degree neighbors (0 while they fit in LDS)."""
+    out = ctypes.c_int64(0)
+    call("gs_nbr_rank_ws_bytes", n_workgroups, max_src_degree, ctypes.byref(out))
+    return out.value
+
+
+def nbr_rank(rowptr, col, n_nodes, group_ptr, group_src, dst, q=None, deg=None, f_rowptr=None, f_col=None, kind="sum", tile=0,
+             max_workgroups=0, max_src_degree=0, t=None, n_gt=None, n_eq=None, ws=None, stream=None):
+    """gs_nbr_rank over a SIMPLE CSR graph (rows strictly ascending, ids in [0, n_nodes), validated by the caller -- see
+    link_heuristics.SimpleGraph): for the queries dst (int32, grouped by source: group g = group_src[g] with
+    dst[group_ptr[g]:group_ptr[g + 1]]) t = s(src, dst) with s(u, x) = sum of q[w] over w in N(u) with x in N(w) (q uint32 [N]; None:
+    1), and the numbers n_gt / n_eq of candidates (all nodes but dst, src and the filter row of src) that rank above / tie.
+    kind "jaccard" ranks by s / (deg[u] + deg[x] - s) (deg int32 [N], q None).  max_src_degree: the longest source row (sizes the
+    cursor workspace).  Returns (t uint32, n_gt int32, n_eq int32) in group order."""
+    dev = rowptr.device
+    G, Q = group_src.numel(), dst.numel()
+    if rowptr.dtype != torch.int64 or col.dtype != torch.int32 or rowptr.numel() != n_nodes + 1:
+        raise _lib.GraphsageAmdError("nbr_rank: the CSR is an int64 rowptr [n_nodes + 1] with an int32 col")
+    if group_ptr.dtype != torch.int64 or group_ptr.numel() != G + 1 or group_src.dtype != torch.int32 or dst.dtype != torch.int32:
+        raise _lib.GraphsageAmdError("nbr_rank: group_ptr int64 [groups + 1], group_src and dst int32")
+    if kind not in NBR_KINDS:
+        raise _lib.GraphsageAmdError("nbr_rank: kind must be one of %s" % sorted(NBR_KINDS))
+    for name, v in (("q", q), ("deg", deg)):           # q: the uint32 bits in an int32 tensor
+        if v is not None and (v.numel() != n_nodes or not v.is_contiguous() or v.dtype != torch.int32):
+            raise _lib.GraphsageAmdError("nbr_rank: %s must be a dense int32 vector of n_nodes = %d entries" % (name, n_nodes))
+    if (f_rowptr is None) != (f_col is None) or (f_rowptr is not None and (
+            f_rowptr.dtype != torch.int64 or f_rowptr.numel() != n_nodes + 1 or f_col.dtype != torch.int32)):
+        raise _lib.GraphsageAmdError("nbr_rank: the filter is an int64 f_rowptr [n_nodes + 1] with an int32 f_col, or neither")
+    t = torch.zeros(Q, dtype=torch.int32, device=dev) if t is None else t
+    n_gt = torch.zeros(Q, dtype=torch.int32, device=dev) if n_gt is None else n_gt
+    n_eq = torch.zeros(Q, dtype=torch.int32, device=dev) if n_eq is None else n_eq
+    for name, v in (("t", t), ("n_gt", n_gt), ("n_eq", n_eq)):
+        if v.numel() != Q or v.element_size() != 4 or not v.is_contiguous():
+            raise _lib.GraphsageAmdError("nbr_rank: %s must be a dense 32-bit vector of %d entries" % (name, Q))
+    grid = nbr_rank_grid(G, max_workgroups)
+    stride = int(max_src_degree) if max_src_degree > NBR_CURSORS else 0
+    if stride and ws is None:
+        ws = torch.empty(nbr_rank_ws_bytes(grid, stride) // 4, dtype=torch.int32, device=dev)
+    d = _lib.NbrRankDesc()
+    d.rowptr, d.col, d.q, d.deg, d.f_rowptr, d.f_col = ptr(rowptr), ptr(col), ptr(q), ptr(deg), ptr(f_rowptr), ptr(f_col)
+    d.group_ptr, d.group_src, d.dst, d.t, d.n_gt, d.n_eq, d.ws = (ptr(group_ptr), ptr(group_src), ptr(dst), ptr(t), ptr(n_gt),
+                                                                   ptr(n_eq), ptr(ws) if stride else None)
+    d.n_nodes, d.n_groups, d.n_queries, d.ws_stride = n_nodes, G, Q, stride
+    d.ws_bytes = 4 * ws.numel() if (stride and ws is not None) else 0
+    d.kind, d.tile, d.max_workgroups, d.reserved_ = NBR_KINDS[kind], tile, max_workgroups, 0
+    call("gs_nbr_rank", ctypes.addressof(d), _s(stream))
+    return t, n_gt, n_eq
+
+
 # ------------------------------------------------------------------------------------------ graphs / events
 class Stream(object):
     """A non-blocking HIP stream created by the library (capturable into a hipGraph)."""

@@ -71,6 +71,10 @@ def build_flags(argv=None):
     p.add_argument('--rank_full', type=b, nargs='?', const=True, default=False,
                    help='after val.npy: rank every held-out edge (both directions) against ALL nodes with the exact embeddings '
                         'on the test graph, known edges filtered (rank_full) -> rank_full.txt; not for n2v / graphsage_seq')
+    p.add_argument('--rank_baselines', default='',
+                   help='comma list of cn | aa | ra | jaccard, or all: after val.npy (and --rank_full), rank the same held-out '
+                        'edges by these neighbor-overlap scores of the TRUE test graph, known edges filtered '
+                        '(link_heuristics.rank_neighbors) -> rank_baseline_<kind>.txt; reads the graph only: every --model')
     p.add_argument('--topk_full', type=int, default=0,
                    help='K > 0: after val.npy, the K best-scoring partners of every node among ALL nodes with the exact '
                         'embeddings on the test graph, known edges filtered (topk_full) -> topk_full.npy / '
@@ -349,6 +353,38 @@ def save_full_ranking(model, minibatch, out_dir):
     return res
 
 
+def rank_baseline_kinds(flags):
+    """The kinds --rank_baselines lists, in its order; an unknown name is refused before any work is done."""
+    from .link_heuristics import parse_kinds
+    try:
+        return parse_kinds(getattr(flags, "rank_baselines", ""))
+    except ValueError as e:
+        raise SystemExit("--rank_baselines: %s" % e)
+
+
+def save_rank_baselines(minibatch, out_dir, kinds):
+    """rank_baseline_<kind>.txt: the edges of --rank_full (every held-out edge, both directions) ranked against all N nodes by the
+    neighbor-overlap scores of the TRUE test graph (minibatch.test_csr, whatever the sampler reads), its edges filtered."""
+    from . import engine as eng
+    from . import link_heuristics as lh
+    graph = lh.SimpleGraph.from_csr(minibatch.test_csr[0], minibatch.test_csr[1], minibatch.G.n_nodes)
+    filt = graph.rank_filter()
+    edges = np.asarray(minibatch.val_edges, dtype=np.int64).reshape(-1, 2)
+    edges = np.concatenate([edges, edges[:, ::-1]], axis=0)
+    if not os.path.exists(out_dir):
+        os.makedirs(out_dir)
+    out = {}
+    for kind in kinds:
+        t0 = time.time()
+        res = lh.rank_neighbors(eng.get_engine(), graph, edges, kind=kind, filt=filt)
+        line = lh.result_line(kind, res, time.time() - t0)
+        print(line)
+        with open(out_dir + "rank_baseline_%s.txt" % kind, "w") as fp:
+            fp.write(line + "\n")
+        out[kind] = res
+    return out
+
+
 def topk_full_line(res):
     """The line --topk_full prints."""
     ids = res["ids"]
@@ -531,6 +567,8 @@ def train(G, context_pairs, embed_rows=None):
             save_full_embeddings(model, minibatch, log_dir())
         if FLAGS.rank_full:
             save_full_ranking(model, minibatch, log_dir())
+        if rank_baseline_kinds(FLAGS):
+            save_rank_baselines(minibatch, log_dir(), rank_baseline_kinds(FLAGS))
         if FLAGS.topk_full:
             save_full_topk(model, minibatch, log_dir(), FLAGS.topk_full)
         if FLAGS.topk_ivf:
@@ -541,6 +579,8 @@ def train(G, context_pairs, embed_rows=None):
             save_eval_classifier(G, log_dir())
         if FLAGS.eval_clusters:
             save_eval_clusters(G, log_dir())
+    elif rank_baseline_kinds(FLAGS):                 # the baselines read the graph alone: no embeddings needed
+        save_rank_baselines(minibatch, log_dir(), rank_baseline_kinds(FLAGS))
     if embed_rows is not None:
         from .supervised_train import save_embed_nodes
         save_embed_nodes(model, minibatch, G.n_nodes, embed_rows, log_dir(), supervised=False)
@@ -603,6 +643,7 @@ def main(argv=None):
     refuse_eval_classifier(FLAGS)
     refuse_eval_clusters(FLAGS)
     refuse_topk_ivf(FLAGS)
+    rank_baseline_kinds(FLAGS)
     tokens = st.read_embed_nodes(FLAGS)
     print("Loading training data..")
     st.FLAGS = argparse.Namespace(synthetic=FLAGS.synthetic, train_prefix=FLAGS.train_prefix, sigmoid=False)

@@ -1577,6 +1577,64 @@ int gs_prop_correct(const float* P, int64_t ldp, const float* E, int64_t lde, co
                     int64_t n, int32_t d, float sigma, float* out, int64_t ldo, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * NBR  link-ranking baselines from neighbor overlap (csrc/gs_nbr_rank.hip): common neighbors, Adamic-Adar, resource allocation
+ *      and the Jaccard ratio of every edge (src, dst), ranked against ALL nodes in the launch that forms the scores.
+ *
+ *      The CSR (rowptr int64 [n_nodes + 1], col int32) is a SIMPLE graph: every row strictly ascending, ids in [0, n_nodes),
+ *      no self loops; it need not be symmetric.  N(w) is the stored row of w.  With the weights q (uint32 [n_nodes]; NULL: 1)
+ *        s(u, x) = sum of q[w] over the w in N(u) with x in N(w)            (row u of A diag(q) A; every sum < 2^32)
+ *      GS_NBR_SUM ranks by s.  GS_NBR_JACCARD (q NULL, deg = the row lengths, int32 [n_nodes]) ranks by the ratio
+ *      s / (deg[u] + deg[x] - s), 0 where s = 0; two ratios a / b and c / e compare as a * e against c * b in uint64, never in
+ *      floating point.
+ *
+ *      The queries come grouped by source: group g is the source group_src[g] with the partners dst[group_ptr[g] ..
+ *      group_ptr[g + 1]) (n_queries = group_ptr[n_groups]; a source may own several groups, a partner may repeat, dst == src is
+ *      legal).  For query k of source u, over the candidates x in [0, n_nodes) with x != dst[k], x != u and x not in the filter
+ *      row of u (f_rowptr int64 [n_nodes + 1], f_col int32: rows strictly ascending, ids in [0, n_nodes); both NULL: no filter)
+ *        t[k]    = s(u, dst[k])                                              (the numerator, also for GS_NBR_JACCARD)
+ *        n_gt[k] = the candidates that rank above dst[k], n_eq[k] = those that tie with it
+ *      A candidate that shares no neighbor scores 0 and is counted, not visited.  Every id is the caller's to validate: the
+ *      kernel reads rows of whatever id it is given.
+ *
+ *      One workgroup takes the groups blockIdx, blockIdx + grid, ...; grid = min(n_groups, CUs * GS_NBR_WG_PER_CU,
+ *      max_workgroups if > 0) (gs_nbr_rank_grid).  The candidate ids are cut into tiles of `tile` ids (a power of two in
+ *      [GS_NBR_MIN_TILE, GS_NBR_MAX_TILE]; 0: GS_NBR_TILE) whose uint32 scores live in LDS; only tiles that a row N(w) touches
+ *      are visited, in ascending order.  Every w in N(u) keeps the offset of its row's first unconsumed id: in LDS for up to
+ *      GS_NBR_CURSORS rows, else in ws (grid * ws_stride uint32, ws_stride >= the longest source row; gs_nbr_rank_ws_bytes),
+ *      else (ws NULL or too narrow) the offset is searched again per tile.  Integer LDS atomics only: no floating point, no
+ *      global atomics, no score vector in memory; the results do not depend on the grid, the tile or the run.
+ *      gs_nbr_rank_desc is 160 bytes on every target (checked at compile time and by the binding; passed by pointer).
+ * ------------------------------------------------------------------------------------------- */
+#define GS_NBR_TILE 8192
+#define GS_NBR_MIN_TILE 64
+#define GS_NBR_MAX_TILE 16384
+#define GS_NBR_PARTNER_CHUNK 64
+#define GS_NBR_CURSORS 2048
+#define GS_NBR_WG_PER_CU 3
+#define GS_NBR_SUM 0
+#define GS_NBR_JACCARD 1
+typedef struct gs_nbr_rank_desc {
+    const int64_t* rowptr;     /* device [n_nodes + 1] */
+    const int32_t* col;        /* device [nnz] */
+    const uint32_t* q;         /* device [n_nodes]; NULL: every weight 1 (required NULL for GS_NBR_JACCARD) */
+    const int32_t* deg;        /* device [n_nodes]; GS_NBR_JACCARD only */
+    const int64_t* f_rowptr;   /* device [n_nodes + 1]; nullable with f_col */
+    const int32_t* f_col;
+    const int64_t* group_ptr;  /* device [n_groups + 1] */
+    const int32_t* group_src;  /* device [n_groups] */
+    const int32_t* dst;        /* device [n_queries], in group order */
+    uint32_t* t;               /* device [n_queries], in group order */
+    int32_t* n_gt;             /* device [n_queries] */
+    int32_t* n_eq;             /* device [n_queries] */
+    uint32_t* ws;              /* cursors of sources with more than GS_NBR_CURSORS neighbors; nullable */
+    int64_t n_nodes, n_groups, n_queries, ws_stride, ws_bytes;
+    int32_t kind, tile, max_workgroups, reserved_;      /* reserved_: 0 */
+} gs_nbr_rank_desc;
+int gs_nbr_rank_grid(int64_t n_groups, int32_t max_workgroups, int64_t* grid_out_host);
+int gs_nbr_rank_ws_bytes(int64_t n_workgroups, int64_t max_src_degree, int64_t* bytes_out_host);
+int gs_nbr_rank(const gs_nbr_rank_desc* desc_host, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side graph ingestion (C++, multithreaded): edge list -> CSR. Replaces the networkx loops of
  * minibatch.py:227-259 for the CSR engine (N2 "next" row).  All pointers are HOST pointers.
  * keep_mask_host (nullable, per edge) drops edges (train_removed / val-test endpoints).
